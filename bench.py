@@ -10,13 +10,29 @@ min_pair_freq=2 (coverage 0.995, unk 0 = the reference Python defaults) on a 10 
 UTF-8 corpus from the committed generator (seed 3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|...] [--layout types|stream]
+                    [--dump-outputs DIR] [--full]
 
-Legs beside the timed steps (all on the same corpus):
+A plain run does what the headline figure needs and no more: corpus (generated once per machine),
+load, W warm-up steps, K timed steps, one JSON line (``value`` = merges/s over the K steps,
+``ms_per_step``, the step's own counters under ``merge_loop``).  ``--dump-outputs DIR`` writes what
+the last timed step computed -- what a caller of ``train()`` + ``save()`` receives -- as float64
+``DIR/num_merges.npy`` (train()'s return value), ``DIR/merges.npy`` (the .model's (left, right,
+new id) rows) and ``DIR/vocab_freq.npy`` (the .vocab's frequency column, one per token id).  The
+corpus comes from the seeded generator, so the same arguments give the same inputs in every run.
+
+``--full`` adds the legs beside the timed steps (all on the same corpus, all after the timed
+region; the options that size them, --cpu-seconds, --pair-count-reps, --encode-reps,
+--device-leg-steps, --no-cpu-baseline, only matter with it):
 * ``roofline``: K1 ``k_pair_hist`` over the corpus in the stream layout (every occurrence as
   int32 tokens, the north star's flat token array; 4 B/token + 12 B/tile), HIP events on the
   trainer stream, against the 8 TB/s HBM peak; ``traffic`` from the committed PMC passes.
-* ``merge_loop``: the dominant kernel of the timed step (the persistent merge loop), which is
-  bound by the per-merge round trip, not by bandwidth: µs per merge, device dispatch -> flag.
+* ``merge_loop`` (in every run: the timed steps' own counters): the dominant kernel of the timed
+  step (the persistent merge loop), which is bound by the per-merge round trip, not by bandwidth:
+  µs per merge, device dispatch -> flag.
+* ``parity_fullsize``: the step's .model/.vocab md5 against the committed full-size oracle run;
+  ``tiebreak_device_leg``: the opt-in device selection on the same corpus; ``load.later_load_s``: a
+  second load of the same file; ``hbm_achievable``: the library's streaming read/copy probe;
+  ``encode``: the encoder over the same corpus with the model just trained.
 * ``cpu_baseline``: oracle/bpe_oracle (the reference-faithful CPU restatement) on one host core,
   started AFTER the timed region (the host replay is most of the merge chain, so the baseline
   must not share the host while it runs), train() capped at --cpu-seconds.  ``value`` is the
@@ -41,7 +57,7 @@ GPU, rank r on device r) unless WORLD_SIZE is already set (the driver's own torc
 * ``replicas`` (opt-in): N INDEPENDENT jobs, every rank trains its own replica of the workload;
   ``value`` = merges of all ranks / max-over-ranks time, ``scaling`` "weak".  Not a scaling of
   one training.
-The K1 leg counts every rank's copy (replicas) or shard of the stream and reports aggregate GB/s.
+The K1 leg (--full) counts every rank's copy (replicas) or shard of the stream and reports aggregate GB/s.
 Rank 0 prints one JSON line.
 """
 import argparse
@@ -715,6 +731,34 @@ def tiebreak_report(st, merges, elapsed, args, out_prefix):
     }
 
 
+def vocab_freqs(model, vocab):
+    """The .vocab's frequency column, one per token id.  Record i = token i as a C string (NUL
+    bytes vanish) + " " + freq + "\n" (bpe.cpp:417); the spellings follow from the .model."""
+    import numpy as np
+    toks = [bytes([b]) for b in range(256)]
+    for a, b, _ in np.fromfile(model, dtype="<i4").reshape(-1, 3):
+        toks.append(toks[a] + toks[b])
+    vb, pos, freq = open(vocab, "rb").read(), 0, []
+    for tok in toks:
+        pos += len(tok.replace(b"\0", b"")) + 1
+        end = vb.index(b"\n", pos)
+        freq.append(int(vb[pos:end]))
+        pos = end + 1
+    return freq
+
+
+def dump_outputs(outdir, last_merges, model, vocab):
+    """--dump-outputs: what the caller of the timed path holds after its last step, as float64
+    arrays (ids, counts and frequencies are integers below 2^53, so the conversion is exact):
+    train()'s return value and the two files save() writes, decoded."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    ops = np.fromfile(model, dtype="<i4").reshape(-1, 3)
+    np.save(os.path.join(outdir, "num_merges.npy"), np.array([last_merges], dtype=np.float64))
+    np.save(os.path.join(outdir, "merges.npy"), ops.astype(np.float64))
+    np.save(os.path.join(outdir, "vocab_freq.npy"), np.array(vocab_freqs(model, vocab), dtype=np.float64))
+
+
 def hbm_probe_leg(device=0, nbytes=4 << 30, reps=10):
     """Achievable HBM bandwidth on this box: streaming read and copy kernels
     of the library (shred_hbm_probe), beside the nominal 8 TB/s peak."""
@@ -766,14 +810,20 @@ def main():
                     help="merge selection: exact (the reference's heap replay, bit-exact files; default) or device "
                          "(opt-in K5 mode: every merge selected on the GPU, ties to the smaller pair key)")
     ap.add_argument("--bytes", type=int, default=0, help="override the corpus size (testing)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beside them: full-size parity, device tiebreak "
+                         "leg, second load, K1 roofline, encoder, HBM probe, CPU baselines (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64): num_merges, merges, "
+                         "vocab_freq")
     ap.add_argument("--device-leg-steps", type=int, default=2,
-                    help="untimed leg after the timed steps: tiebreak=device trains on the same corpus (0 = skip)")
+                    help="--full: untimed leg after the timed steps: tiebreak=device trains on the same corpus (0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--encode-reps", type=int, default=5, help="encoder leg repetitions (0 = skip)")
+    ap.add_argument("--encode-reps", type=int, default=5, help="--full: encoder leg repetitions (0 = skip)")
     ap.add_argument("--no-pin", action="store_true", help="do not keep the host loop on one L3 domain")
     ap.add_argument("--pair-count-reps", type=int, default=10,
-                    help="K1 roofline leg on the stream layout of the same corpus (0: skip)")
+                    help="--full: K1 roofline leg on the stream layout of the same corpus (0: skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rank bookkeeping only (no GPU, no corpus): rank 0 prints the ranks it saw")
     args = ap.parse_args()
@@ -939,9 +989,10 @@ def main():
     barrier()
     torch.cuda.synchronize()
     start = time.perf_counter()
-    merges = 0
+    merges = last_merges = 0
     for _ in range(args.steps):
-        merges += train_step()
+        last_merges = train_step()
+        merges += last_merges
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - start
@@ -958,12 +1009,18 @@ def main():
         all_merges = int(tm.item())
     st = t.stats()
     tmpd = os.environ.get("TMPDIR", "/tmp")
-    t._save(t.trainer, os.path.join(tmpd, f"bench_r{rank}.model").encode(),
-            os.path.join(tmpd, f"bench_r{rank}.vocab").encode())
+    # the last step's files: the --full legs and the tiebreak=device report read them,
+    # --dump-outputs decodes them (rank 0)
+    if args.full or args.dump_outputs or args.tiebreak == "device":
+        t._save(t.trainer, os.path.join(tmpd, f"bench_r{rank}.model").encode(),
+                os.path.join(tmpd, f"bench_r{rank}.vocab").encode())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_merges, os.path.join(tmpd, f"bench_r{rank}.model"),
+                     os.path.join(tmpd, f"bench_r{rank}.vocab"))
     # untimed leg: the opt-in tiebreak=device mode on the same loaded corpus and box (not the
     # reference's merge order, so never `value`): one warm train, then --device-leg-steps timed
     device_leg = None
-    if (rank == 0 and world == 1 and args.tiebreak == "exact" and args.layout == "types"
+    if (args.full and rank == 0 and world == 1 and args.tiebreak == "exact" and args.layout == "types"
             and args.device_leg_steps > 0):
         try:
             t.set_option("tiebreak", "device")
@@ -989,7 +1046,7 @@ def main():
     # process -- the first after the corpus was generated when gen_s > 0, with the file's page-cache
     # pages fresh -- and later loads (the pinned ring kept, pages warm) are faster
     later_load_s = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             t1 = time.time()
             load(path)
@@ -998,7 +1055,7 @@ def main():
             later_load_s = None
     # the CPU baseline starts only now: the timed steps ran with the host to themselves
     cpu_h = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu_h = cpu_baseline_start(cfg, path, args.cpu_seconds)
         except Exception as e:  # the GPU number stands on its own
@@ -1007,7 +1064,7 @@ def main():
 
     # K1 HBM leg (the metric's "pair-count HBM GB/s"): every rank counts its stream copy / shard
     pair_count = None
-    if args.pair_count_reps > 0:
+    if args.full and args.pair_count_reps > 0:
         try:
             pair_count = pair_count_leg(cfg, path, args.pair_count_reps, device=dev, dist=dist,
                                         shard=one_job)
@@ -1015,7 +1072,7 @@ def main():
             pair_count = {"error": repr(e)}
 
     encode = None
-    if args.encode_reps > 0 and rank == 0:
+    if args.full and args.encode_reps > 0 and rank == 0:
         try:
             encode = encode_leg(os.path.join(tmpd, f"bench_r{rank}.model"), os.path.join(tmpd, f"bench_r{rank}.vocab"),
                                 cfg["unk"], path, args.encode_reps, device=dev, cfg_name=args.config)
@@ -1042,6 +1099,7 @@ def main():
             "n_gpus": min(world, ndev),
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": "strong" if one_job else "weak",
@@ -1109,7 +1167,7 @@ def main():
             result["tiebreak_device"] = tiebreak_report(st, merges, elapsed, args, os.path.join(tmpd, f"bench_r{rank}"))
         if device_leg is not None:
             result["tiebreak_device_leg"] = device_leg
-        case = fullsize_case(case_name) if case_name else None
+        case = fullsize_case(case_name) if (case_name and args.full) else None
         if case and case["recipe"]["bytes"] == cfg["bytes"] and args.tiebreak == "exact":
             result["config"]["corpus_md5_expected"] = case["corpus_md5"]
             result["config"]["unique_bytes"] = case["unique_bytes"]
@@ -1136,13 +1194,14 @@ def main():
                                               "(merge_loop.resident, merge_loop.index)")
         if encode is not None:
             result["encode"] = encode
-        try:
-            result["hbm_achievable"] = hbm_probe_leg(device=dev)
-            if (result.get("pair_count") or {}).get("achieved"):
-                result["pair_count"]["frac_of_achievable_read"] = (
-                    result["pair_count"]["achieved"] / world / result["hbm_achievable"]["read_GBps"])
-        except Exception as e:
-            result["hbm_achievable"] = {"error": repr(e)}
+        if args.full:
+            try:
+                result["hbm_achievable"] = hbm_probe_leg(device=dev)
+                if (result.get("pair_count") or {}).get("achieved"):
+                    result["pair_count"]["frac_of_achievable_read"] = (
+                        result["pair_count"]["achieved"] / world / result["hbm_achievable"]["read_GBps"])
+            except Exception as e:
+                result["hbm_achievable"] = {"error": repr(e)}
         if cpu_h is not None:
             try:
                 if "error" in cpu_h:

@@ -44,6 +44,27 @@ def test_bench_single_rank_dry_run():
     assert rep["n_gpus"] == 1 and [r["rank"] for r in rep["ranks"]] == [0]
 
 
+@pytest.mark.parametrize("name", ["small_v300", "adv_unk0", "mixed2m_v4000"])
+def test_dump_outputs_decodes_the_saved_files(name, tmp_path):
+    """--dump-outputs: float64 arrays holding exactly train()'s count, the .model's rows and the
+    .vocab's frequency column (adv_unk0: tokens with NUL bytes, which the .vocab spells without)."""
+    import numpy as np
+    from conftest import GOLDEN
+    from encode_ref import model_merges, token_bytes, vocab_freqs
+    sys.path.insert(0, REPO)
+    import bench
+    model, vocab = os.path.join(GOLDEN, name, "model.bin"), os.path.join(GOLDEN, name, "vocab.txt")
+    merges = model_merges(open(model, "rb").read())
+    bench.dump_outputs(str(tmp_path / "out"), len(merges), model, vocab)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["merges", "num_merges", "vocab_freq"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["num_merges"].tolist() == [len(merges)]
+    assert got["merges"].shape == merges.shape and np.array_equal(got["merges"], merges)
+    freqs = vocab_freqs(open(vocab, "rb").read(), token_bytes(merges))
+    assert np.array_equal(got["vocab_freq"].astype(np.uint64), freqs)
+
+
 def test_merge_loop_report_accounting():
     sys.path.insert(0, REPO)
     import bench
