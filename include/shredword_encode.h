@@ -63,6 +63,45 @@ int64_t shred_encode_device(ShredEncoder* enc, const void* text, size_t n, void*
  * (nothing is written past cap), or -1 for an id outside [0, 256 + num_merges).  Host only. */
 int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint8_t* out, size_t cap);
 
+/* ---- token byte offsets and per-line id offsets ("offset mapping", dataset rows) ----------
+ *
+ * Ids come out in text order and no token spans a delimiter.  Id x covers len(x) source bytes:
+ * 1 for an id below 256 (a byte's symbol; negative ids such as unk_id = -1 included), and
+ * len(first[m]) + len(second[m]) for 256 + m.  The lengths follow from the merge list alone, so
+ * they also hold for bytes the byte map sends to unk_id.  For a text of n bytes with T ids:
+ *
+ *   starts[k]    int64 byte offset in `text` of the first byte of token k; its end is
+ *                starts[k] + len(ids[k]).  Token k begins a word iff k == 0 or
+ *                starts[k] != starts[k-1] + len(ids[k-1]).
+ *   lines        split on byte 10 only ('\r' is a word delimiter already, so CRLF text works):
+ *                L = count('\n') + (n > 0 && text[n-1] != '\n').
+ *   line_off     L + 1 int64 entries, line_off[0] = 0, line_off[L] = T; line i holds
+ *                ids[line_off[i] : line_off[i+1]] for i in [0, L).  A line of only delimiters is
+ *                an empty row.  n == 0 gives L = 0 and line_off = [0].
+ *
+ * The ids are exactly those of shred_encode on the same text.  The passes run on the GPU behind
+ * the encode; their scratch (8 B per id + 32 B per 4096 text bytes) is allocated on the first
+ * spans call and freed with the encoder, so shred_encode's footprint is unchanged.
+ */
+
+/* 256 + num_merges source-byte lengths (ids < 256: 1; saturating at INT32_MAX).  Returns 0, or -1
+ * when cap is smaller than 256 + num_merges.  Host only. */
+int shred_encoder_token_lengths(const ShredEncoder* enc, int32_t* out, size_t cap);
+
+/* shred_encode plus, optionally, starts (NULL or cap int64) and line_off (NULL, or line_cap >=
+ * lines + 1 int64).  *num_lines (may be NULL) receives L.  Returns the id count; -1/-2/-3 as
+ * shred_encode, -2 also when line_cap is too small (then *num_lines holds the L that is needed
+ * and nothing is written to line_off); -4 when the byte map holds an id >= 256 (a mapped byte
+ * could not be told from a merged token, so lengths are undefined). */
+int64_t shred_encode_spans(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap,
+                           int64_t* starts, int64_t* line_off, size_t line_cap, size_t* num_lines);
+
+/* The same on device buffers; kernel_ms (NULL or 2 doubles): [0] the encode passes as in
+ * shred_encode_device, [1] the span passes. */
+int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n, void* out, size_t cap,
+                                  void* starts, void* line_off, size_t line_cap, size_t* num_lines,
+                                  void* stream, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

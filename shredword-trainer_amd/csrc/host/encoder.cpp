@@ -4,6 +4,8 @@
 // (encode_device.hip).  There is no host encoder: without a device the calls fail.
 #include "shredword_encode.h"
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -38,6 +40,8 @@ struct ShredEncoder {
   std::vector<int32_t> first, second;
   int32_t byte_map[256];
   std::vector<std::string> tokens;  // bytes of every id (256 + merges)
+  std::vector<int32_t> lens;        // source bytes of every id, from the merge list alone
+  bool spans_ok = true;             // no byte maps to an id >= 256
   std::unique_ptr<shred::EncodeDevice> dev;
 };
 
@@ -65,6 +69,10 @@ ShredEncoder* make(std::vector<int32_t> first, std::vector<int32_t> second, cons
   e->tokens.resize(256 + M);
   for (int b = 0; b < 256; ++b) e->tokens[b] = std::string(1, (char)b);
   for (size_t m = 0; m < M; ++m) e->tokens[256 + m] = e->tokens[first[m]] + e->tokens[second[m]];
+  e->lens.assign(256 + M, 1);
+  for (size_t m = 0; m < M; ++m)
+    e->lens[256 + m] = (int32_t)std::min<int64_t>((int64_t)e->lens[first[m]] + e->lens[second[m]], INT32_MAX);
+  for (int b = 0; b < 256; ++b) e->spans_ok = e->spans_ok && e->byte_map[b] < 256;
   std::string why;
   e->dev.reset(shred::EncodeDevice::create(device, shred::enc_build_table(first, second), e->byte_map, &why));
   if (!e->dev) {
@@ -187,6 +195,28 @@ int64_t shred_encode_device(ShredEncoder* enc, const void* text, size_t n, void*
                             double* kernel_ms) {
   if (!enc || (n && (!text || !out))) return -1;
   return enc->dev->encode((const uint8_t*)text, n, (int32_t*)out, cap, stream, kernel_ms);
+}
+
+int shred_encoder_token_lengths(const ShredEncoder* enc, int32_t* out, size_t cap) {
+  if (!enc || !out || cap < enc->lens.size()) return -1;
+  std::memcpy(out, enc->lens.data(), enc->lens.size() * sizeof(int32_t));
+  return 0;
+}
+
+int64_t shred_encode_spans(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap,
+                           int64_t* starts, int64_t* line_off, size_t line_cap, size_t* num_lines) {
+  if (!enc || (n && (!text || !out))) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_spans_host(text, n, out, cap, starts, line_off, line_cap, num_lines, enc->lens);
+}
+
+int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n, void* out, size_t cap, void* starts,
+                                  void* line_off, size_t line_cap, size_t* num_lines, void* stream,
+                                  double* kernel_ms) {
+  if (!enc || (n && (!text || !out))) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_spans((const uint8_t*)text, n, (int32_t*)out, cap, (int64_t*)starts, (int64_t*)line_off,
+                                line_cap, num_lines, enc->lens, stream, kernel_ms);
 }
 
 int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint8_t* out, size_t cap) {

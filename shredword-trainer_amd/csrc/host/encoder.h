@@ -39,10 +39,32 @@ class EncodeDevice {
   // Calls that fell back from the word cache to the direct path (overflow or hash collision).
   uint64_t fallbacks() const { return fallbacks_; }
 
+  // encode() plus the span passes (encode_spans.hip): starts (nullptr or cap int64) and line_off
+  // (nullptr or line_cap int64) on the device, as include/shredword_encode.h defines them.
+  // lens: the 256 + M source-byte lengths of the ids (host; uploaded on the first call).
+  // kernel_ms: nullptr or 2 doubles (encode passes, span passes).  Returns as encode(); -2 also
+  // when line_cap < lines + 1 (*num_lines is set, line_off untouched).
+  int64_t encode_spans(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts, int64_t* line_off,
+                       size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens, void* stream,
+                       double* kernel_ms);
+  // The same on host buffers, in the pieces of encode_host.
+  int64_t encode_spans_host(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts,
+                            int64_t* line_off, size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens);
+
  private:
   EncodeDevice() = default;
   bool reserve(size_t n, std::string* why);
   bool reserve_host(size_t n);
+  // Span passes over n text bytes and their T ids (both on the device): starts[k] = start_base +
+  // byte offset, line[q + 1] = id_base + id offset of the line after the q-th '\n' (line[0] is
+  // not written; line_cap entries).  *newlines / *last_byte: the text's '\n' count and last byte.
+  // Returns 0, -1 on a device error, -2 when line_cap < newlines + 1 (whole: < lines + 1, the
+  // caller writes line[lines]); nothing is written then.
+  int span_passes(const uint8_t* text, size_t n, const int32_t* ids, size_t T, int64_t* starts, int64_t* line,
+                  size_t line_cap, uint64_t start_base, uint64_t id_base, bool whole,
+                  const std::vector<int32_t>& lens, void* stream, size_t* newlines, uint8_t* last_byte, double* ms);
+  bool reserve_spans(size_t n, size_t T, const std::vector<int32_t>& lens);
+  void free_spans();  // called by the destructor
   int device_ = 0;
   void* stream_ = nullptr;      // hipStream_t
   uint64_t* table_ = nullptr;
@@ -71,6 +93,20 @@ class EncodeDevice {
   int32_t* dout_ = nullptr;
   void* ev_[4] = {nullptr, nullptr, nullptr, nullptr};
   uint64_t fallbacks_ = 0;
+  // span passes (encode_spans.hip): allocated on the first spans call, never by encode()
+  int32_t* sp_lens_ = nullptr;     // 256 + M token lengths
+  size_t sp_chunks_ = 0;           // chunks sp_cnt_ holds
+  uint64_t* sp_cnt_ = nullptr;     // 4 x chunks: non-delimiter / '\n' counts, their inclusive sums
+  size_t sp_ids_ = 0;              // ids sp_prefix_ holds
+  uint64_t* sp_prefix_ = nullptr;  // P[k]: source bytes of the ids before k
+  void* sp_tmp_ = nullptr;         // hipCUB scan scratch
+  size_t sp_tmp_bytes_ = 0;
+  uint64_t* sp_host_ = nullptr;    // pinned: '\n' total, last text byte
+  void* sp_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  // host-path staging of the span outputs
+  size_t sp_hstarts_cap_ = 0, sp_hline_cap_ = 0;
+  int64_t* sp_hstarts_ = nullptr;
+  int64_t* sp_hline_ = nullptr;
 };
 
 }  // namespace shred

@@ -154,3 +154,12 @@ lib.shred_encode_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_siz
 lib.shred_encode_device.restype = c_int64
 lib.shred_decode.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t]
 lib.shred_decode.restype = c_int64
+# token byte offsets and per-line id offsets
+lib.shred_encoder_token_lengths.argtypes = [Encoder, POINTER(c_int32), c_size_t]
+lib.shred_encoder_token_lengths.restype = c_int
+lib.shred_encode_spans.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                   POINTER(c_size_t)]
+lib.shred_encode_spans.restype = c_int64
+lib.shred_encode_spans_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
+                                          c_size_t, POINTER(c_size_t), c_void_p, POINTER(c_double)]
+lib.shred_encode_spans_device.restype = c_int64

@@ -68,20 +68,34 @@ class BPEEncoder:
         lib.shred_encoder_info(self.enc, None, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
         return out
 
+    @property
+    def token_lengths(self) -> np.ndarray:
+        """Source bytes each id covers: int32, 256 + num_merges entries (ids below 256: 1)."""
+        out = np.empty(256 + self.num_merges, dtype=np.int32)
+        if lib.shred_encoder_token_lengths(self.enc, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), out.size):
+            raise RuntimeError("token_lengths failed")
+        return out
+
     @staticmethod
     def _check(r: int) -> int:
         if r == -3:
             raise ValueError(f"a word is longer than {MAX_WORD} bytes")
+        if r == -4:
+            raise ValueError("the byte map holds an id >= 256: token lengths are undefined")
         if r < 0:
             raise RuntimeError(f"encode failed (code {r})")
         return r
 
-    def encode(self, text) -> np.ndarray:
-        """bytes / str / uint8 array -> int32 ids of every word, in text order."""
+    @staticmethod
+    def _host_text(text) -> np.ndarray:
         if isinstance(text, str):
             text = text.encode("utf-8")
-        buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) \
+        return np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) \
             else np.ascontiguousarray(text, dtype=np.uint8)
+
+    def encode(self, text) -> np.ndarray:
+        """bytes / str / uint8 array -> int32 ids of every word, in text order."""
+        buf = self._host_text(text)
         out = np.empty(max(1, buf.size), dtype=np.int32)
         r = self._check(lib.shred_encode(self.enc, buf.ctypes.data, buf.size, out.ctypes.data, out.size))
         return out[:r].copy()
@@ -104,6 +118,56 @@ class BPEEncoder:
         r = self._check(lib.shred_encode_device(self.enc, text.data_ptr(), n, out.data_ptr(), out.numel(),
                                                 ctypes.c_void_p(st), ctypes.byref(ms)))
         return out[:r], ms.value
+
+    def _spans_host(self, text, want_starts, want_lines):
+        buf = self._host_text(text)
+        out = np.empty(max(1, buf.size), dtype=np.int32)
+        starts = np.empty(out.size, dtype=np.int64) if want_starts else None
+        line = np.empty(np.count_nonzero(buf == 10) + 2, dtype=np.int64) if want_lines else None
+        nl = ctypes.c_size_t()
+        r = self._check(lib.shred_encode_spans(self.enc, buf.ctypes.data, buf.size, out.ctypes.data, out.size,
+                                               None if starts is None else starts.ctypes.data,
+                                               None if line is None else line.ctypes.data,
+                                               0 if line is None else line.size, ctypes.byref(nl)))
+        return (out[:r].copy(), None if starts is None else starts[:r].copy(),
+                None if line is None else line[:nl.value + 1].copy())
+
+    def encode_lines(self, text):
+        """-> (ids, line_offsets): line i (split on '\\n' only) holds ids[line_offsets[i]:line_offsets[i + 1]];
+        int64, lines + 1 entries, where a text not ending in '\\n' has a last line of its own."""
+        ids, _, line = self._spans_host(text, False, True)
+        return ids, line
+
+    def encode_spans(self, text, lines: bool = False):
+        """-> (ids, starts) or (ids, starts, line_offsets).  starts[k] (int64) is the byte offset in
+        the text of token k's first byte; the token ends at starts[k] + token_lengths[max(ids[k], 0)]
+        (an id below 256 covers 1 byte), and begins a word iff k == 0 or it does not start where
+        token k - 1 ended."""
+        ids, starts, line = self._spans_host(text, True, lines)
+        return (ids, starts, line) if lines else (ids, starts)
+
+    def encode_spans_device(self, text, starts: bool = True, lines: bool = True, stream=None):
+        """text: 1-D uint8 torch tensor on the encoder's GPU -> (ids, starts or None, line_offsets or
+        None, (encode_ms, spans_ms)): int32 / int64 / int64 tensor views on the text's device."""
+        import torch
+        if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_cuda or not text.is_contiguous():
+            raise ValueError("text must be a contiguous 1-D uint8 CUDA tensor")
+        if text.device.index != self.device:
+            raise ValueError(f"text is on {text.device}, the encoder on cuda:{self.device}")
+        n = text.numel()
+        out = torch.empty(max(1, n), dtype=torch.int32, device=text.device)
+        st_t = torch.empty(max(1, n), dtype=torch.int64, device=text.device) if starts else None
+        ln_t = torch.empty(int((text == 10).sum().item()) + 1 + 1, dtype=torch.int64, device=text.device) \
+            if lines else None
+        ms = (ctypes.c_double * 2)()
+        nl = ctypes.c_size_t()
+        st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
+        r = self._check(lib.shred_encode_spans_device(
+            self.enc, text.data_ptr(), n, out.data_ptr(), out.numel(),
+            None if st_t is None else st_t.data_ptr(), None if ln_t is None else ln_t.data_ptr(),
+            0 if ln_t is None else ln_t.numel(), ctypes.byref(nl), ctypes.c_void_p(st), ms))
+        return (out[:r], None if st_t is None else st_t[:r], None if ln_t is None else ln_t[:nl.value + 1],
+                (ms[0], ms[1]))
 
     def decode(self, ids) -> bytes:
         """Concatenated bytes of the ids (whitespace between words is not restored)."""

@@ -1,5 +1,6 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps]     (SHREDWORD_LIB picks the build)"""
+                                   python enc_bench.py run CORPUS DIR [reps] [spans]   (SHREDWORD_LIB picks the build)
+With a trailing `spans`, run also times encode_spans_device (token starts + line offsets)."""
 import os
 import subprocess
 import sys
@@ -22,8 +23,12 @@ if mode == "prepare":
     t._save(t.trainer, os.path.join(d, "m.model").encode(), os.path.join(d, "m.vocab").encode())
     t.destroy()
 else:
-    d = sys.argv[3]
-    reps = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+    args = sys.argv[3:]
+    spans = args[-1] == "spans"
+    if spans:
+        args = args[:-1]
+    d = args[0]
+    reps = int(args[1]) if len(args) > 1 else 5
     import torch
     from shredword.encoder import BPEEncoder
     enc = BPEEncoder(os.path.join(d, "m.model"), os.path.join(d, "m.vocab"), unk_id=0)
@@ -32,5 +37,12 @@ else:
     ids, _ = enc.encode_device(text, out)
     ms = sorted(enc.encode_device(text, out)[1] for _ in range(reps))
     print(os.environ.get("SHREDWORD_LIB", "default"), "ids", ids.numel(), "ms", ms[len(ms) // 2],
-          "GB/s", text.numel() / ms[len(ms) // 2] / 1e6, flush=True)
+          "GB/s", text.numel() / ms[len(ms) // 2] / 1e6, "min", ms[0], "max", ms[-1], flush=True)
+    if spans:
+        del out
+        enc.encode_spans_device(text)  # first call: allocates the span scratch
+        runs = sorted((enc.encode_spans_device(text)[3] for _ in range(reps)), key=lambda t: t[1])
+        encode_ms, spans_ms = sorted(t[0] for t in runs)[reps // 2], runs[reps // 2][1]
+        print("spans: encode_ms", encode_ms, "spans_ms", spans_ms, "ratio", spans_ms / encode_ms,
+              "spans min", runs[0][1], "max", runs[-1][1], flush=True)
     enc.destroy()
