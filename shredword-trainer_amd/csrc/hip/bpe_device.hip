@@ -1,237 +1,33 @@
-// MI355X (gfx950) kernels of the BPE merge loop and the Device class that drives them.
+// MI355X (gfx950) launch path of the BPE merge loop and the part of the Device class that owns
+// the tables and chooses between the merge paths.
 //
 // Integer-only, HBM/LDS-bound work (no MFMA).  Every kernel walks the tiled token stream of
 // device.h with 256-thread workgroups (4 wave64s), 16 consecutive tokens per lane, one 4096-token
 // chunk per iteration; a tile longer than one chunk (a word of > 4095 tokens) is walked chunk by
 // chunk with carries, so no word length is special.
 //
-//   k_pair_count   K1  weighted pair histogram + first touch     (reference bpe.cpp:187-206)
 //   k_merge        K2+K3 match (a,b), emit the 4 neighbour deltas per occurrence, rewrite the
 //                  chunk compacted in place                      (reference bpe.cpp:259-296)
 //   k_collect      K4  touched delta slots -> host records       (FreqChangeMap, bpe.cpp:9-50)
-//   k_token_freq   K6  final weighted token histogram            (reference bpe.cpp:409-415)
+//   k_unmerge      rollback of a chain's unconfirmed merges
 //
-// Deltas and pair counts are staged in per-workgroup LDS hash tables and spilled to HBM tables
+// Device's other methods: pair_count.hip (K1, K6, probes), resident_loop.hip (k_resident);
+// hip_common.h holds what the units share.
+//
+// Deltas are staged in per-workgroup LDS hash tables and spilled to HBM tables
 // with 64-bit atomics (sum) and atomicMin (first touch), so the reduction is order-free and the
 // result bit-identical run to run.
-#include <hip/hip_runtime.h>
-#include <thread>
-
-#ifndef SHRED_MAX_GROUPS
-#define SHRED_MAX_GROUPS 256
-#endif
-#ifndef SHRED_DELTA_LDS
-#define SHRED_DELTA_LDS 2048
-#endif
-#ifndef SHRED_DENSE_TOK
-#define SHRED_DENSE_TOK 32768
-#endif
-#ifndef SHRED_SIG_BITS
-#define SHRED_SIG_BITS 8192
-#endif
-
 #include <algorithm>
-#include <atomic>
-#include <type_traits>
 #include <cstring>
-#include <stdexcept>
-#include <string>
+#include <iterator>
 
-#include "../host/common.h"
 #include "../host/device.h"
 #include "../host/dist.h"
+#include "hip_common.h"
 
 namespace shred {
 
-#define HIP_OK(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      std::fprintf(stderr, "[ERROR]\t HIP %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), \
-                   __FILE__, __LINE__);                                                     \
-      std::fflush(stderr);                                                                  \
-      std::abort();                                                                         \
-    }                                                                                       \
-  } while (0)
-
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kPer = 16;
-constexpr int kChunk = kThreads * kPer;  // 4096 tokens = 16 KiB per chunk
-constexpr int kPairLds = 2048;           // per-workgroup pair-count staging slots
-constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
-constexpr unsigned long long kEmpty64 = ~0ull;
-constexpr int32_t kPad = INT32_MIN;      // beyond the tile; also looks like a header
-constexpr size_t kStreamPad = kChunk + 64;  // elements allocated past the stream (whole-chunk reads)
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool is_hdr(int32_t t) { return t < kHeaderLimit; }
-__device__ __forceinline__ uint32_t hdr_rank(int32_t t) { return (uint32_t)(t - kHeaderBase); }
-
-__device__ __forceinline__ u64 mix64(u64 k) {
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
-
-// Host-visible writes.  Plain stores, published by one system-scope release (L2 write-back)
-// before the flag: measured on MI355X, write-through system stores (sc0 sc1, SHRED_SYS_STORES)
-// are one small PCIe write each and made a merge 2-8x slower, while a flag behind plain stores
-// without the release let the host read stale records.
-#ifdef SHRED_SYS_STORES
-__device__ __forceinline__ void sys_store(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void sys_store(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-#else
-__device__ __forceinline__ void sys_store(uint32_t* p, uint32_t v) { *p = v; }
-__device__ __forceinline__ void sys_store(unsigned long long* p, unsigned long long v) { *p = v; }
-#endif
-// Raises a host-visible flag after this lane's (and, behind a barrier, its workgroup's) writes.
-__device__ __forceinline__ void sys_flag(uint32_t* flag, uint32_t v) {
-#ifdef SHRED_SYS_STORES
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-  __threadfence_system();
-  __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
-}
-__device__ __forceinline__ void sys_record(void* rec, uint32_t key, unsigned long long sum, unsigned long long ft) {
-  unsigned long long* r = static_cast<unsigned long long*>(rec);
-  sys_store(r, (unsigned long long)key);
-  sys_store(r + 1, sum);
-  sys_store(r + 2, ft);
-}
-
-// One exclusive block scan of a packed header key (max) and a counter (sum) over 256 lanes.
-struct ScanLds {
-  u64 hdr[4];
-  int cnt[4];
-};
-
-__device__ __forceinline__ void block_scan_hdr_cnt(u64 hdr, int cnt, ScanLds& s, u64* hdr_excl, int* cnt_excl,
-                                                   u64* hdr_tot, int* cnt_tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  u64 h = hdr;
-  int c = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    u64 hy = __shfl_up(h, d, 64);
-    int cy = __shfl_up(c, d, 64);
-    if (lane >= d) {
-      h = hy > h ? hy : h;
-      c += cy;
-    }
-  }
-  if (lane == 63) {
-    s.hdr[w] = h;
-    s.cnt[w] = c;
-  }
-  __syncthreads();
-  u64 hp = 0;
-  int cp = 0;
-  for (int i = 0; i < w; ++i) {
-    hp = s.hdr[i] > hp ? s.hdr[i] : hp;
-    cp += s.cnt[i];
-  }
-  u64 ht = 0;
-  int ct = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ht = s.hdr[i] > ht ? s.hdr[i] : ht;
-    ct += s.cnt[i];
-  }
-  u64 hx = __shfl_up(h, 1, 64);
-  int cx = __shfl_up(c, 1, 64);
-  if (lane == 0) {
-    hx = 0;
-    cx = 0;
-  }
-  *hdr_excl = hx > hp ? hx : hp;
-  *cnt_excl = cx + cp;
-  *hdr_tot = ht;
-  *cnt_tot = ct;
-  __syncthreads();
-}
-
-// ---- wave-level data movement on DPP (gfx9 row / wave shifts and row broadcasts): a few cycles
-// each instead of an LDS round trip per __shfl (ds_bpermute).
-template <int kCtrl, int kRowMask = 0xf, bool kBound = true>
-__device__ __forceinline__ uint32_t dpp32(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, kCtrl, kRowMask, 0xf, kBound);
-}
-template <int kCtrl, int kRowMask = 0xf, bool kBound = true>
-__device__ __forceinline__ u64 dpp64(u64 x) {
-  const uint32_t lo = dpp32<kCtrl, kRowMask, kBound>((uint32_t)x);
-  const uint32_t hi = dpp32<kCtrl, kRowMask, kBound>((uint32_t)(x >> 32));
-  return ((u64)hi << 32) | lo;
-}
-constexpr int kDppWaveShl1 = 0x130;  // lane i <- lane i + 1 (lane 63 <- 0)
-constexpr int kDppWaveShr1 = 0x138;  // lane i <- lane i - 1 (lane 0 <- 0)
-__device__ __forceinline__ int32_t wave_next(int32_t x) { return (int32_t)dpp32<kDppWaveShl1>((uint32_t)x); }
-__device__ __forceinline__ uint32_t wave_prev(uint32_t x) { return dpp32<kDppWaveShr1>(x); }
-__device__ __forceinline__ u64 wave_prev64(u64 x) { return dpp64<kDppWaveShr1>(x); }
-
-// Inclusive wave scans (sum / max, identity 0): row shifts 1, 2, 4, 8, then row broadcasts 15, 31.
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t x) {
-  x += dpp32<0x111>(x);
-  x += dpp32<0x112>(x);
-  x += dpp32<0x114>(x);
-  x += dpp32<0x118>(x);
-  x += dpp32<0x142, 0xa, false>(x);
-  x += dpp32<0x143, 0xc, false>(x);
-  return x;
-}
-__device__ __forceinline__ u64 max64(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 wave_scan_max64(u64 x) {
-  x = max64(x, dpp64<0x111>(x));
-  x = max64(x, dpp64<0x112>(x));
-  x = max64(x, dpp64<0x114>(x));
-  x = max64(x, dpp64<0x118>(x));
-  x = max64(x, dpp64<0x142, 0xa, false>(x));
-  x = max64(x, dpp64<0x143, 0xc, false>(x));
-  return x;
-}
-__device__ __forceinline__ uint32_t lane_read(uint32_t x, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)x, lane);
-}
-__device__ __forceinline__ u64 lane_read64(u64 x, int lane) {
-  return ((u64)lane_read((uint32_t)(x >> 32), lane) << 32) | lane_read((uint32_t)x, lane);
-}
-
-// Loads this lane's 16 tokens of chunk [cs, cs+cl) (kPad beyond cl) as four unconditional
-// 16-byte loads: tiles start 16-byte aligned and the stream is padded by kStreamPad elements, so
-// reading a whole chunk from any tile start stays inside the allocation.  Branch-free, all four
-// loads are in flight together (a bounds-checked form compiled to one wait per quad).
-__device__ __forceinline__ void load_chunk(const int32_t* base, uint32_t cs, uint32_t cl, int p0, int32_t (&v)[kPer]) {
-  const int4* q = reinterpret_cast<const int4*>(base + cs + p0);
-  int4 x[kPer / 4];
-#pragma unroll
-  for (int k = 0; k < kPer / 4; ++k) x[k] = q[k];
-#pragma unroll
-  for (int k = 0; k < kPer / 4; ++k) {
-    v[4 * k] = p0 + 4 * k < (int)cl ? x[k].x : kPad;
-    v[4 * k + 1] = p0 + 4 * k + 1 < (int)cl ? x[k].y : kPad;
-    v[4 * k + 2] = p0 + 4 * k + 2 < (int)cl ? x[k].z : kPad;
-    v[4 * k + 3] = p0 + 4 * k + 3 < (int)cl ? x[k].w : kPad;
-  }
-}
-
-// Token following this lane's 16 (from the next lane, or from memory at a wave edge).
-__device__ __forceinline__ int32_t next_token(const int32_t* base, uint32_t cs, uint32_t len, int p0, int32_t v0) {
-  int32_t nx = wave_next(v0);
-  const int32_t m = base[cs + p0 + kPer];  // inside the padded allocation; used by lane 63 only
-  if ((threadIdx.x & 63) == 63) nx = (cs + p0 + kPer < len) ? m : kPad;
-  return nx;
-}
 
 // ------------------------------------------------------------------------------------------
 // K2+K3(+K4): merge scan.
@@ -247,26 +43,15 @@ __device__ __forceinline__ int32_t next_token(const int32_t* base, uint32_t cs, 
 // place, and (for single-chunk tiles) the tile's signature is rebuilt from the compacted chunk.
 // Completion: the last workgroup (per-XCD sharded tickets) turns the touched delta slots into host
 // records and raises a host-visible flag, so one launch + one flag wait is a merge's device side.
-constexpr int kWaveTok = 64 * kPer;  // 1024 tokens per wave chunk
-constexpr int kWaves = kThreads / 64;
-constexpr int kDeltaLdsW = SHRED_DELTA_LDS;
 constexpr uint32_t kFusedCollectMax = 4096;  // beyond this the host launches k_collect
 constexpr uint32_t kNeedCollect = 0x80000000u;
 constexpr uint32_t kTimingStride = 8;
 constexpr uint32_t kInlineTiles = 768;     // candidate tiles that fit the kernel arguments
 constexpr int kGroup = 4;                  // tiles walked together per wave (loads in flight)
-// LDS staging index skew: lane l touches positions 16 l + j together, which unskewed all fall in
-// two of the 32 banks; i + i / 16 gives a stride of 17 words, conflict-free.
-__device__ __forceinline__ int SK(int i) { return i + (i >> 4); }
-constexpr int kStPad = kWaveTok + 8 + (kWaveTok + 8) / 16 + 1;
-constexpr int kMaxMergeGroups = SHRED_MAX_GROUPS;
-constexpr int kSigBits = SHRED_SIG_BITS;   // per-tile pair signature
-constexpr int kSigWords = kSigBits / 32;
 constexpr uint32_t kWin = 32;              // candidate tiles per workgroup window (filter pass)
 constexpr int kMaxChain = 8;               // merges one k_merge launch applies in order
 constexpr int kChainShift = 27;            // matched-tile entries: tile | (chain index << 27)
 constexpr uint32_t kMtLds = 256;           // matched tiles a workgroup keeps in LDS (more: global list)
-constexpr int kRegHdr = 8;                 // region header: nrec, nmt, spill, pad, merged (2), written (2)
 [[maybe_unused]] constexpr int kStamps = 18;               // SHRED_STAMPS: entry, init, windows, flush, ticket, collect, flag
 #ifdef SHRED_STAMPS
 #define STAMP(k) \
@@ -279,66 +64,6 @@ constexpr int kRegHdr = 8;                 // region header: nrec, nmt, spill, p
 #define STAMP_ONCE(k)
 #endif
 static_assert(kMaxChain == Device::kChainMax, "chain length shared with the host");
-static_assert(kSigWords % 256 == 0 || kSigWords == 64 || kSigWords == 128, "signature written as 16 B per lane");
-
-// The two signature bits of pair (x, y).
-__device__ __forceinline__ void sig_bits(int32_t x, int32_t y, uint32_t* h1, uint32_t* h2) {
-  uint32_t k = (uint32_t)x * 0x9E3779B1u ^ ((uint32_t)y + 0x7F4A7C15u) * 0x85EBCA77u;
-  k ^= k >> 15;
-  k *= 0x2C1B3C6Du;
-  k ^= k >> 12;
-  k *= 0x297A2D39u;
-  k ^= k >> 15;
-  *h1 = k & (kSigBits - 1);
-  *h2 = (k >> 16) & (kSigBits - 1);
-}
-
-__device__ __forceinline__ void sig_add(uint32_t* s, int32_t x, int32_t y) {
-  uint32_t h1, h2;
-  sig_bits(x, y, &h1, &h2);
-  atomicOr(&s[h1 >> 5], 1u << (h1 & 31));
-  atomicOr(&s[h2 >> 5], 1u << (h2 & 31));
-}
-
-// Writes a wave's LDS signature to the tile's HBM signature (16 B per lane per pass).
-__device__ __forceinline__ void sig_store(uint32_t* dst, const uint32_t* s, int lane) {
-  for (int w = lane * 4; w < kSigWords; w += 256) {
-    uint4 v;
-    v.x = s[w];
-    v.y = s[w + 1];
-    v.z = s[w + 2];
-    v.w = s[w + 3];
-    *reinterpret_cast<uint4*>(dst + w) = v;
-  }
-}
-
-__device__ __forceinline__ void sig_clear(uint32_t* s, int lane) {
-  for (int w = lane; w < kSigWords; w += 64) s[w] = 0;
-}
-
-// Orders this wave's LDS accesses across lanes (LDS executes one wave's ops in order; this
-// keeps the compiler from moving them and drains lgkmcnt).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-// Rebuilds a single-chunk tile's signature from its tokens v (this lane's 16, kPad beyond) and
-// the token after them (nx); longer tiles keep an all-ones signature.
-__device__ __forceinline__ void sig_rebuild(uint32_t* s_sig, uint32_t* dst, const int32_t (&v)[kPer], int32_t nx,
-                                            int lane) {
-  sig_clear(s_sig, lane);
-  wave_lds_sync();
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const int32_t x = v[j], y = j + 1 < kPer ? v[j + 1] : nx;
-    if (!is_hdr(x) && !is_hdr(y)) sig_add(s_sig, x, y);
-  }
-  wave_lds_sync();
-  sig_store(dst, s_sig, lane);
-}
 
 struct MergeParams {
   int32_t* tok;
@@ -385,15 +110,6 @@ struct DeltaLds {
 };
 
 template <class P>
-__device__ __forceinline__ void delta_global(const P& p, uint32_t key, u64 w, u64 ft) {
-  atomicAdd(&p.dsum[key], w);
-  const u64 old = atomicMin(&p.dft[key], ft);
-  if (old == kEmpty64) {  // exactly one toucher sees MAX
-    atomicExch(&p.dlist[atomicAdd(p.dcount, 1u)], key);
-  }
-}
-
-template <class P>
 __device__ __forceinline__ void delta_emit(DeltaLds& h, const P& p, uint32_t key, u64 w, u64 ft) {
   uint32_t s = (key * 2654435761u) >> (32 - __builtin_ctz(kDeltaLdsW));
   for (int probe = 0; probe < 16; ++probe) {
@@ -408,12 +124,6 @@ __device__ __forceinline__ void delta_emit(DeltaLds& h, const P& p, uint32_t key
   h.spill = 1;
   delta_global(p, key, w, ft);
 }
-
-__device__ __forceinline__ uint32_t slot_of(int32_t id, uint32_t cap) {
-  return (uint32_t)id < cap ? (uint32_t)id + 1u : 0u;
-}
-
-__device__ __forceinline__ int wave_incl_sum(int x) { return (int)wave_scan_add((uint32_t)x); }
 
 template <bool kWeighted>
 __global__ __launch_bounds__(kThreads) void k_merge(MergeParams p) {
@@ -954,977 +664,6 @@ __global__ __launch_bounds__(kThreads) void k_merge(MergeParams p) {
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// K2+K3 resident: the merge loop as ONE persistent launch with the word table held in LDS.
-//
-// When the types table fits the chip's LDS (256 CUs x ~100 KB: C2's 17 MB), workgroup w (one
-// per CU) copies its contiguous range of tiles and their word weights into LDS once and keeps
-// them there for the whole merge loop, so a merge never reads the table from HBM.  The host
-// posts each merge in a mailbox in pinned host memory; workgroup 0 (the leader) is the only
-// poller of host memory (pollers of one host line serialise over PCIe: 256 of them cost 200 us
-// per command on MI355X, one costs ~3 us) and hands the merge to its participants — the owners
-// of the merge's candidate tiles from the host tile index, or every workgroup — through one
-// 8-byte go word per workgroup on a 128-B line of its own (sc1 store after the sc1 command
-// stores and a vmcnt drain; each workgroup polls only its own word).  A participant applies the
-// merge to its tiles in LDS exactly as k_merge does to a single-chunk tile, reduces the
-// neighbour deltas in an LDS hash, publishes them to its region, and takes a ticket among the
-// participants; the last one gathers the regions into the host-visible records and raises the
-// host flag, as k_merge's fused completion does.  A STOP command (or a poll time-out) writes the
-// tiles back to HBM and ends the launch, so the HBM stream is current whenever the host uses it.
-constexpr int kResDeltaW = 1024;         // LDS delta slots per workgroup (spills go to HBM)
-constexpr int kResSigBits = 4096;        // per-tile pair signature held in LDS (Bloom, 2 hashes)
-constexpr int kResSigWords = kResSigBits / 32;
-constexpr uint32_t kResSigRebuild = 192;  // pairs added to a tile's signature before it is rebuilt
-constexpr uint32_t kResMaxTiles = 320;   // tiles one workgroup may own (C5 at 100 GB: 271)
-constexpr uint32_t kOpMerge = 1, kOpStop = 2, kOpTimeout = 3;
-
-// host command ring, device command ring, per-workgroup queues: at most 10 commands are ever
-// outstanding (Device::rollback), so no entry is overwritten before it is read
-constexpr uint32_t kResRing = 16;
-// Workgroup roles: 0 dispatches the host's commands, 1 completes every merge (gathers the
-// participants' records to the host), 2 .. grid-1 own the tiles.
-constexpr uint32_t kResGatherWg = 1, kResFirstWorker = 2;
-constexpr int kResGatherBatch = 16;  // records per gatherer thread per round trip
-constexpr int kResThreadsHbm = 512;  // k_resident block size when the tokens stay in HBM
-constexpr uint32_t kAllTiles = 0xFFFFFFFFu;  // hcount[2]: merge X matched (nearly) every tile
-static_assert(kResDeltaW < (1 << 12) && kResMaxTiles * kWaveTok < (1u << 22), "region header fields (k_resident)");
-constexpr uint32_t kOpUnmerge = 4;
-// k_resident: not every workgroup became resident within the leader's bound (another kernel or
-// process holds CUs); every workgroup leaves without touching the table, the host falls back
-constexpr uint32_t kOpAbort = 5;
-
-// One host command (pinned host memory, written by the host; only the leader reads it).
-// Every field is an 8-byte granule {seq, value} written by one aligned 8-byte store, so the
-// leader reads the whole command in ONE round trip (13 lanes, one granule each) and takes it
-// only when every granule carries the command number: no ordering between the host's stores or
-// the device's loads is needed.  The command for number s lives in cmd[s % kResRing].
-constexpr int kCmdOp = 0, kCmdA = 1, kCmdB = 2, kCmdX = 3, kCmdSlotN = 4, kCmdMask = 5;  // mask: 8 granules
-constexpr int kCmdGranules = 13;
-struct ResCmd {
-  uint64_t g[16];  // g[k] = seq | value << 32
-};
-struct ResMbox {
-  ResCmd cmd[kResRing];
-};
-
-// The per-merge device tables and host-visible buffers of one slot (as k_merge's MergeSlot).
-struct ResSlot {
-  u64* dsum;
-  u64* dft;
-  uint32_t* dlist;
-  uint32_t* dcount;   // [0] touched global slots
-  uint32_t* done;     // [8]: participants that published their region (the gatherer resets it)
-  DeltaRecord* out;   // host-visible records
-  uint32_t* hcount;   // host-visible: [0] records, [1] flag = seq, [2] matched tiles
-  u64* hstats;        // host-visible: [0] occurrences, [1] tokens rewritten, [2] device ticks of the merge
-  uint32_t* hmlist;   // host-visible matched tiles
-  uint32_t* rhdr;     // per-participant regions (as k_merge's)
-  u64* rrec;
-  uint32_t* rtile;
-};
-
-struct ResParams {
-  int32_t* tok;
-  const uint64_t* tile_off;
-  uint32_t* tile_len;
-  const uint64_t* weight;
-  const uint32_t* wg_tiles;  // grid + 1: workgroup w owns tiles [wg_tiles[w], wg_tiles[w+1])
-  const uint32_t* wg_rank;   // grid + 1: ... and the weights of ranks [wg_rank[w], wg_rank[w+1])
-  const uint32_t* tile_lofs; // per tile: word offset in its owner's LDS token area (multiple of 4)
-  uint32_t tok_words;        // LDS token area (words, multiple of 4, incl. one chunk of read slack)
-  uint32_t w_words;          // LDS weight area (u64 entries, even)
-  const ResMbox* mbox;
-  uint32_t* cmd;             // device command ring: kResRing x 8 words [a, b, X, nparts, slot, op, stamp lo, hi]
-  u64* q;                    // per-workgroup queues: kResRing entries each (zeroed before the launch)
-  uint32_t* status;          // host-visible: [0] kOpTimeout / kOpAbort when the launch ended itself,
-                             //   [2] 1 once every workgroup was seen resident
-  uint32_t* arrive;          // workgroups that started (zeroed before the launch)
-  uint32_t arrive_polls;     // the leader's bound on waiting for them
-  uint32_t seq0;             // first command number of this launch
-  uint32_t leader_polls;     // idle leader iterations before the launch ends itself
-  uint32_t keys_per_merge, slot_cap;
-  uint32_t sig_words;        // LDS signature words per tile (kResSigWords, or a half / quarter of it)
-  uint32_t w_global;         // 1: the weights stay in HBM (w_words = 0), read per matched occurrence
-  uint32_t region_keys;      // a participant with more LDS delta keys adds them to the global tables
-  uint32_t mt_dense;         // more matched tiles than this: the host index marks X in every tile
-  uint32_t mt_words;         // the matched tiles go to the host as a bitmap of this many u32 words
-  ResSlot sl[Device::kResSlots];  // merge X uses sl[X % kResSlots]
-  uint32_t* dbg;      // diagnostic (SHREDWORD_RESIDENT_DEBUG): per workgroup [phase, last seq, pi, T]
-  u64* stamps;        // diagnostic: per participant [go seen, work done, loop cycles, -] (s_memrealtime)
-};
-
-struct ResDelta {
-  uint32_t key[kResDeltaW];
-  u64 sum[kResDeltaW];
-  u64 ft[kResDeltaW];
-  uint32_t spill;
-};
-
-// Queue entry: two 8-byte halves, each tagged with this workgroup's entry number (count, 1-based,
-// 16 bits); a reader takes the entry when both halves carry the count it expects.
-//   half 0: count 16 | pi 8 | op 3 | slot 2 | T 9 | a 20     half 1: count 16 | b 20 | X 20
-__device__ __forceinline__ void q_pack(uint32_t cnt, uint32_t pi, uint32_t op, uint32_t slot, uint32_t T, int32_t a,
-                                       int32_t b, int32_t X, u64* h0, u64* h1) {
-  const u64 c = cnt & 0xFFFFu;
-  *h0 = c | ((u64)(pi & 0xFFu) << 16) | ((u64)(op & 7u) << 24) | ((u64)(slot & 3u) << 27) | ((u64)(T & 0x1FFu) << 29) |
-        ((u64)((uint32_t)a & 0xFFFFFu) << 38);
-  *h1 = c | ((u64)((uint32_t)b & 0xFFFFFu) << 16) | ((u64)((uint32_t)X & 0xFFFFFu) << 36);
-}
-
-// sm = the tile signature's bit count - 1 (kResSigBits, or a half / quarter of it when the table
-// needs a smaller LDS plan: Device::plan_resident)
-__device__ __forceinline__ void res_sig_bits(int32_t x, int32_t y, uint32_t* h1, uint32_t* h2, uint32_t sm) {
-  uint32_t k = (uint32_t)x * 0x9E3779B1u ^ ((uint32_t)y + 0x7F4A7C15u) * 0x85EBCA77u;
-  k ^= k >> 15;
-  k *= 0x2C1B3C6Du;
-  k ^= k >> 12;
-  k *= 0x297A2D39u;
-  k ^= k >> 15;
-  *h1 = k & sm;
-  *h2 = (k >> 16) & sm;
-}
-__device__ __forceinline__ bool res_sig_test(const uint32_t* sg, int32_t x, int32_t y, uint32_t sm) {
-  uint32_t h1, h2;
-  res_sig_bits(x, y, &h1, &h2, sm);
-  return ((sg[h1 >> 5] >> (h1 & 31)) & 1u) && ((sg[h2 >> 5] >> (h2 & 31)) & 1u);
-}
-// Rebuilds a tile's LDS signature from its tokens t[0, len) (one wave).
-__device__ __forceinline__ void res_sig_build(uint32_t* sg, const int32_t* t, uint32_t len, int lane, uint32_t sm) {
-  for (int w = lane; w < (int)((sm + 1) >> 5); w += 64) sg[w] = 0;
-  wave_lds_sync();
-  for (uint32_t i = (uint32_t)lane; i + 1 < len; i += 64) {
-    const int32_t x = t[i], y = t[i + 1];
-    if (!is_hdr(x) && !is_hdr(y)) {
-      uint32_t h1, h2;
-      res_sig_bits(x, y, &h1, &h2, sm);
-      atomicOr(&sg[h1 >> 5], 1u << (h1 & 31));
-      atomicOr(&sg[h2 >> 5], 1u << (h2 & 31));
-    }
-  }
-  wave_lds_sync();
-}
-
-
-// One wave applies (a, b) -> X to a single-chunk tile held in LDS at tb (live length *len):
-// k_merge's per-chunk logic with no carries (the tile is its own first and last chunk).
-// Returns the occurrences merged; the tile is compacted in place and *len updated.
-// This lane's 16 tokens of a tile (four 16-B loads).
-struct TileRegs {
-  int4 q[kPer / 4];
-};
-__device__ __forceinline__ void res_load_tile(const int32_t* tb, int lane, TileRegs* r) {
-  const int p0 = lane * kPer;
-#pragma unroll
-  for (int q = 0; q < kPer / 4; ++q) r->q[q] = *reinterpret_cast<const int4*>(tb + p0 + 4 * q);
-}
-
-// The per-launch plan the merge body needs beside the tile: signature mask, and where the word
-// weights live (LDS s_w from rank r0, or HBM when the table's weights do not fit LDS).
-struct ResPlan {
-  uint32_t sm;
-  const u64* gw;  // non-null: weights from HBM (indexed by rank)
-};
-
-template <bool kWeighted>
-__device__ __forceinline__ uint32_t res_merge_body(int32_t* tb, const TileRegs& tr, uint32_t* lenp, uint32_t* sg,
-                                                   uint32_t* sgadd, int32_t* st, const u64* s_w, uint32_t r0, int32_t a,
-                                                   int32_t b, int32_t X, ResDelta& h, const ResSlot& p,
-                                                   uint32_t slot_cap, int lane, u64* n_written, const ResPlan& rp);
-
-template <bool kWeighted>
-__device__ __forceinline__ uint32_t res_merge_tile(int32_t* tb, uint32_t* lenp, uint32_t* sg, uint32_t* sgadd, int32_t* st,
-                                                   const u64* s_w,
-                                                   uint32_t r0, int32_t a, int32_t b, int32_t X, ResDelta& h,
-                                                   const ResSlot& p, uint32_t slot_cap, int lane, u64* n_written,
-                                                   const ResPlan& rp) {
-  if (!res_sig_test(sg, a, b, rp.sm)) return 0;  // the pair cannot be in this tile
-  TileRegs tr;
-  res_load_tile(tb, lane, &tr);
-  return res_merge_body<kWeighted>(tb, tr, lenp, sg, sgadd, st, s_w, r0, a, b, X, h, p, slot_cap, lane, n_written, rp);
-}
-
-// The merge of one tile whose 16 tokens per lane are already in registers (tr).
-template <bool kWeighted>
-__device__ __forceinline__ uint32_t res_merge_body(int32_t* tb, const TileRegs& tr, uint32_t* lenp, uint32_t* sg,
-                                                   uint32_t* sgadd, int32_t* st, const u64* s_w, uint32_t r0, int32_t a,
-                                                   int32_t b, int32_t X, ResDelta& h, const ResSlot& p,
-                                                   uint32_t slot_cap, int lane, u64* n_written, const ResPlan& rp) {
-  const uint32_t len = *lenp;
-  const int p0 = lane * kPer;
-  int32_t v[kPer];
-#pragma unroll
-  for (int q = 0; q < kPer / 4; ++q) {
-    v[4 * q] = tr.q[q].x;
-    v[4 * q + 1] = tr.q[q].y;
-    v[4 * q + 2] = tr.q[q].z;
-    v[4 * q + 3] = tr.q[q].w;
-  }
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    if ((uint32_t)(p0 + j) >= len) v[j] = kPad;
-  int32_t nx = wave_next(v[0]);
-  if (lane == 63) nx = kPad;
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) any |= (v[j] == a) & ((j + 1 < kPer ? v[j + 1] : nx) == b);
-  if (!__any(any)) return 0;
-  const bool same = (a == b);
-  const uint32_t cl = len;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) st[SK(2 + p0 + j)] = v[j];
-  if (lane == 0) {
-    st[SK(0)] = kPad;
-    st[SK(1)] = kPad;
-  }
-  if (lane == 63) {
-    st[SK(2 + kWaveTok)] = kPad;
-    st[SK(3 + kWaveTok)] = kPad;
-  }
-  wave_lds_sync();
-  uint32_t mask = 0;
-  if (same) {
-    u64 nl = 0;  // last index whose token != a, + 1 (0 = none)
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (v[j] != a) nl = (u64)(p0 + j) + 1;
-    const u64 inc = wave_scan_max64(nl);
-    long long last = (long long)wave_prev64(inc) - 1;
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const long long gi = (long long)(p0 + j);
-      if (v[j] != a) last = gi;
-      else if ((j + 1 < kPer ? v[j + 1] : nx) == a && ((gi - last - 1) & 1) == 0) mask |= 1u << j;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (v[j] == a && (j + 1 < kPer ? v[j + 1] : nx) == b) mask |= 1u << j;
-  }
-  uint32_t prevm = wave_prev(mask);
-  if (lane == 0) prevm = 0;
-  const uint32_t m_ext = (mask << 2) | ((prevm >> 14) & 3u);  // bit k <-> position p0 - 2 + k
-  const uint32_t removed = (m_ext >> 1) & 0xFFFFu;           // bit j <-> match at p0 + j - 1
-  const int valid = max(0, min(kPer, (int)cl - p0));
-  const uint32_t vmask = valid >= kPer ? 0xFFFFu : ((1u << valid) - 1u);
-  const int kc = __popc(~removed & vmask);
-  const int nm = __popc(mask);
-  uint32_t hmask = 0;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    if (is_hdr(v[j])) hmask |= 1u << j;
-  hmask &= vmask;
-  u64 hl = 0;
-  if (hmask) {
-    const int j = 31 - __clz(hmask);
-    hl = ((u64)(p0 + j + 1) << 32) | hdr_rank(st[SK(2 + p0 + j)]);
-  }
-  const u64 hinc = wave_scan_max64(hl);
-  const u64 hdr_ex = wave_prev64(hinc);
-  const int cinc = wave_incl_sum(kc | (nm << 16));
-  const int ctot = (int)lane_read((uint32_t)cinc, 63);
-  const int kc_ex = (cinc - (kc | (nm << 16))) & 0xFFFF;
-  const int kept = ctot & 0xFFFF;
-  const int matches = ctot >> 16;
-  if (mask) {
-    const u64 hdr_in = lane == 0 ? 0ull : hdr_ex;
-    for (uint32_t mrem = mask; mrem; mrem &= mrem - 1) {
-      const int j = __ffs(mrem) - 1;
-      const uint32_t hb = hmask & ((2u << j) - 1u);
-      u64 hdr = hdr_in;
-      if (hb) {
-        const int jh = 31 - __clz(hb);
-        hdr = ((u64)(p0 + jh + 1) << 32) | hdr_rank(st[SK(2 + p0 + jh)]);
-      }
-      const uint32_t hidx = (uint32_t)(hdr >> 32) - 1u;
-      const uint32_t rank = (uint32_t)hdr;
-      const uint32_t gi = p0 + j;
-      const u64 w = kWeighted ? (rp.gw ? rp.gw[rank] : s_w[rank - r0]) : 1ull;
-      const u64 ftb = ((u64)rank << 32) | ((u64)(gi - hidx - 1u) << 2);
-      const bool vl = gi - 1u > hidx;  // a left neighbour inside the word (X if it was just merged)
-      const int32_t left = ((m_ext >> j) & 1u) ? X : st[SK(1 + p0 + j)];
-      const int32_t right = st[SK(4 + p0 + j)];  // the original token after b
-      const bool vr = !is_hdr(right);
-      const uint32_t sl = slot_of(left, slot_cap) << 2, sr = slot_of(right, slot_cap) << 2;
-      const uint32_t key[4] = {sl | kOldLeft, sl | kNewLeft, sr | kOldRight, sr | kNewRight};
-      const bool val[4] = {vl, vl, vr, vr};
-      // the four slots are probed together (their CAS round trips overlap), then summed
-      uint32_t slot[4];
-      bool pend[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        slot[k] = (key[k] * 2654435761u) >> (32 - __builtin_ctz(kResDeltaW));
-        pend[k] = val[k];
-      }
-      for (int probe = 0; probe < 16 && (pend[0] | pend[1] | pend[2] | pend[3]); ++probe) {
-        uint32_t prev[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) prev[k] = pend[k] ? atomicCAS(&h.key[slot[k]], kEmpty32, key[k]) : key[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (pend[k]) {
-            if (prev[k] == kEmpty32 || prev[k] == key[k]) pend[k] = false;
-            else slot[k] = (slot[k] + 1) & (kResDeltaW - 1);
-          }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (!val[k]) continue;
-        if (pend[k]) {  // the LDS hash is full around these slots: the global tables take it
-          h.spill = 1;
-          delta_global(p, key[k], w, ftb | (u64)(k));
-        } else {
-          atomicAdd(&h.sum[slot[k]], w);
-          atomicMin(&h.ft[slot[k]], ftb | (u64)(k));
-        }
-      }
-      // the tile's signature gains the new pairs (a superset stays valid; rebuilt when loose)
-      uint32_t h1, h2, h3, h4;
-      res_sig_bits(left, X, &h1, &h2, rp.sm);
-      res_sig_bits(X, right, &h3, &h4, rp.sm);
-      atomicOr(&sg[h1 >> 5], vl ? 1u << (h1 & 31) : 0u);
-      atomicOr(&sg[h2 >> 5], vl ? 1u << (h2 & 31) : 0u);
-      atomicOr(&sg[h3 >> 5], vr ? 1u << (h3 & 31) : 0u);
-      atomicOr(&sg[h4 >> 5], vr ? 1u << (h4 & 31) : 0u);
-    }
-  }
-  wave_lds_sync();  // every neighbour read is done: compact in place
-  // branch-free: a dropped position writes this lane's trash word past the staging area
-  int o = kc_ex;
-  const int trash = kStPad + lane;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const bool keep = j < valid && !((removed >> j) & 1u);
-    st[keep ? SK(2 + o) : trash] = ((mask >> j) & 1u) ? X : v[j];
-    o += keep ? 1 : 0;
-  }
-  // a tile whose signature gathered many added pairs since its last build is re-signed below
-  const uint32_t added = *sgadd + 2u * (uint32_t)matches;
-  const bool rebuild = added > (kResSigRebuild * (rp.sm + 1)) / (uint32_t)kResSigBits;  // scaled with the signature
-  if (rebuild)
-    for (int w = lane; w < (int)((rp.sm + 1) >> 5); w += 64) sg[w] = 0;
-  wave_lds_sync();
-  int32_t c[kPer + 1];  // this lane's compacted tokens (kPad past the end) and the next one
-#pragma unroll
-  for (int j = 0; j <= kPer; ++j) {
-    const int32_t t = st[SK(2 + p0 + j)];
-    c[j] = p0 + j < kept ? t : kPad;
-  }
-#pragma unroll
-  for (int q = 0; q < kPer / 4; ++q) {
-    if (p0 + 4 * q < kept) {
-      int4 x;
-      x.x = c[4 * q];
-      x.y = c[4 * q + 1];
-      x.z = c[4 * q + 2];
-      x.w = c[4 * q + 3];
-      *reinterpret_cast<int4*>(tb + p0 + 4 * q) = x;
-    }
-  }
-  if (lane == 0) *lenp = (uint32_t)kept;
-  *n_written += (u64)kept;
-  if (rebuild) {
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {  // signature of the compacted tile (OR of 0 where no pair)
-      uint32_t h1, h2;
-      res_sig_bits(c[j], c[j + 1], &h1, &h2, rp.sm);
-      const bool pr = !is_hdr(c[j]) && !is_hdr(c[j + 1]);
-      atomicOr(&sg[h1 >> 5], pr ? 1u << (h1 & 31) : 0u);
-      atomicOr(&sg[h2 >> 5], pr ? 1u << (h2 & 31) : 0u);
-    }
-  }
-  if (lane == 0) *sgadd = rebuild ? 0u : added;
-  wave_lds_sync();
-  return (uint32_t)matches;
-}
-
-// One wave expands every X in a single-chunk tile held in LDS back into (a, b) — the undo of a
-// speculative merge that the host did not confirm; the tile's length grows back, within its
-// original LDS capacity.  The signature is rebuilt exactly.
-__device__ __forceinline__ void res_unmerge_tile(int32_t* tb, uint32_t* lenp, uint32_t* sg, uint32_t* sgadd, int32_t* st,
-                                                 int32_t a, int32_t b, int32_t X, int lane, uint32_t sm) {
-  const uint32_t len = *lenp;
-  const int p0 = lane * kPer;
-  int32_t v[kPer];
-#pragma unroll
-  for (int q = 0; q < kPer / 4; ++q) {
-    const int4 x = *reinterpret_cast<const int4*>(tb + p0 + 4 * q);
-    v[4 * q] = x.x;
-    v[4 * q + 1] = x.y;
-    v[4 * q + 2] = x.z;
-    v[4 * q + 3] = x.w;
-  }
-  int nx = 0;  // this lane's X count
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    if ((uint32_t)(p0 + j) >= len) v[j] = kPad;
-    nx += v[j] == X ? 1 : 0;
-  }
-  if (!__any(nx != 0)) return;
-  const int inc = wave_incl_sum(nx);
-  const int total = (int)lane_read((uint32_t)inc, 63);
-  const int nlen = (int)len + total;  // <= the tile's LDS capacity: the merge removed these tokens
-  int o = p0 + inc - nx;              // this lane's first output position
-  const int trash = kStPad + lane;
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const bool live = (uint32_t)(p0 + j) < len;
-    const bool isx = live && v[j] == X;
-    st[live ? SK(o) : trash] = isx ? a : v[j];
-    st[isx ? SK(o + 1) : trash] = b;
-    o += live ? (isx ? 2 : 1) : 0;
-  }
-  wave_lds_sync();
-  for (int i = lane; i < (int)((sm + 1) >> 5); i += 64) sg[i] = 0;
-  int32_t c[kPer + 1];
-#pragma unroll
-  for (int j = 0; j <= kPer; ++j) {
-    const int32_t t = st[SK(p0 + j)];
-    c[j] = p0 + j < nlen ? t : kPad;
-  }
-#pragma unroll
-  for (int q = 0; q < kPer / 4; ++q) {
-    if (p0 + 4 * q < nlen) {
-      int4 x;
-      x.x = c[4 * q];
-      x.y = c[4 * q + 1];
-      x.z = c[4 * q + 2];
-      x.w = c[4 * q + 3];
-      *reinterpret_cast<int4*>(tb + p0 + 4 * q) = x;
-    }
-  }
-  wave_lds_sync();
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    uint32_t h1, h2;
-    res_sig_bits(c[j], c[j + 1], &h1, &h2, sm);
-    const bool pr = !is_hdr(c[j]) && !is_hdr(c[j + 1]);
-    atomicOr(&sg[h1 >> 5], pr ? 1u << (h1 & 31) : 0u);
-    atomicOr(&sg[h2 >> 5], pr ? 1u << (h2 & 31) : 0u);
-  }
-  if (lane == 0) {
-    *lenp = (uint32_t)nlen;
-    *sgadd = 0;
-  }
-  wave_lds_sync();
-}
-
-// kLdsTok: the tokens live in LDS (the table fits the chip's LDS); otherwise they stay in HBM
-// (read and rewritten in place by their owner workgroup only) and LDS holds the weights and the
-// tile signatures, which is what decides which tiles a merge reads at all.
-template <bool kWeighted, bool kLdsTok>
-__global__ __launch_bounds__(kLdsTok ? 256 : kResThreadsHbm) void k_resident(ResParams p) {
-  constexpr int kRT = kLdsTok ? 256 : kResThreadsHbm;  // threads: more waves hide the HBM tile loads
-  constexpr int kRW = kRT / 64;
-  constexpr int kGB = kLdsTok ? kResGatherBatch : kResGatherBatch / 4;  // gatherer loads in flight per thread
-  extern __shared__ __align__(16) int32_t s_dyn[];
-  int32_t* s_res = s_dyn;                                     // the tiles' tokens
-  u64* s_w = reinterpret_cast<u64*>(s_dyn + p.tok_words);     // the words' weights
-  uint32_t* s_sig = reinterpret_cast<uint32_t*>(s_dyn + p.tok_words + 2 * p.w_words);  // per-tile signatures
-  const uint32_t sw = p.sig_words;
-  const ResPlan rplan{sw * 32u - 1u, p.w_global ? reinterpret_cast<const u64*>(p.weight) : nullptr};
-  __shared__ int32_t s_tok[kRW][kStPad + 64];  // + a trash word per lane (branch-free compaction)
-  __shared__ ResDelta h;
-  __shared__ uint32_t s_len[kResMaxTiles], s_lofs[kResMaxTiles], s_sigadd[kResMaxTiles];
-  __shared__ u64 s_toff[kResMaxTiles];
-  __shared__ uint32_t s_mt[kResMaxTiles];
-  __shared__ uint8_t s_lm[kResMaxTiles];   // per tile: bit X % 8 set when merge X matched there
-  __shared__ uint32_t s_qc[kMaxMergeGroups];  // leader: entries written to each workgroup's queue
-  __shared__ uint32_t s_nmt, s_nrec, s_nkeys;
-  __shared__ uint32_t s_cmd[8];
-  __shared__ u64 s_cnt[2];
-  __shared__ u64 s_tlead;
-  __shared__ u64 s_ts[4];      // diagnostic (stamps): the gatherer's phase ends
-  __shared__ uint32_t s_nout;  // the last participant: records written to the host
-  __shared__ uint32_t s_pre[kMaxMergeGroups + 1], s_pmt[kMaxMergeGroups + 1];
-  __shared__ uint32_t s_wtot[2][kRW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const uint32_t G = gridDim.x, me = blockIdx.x;
-  const uint32_t t0 = p.wg_tiles[me], nt = p.wg_tiles[me + 1] - t0;
-  const uint32_t r0 = p.wg_rank[me], nr = p.wg_rank[me + 1] - r0;
-  int32_t* st = s_tok[wid];
-  // ---- co-residency: every workgroup counts itself in; the leader dispatches nothing until all
-  // have (below), so a launch that is only partly resident aborts instead of hanging
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(p.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-  // ---- residency: tiles, weights and signatures into LDS
-  for (uint32_t i = threadIdx.x; i < nt; i += kRT) {
-    s_len[i] = p.tile_len[t0 + i];
-    s_lofs[i] = p.tile_lofs[t0 + i];
-    s_toff[i] = p.tile_off[t0 + i];
-    s_sigadd[i] = 0;
-    s_lm[i] = 0;
-  }
-  for (uint32_t i = threadIdx.x; i < G; i += kRT) s_qc[i] = 0;
-  for (int i = threadIdx.x; i < kResDeltaW; i += kRT) {
-    h.key[i] = kEmpty32;
-    h.sum[i] = 0;
-    h.ft[i] = kEmpty64;
-  }
-  if (kWeighted)
-    for (uint32_t i = threadIdx.x; nr && !p.w_global && i < nr; i += kRT) s_w[i] = p.weight[r0 + i];
-  if (threadIdx.x == 0) h.spill = 0;
-  __syncthreads();
-  auto tile_ptr = [&](uint32_t i) -> int32_t* {
-    if constexpr (kLdsTok) return s_res + s_lofs[i];
-    else return p.tok + s_toff[i];
-  };
-  for (uint32_t i = wid; i < nt; i += kRW) {
-    if constexpr (kLdsTok) {
-      const int32_t* src = p.tok + s_toff[i];
-      int32_t* dst = s_res + s_lofs[i];
-      const uint32_t n4 = (s_len[i] + 3u) >> 2;
-      for (uint32_t q = (uint32_t)lane; q < n4; q += 64)
-        *reinterpret_cast<int4*>(dst + 4 * q) = *reinterpret_cast<const int4*>(src + 4 * q);
-      wave_lds_sync();
-    }
-    res_sig_build(s_sig + (size_t)i * sw, tile_ptr(i), s_len[i], lane, rplan.sm);
-  }
-  __syncthreads();
-
-  uint32_t expect = p.seq0;  // leader: the next host command
-  uint32_t idle = 0;         // leader: polls without a command
-  uint32_t consumed = 0;     // thread 0: entries taken from this workgroup's queue
-  uint32_t exit_op = kOpStop;
-  const u64* myq = p.q + (size_t)me * kResRing * 2;
-  if (me == 0 && wid == 0) {  // the leader waits (bounded) until every workgroup is resident
-    bool all = false;
-    for (uint32_t k = 0; k < p.arrive_polls && !all; ++k) {
-      all = __hip_atomic_load(p.arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= G;
-      if (!all) __builtin_amdgcn_s_sleep(8);
-    }
-    if (lane == 0) {
-      if (all) {
-        __hip_atomic_store(p.status + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else {  // an abort as the first entry of every queue (the missing workgroups read it when
-                // they start, after the host has moved on to another stream)
-        for (uint32_t wg = 0; wg < G; ++wg) {
-          u64 h0, h1;
-          q_pack(1, 0, kOpAbort, 0, G, 0, 0, 0, &h0, &h1);
-          u64* e = p.q + (size_t)wg * kResRing * 2;
-          __hip_atomic_store(e, h0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(e + 1, h1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __threadfence_system();
-        __hip_atomic_store(p.status, kOpAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      s_cmd[7] = all ? 1u : 0u;
-    }
-  }
-  __syncthreads();
-  if (me == 0 && s_cmd[7] == 0) return;  // aborted: the table was not touched
-  for (;;) {
-    // ---- the leader hands out the next host command, if one is posted (one poll per pass)
-    if (me == 0 && wid == 0) {
-      const uint64_t* hc = p.mbox->cmd[expect % kResRing].g;
-      // lane k < kCmdGranules reads granule k: the whole command in one round trip
-      const u64 gv = lane < kCmdGranules ? __hip_atomic_load(hc + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0ull;
-      const bool tagged = lane >= kCmdGranules || (uint32_t)gv == expect;
-      const bool ready = __all(tagged);
-      const uint32_t val = (uint32_t)(gv >> 32);
-      uint32_t op = 0;
-      if (ready) {
-        op = (uint32_t)__shfl((int)val, kCmdOp, 64);
-        idle = 0;
-      } else if (++idle >= p.leader_polls) {
-        op = kOpTimeout;  // nobody posts any more: every workgroup writes back and leaves
-      }
-      if (op) {
-        const int32_t a = __shfl((int)val, kCmdA, 64), b = __shfl((int)val, kCmdB, 64), X = __shfl((int)val, kCmdX, 64);
-        const uint32_t sn = (uint32_t)__shfl((int)val, kCmdSlotN, 64);
-        const bool merge_like = ready && (op == kOpMerge || op == kOpUnmerge);
-        // lane l covers workgroups 4l .. 4l+3: its mask nibble, participant indices by a wave scan
-        const uint32_t mw = (uint32_t)__shfl((int)val, kCmdMask + (lane >> 3), 64);
-        uint32_t nib = merge_like ? (mw >> ((lane & 7) * 4)) & 0xFu : 0xFu;
-        if (4u * (uint32_t)lane >= G) nib = 0;
-        for (int k = 0; k < 4; ++k)
-          if (4u * lane + k >= G) nib &= ~(1u << k);
-        const uint32_t cnt = __popc(nib);
-        const uint32_t incl = wave_scan_add(cnt);
-        const uint32_t T = merge_like ? lane_read(incl, 63) : G;
-        uint32_t pi = incl - cnt;
-        if (lane == 0 && merge_like) {
-          uint32_t* dc = p.cmd + ((uint32_t)X % kResRing) * 8;
-          __hip_atomic_store(reinterpret_cast<u64*>(dc + 6), (u64)__builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (!((nib >> k) & 1u)) continue;
-          const uint32_t wg = 4u * lane + k;  // distinct workgroups per lane: the counters need no atomics
-          const uint32_t c = ++s_qc[wg];
-          u64 h0, h1;
-          q_pack(c, pi++, op, sn & 3u, T, a, b, X, &h0, &h1);
-          u64* e = p.q + ((size_t)wg * kResRing + ((c - 1) % kResRing)) * 2;
-          __hip_atomic_store(e, h0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(e + 1, h1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        ++expect;
-      }
-      if (lane == 0) s_cmd[7] = op;
-    }
-    // ---- this workgroup's next queue entry (the leader's workgroup never blocks here)
-    if (threadIdx.x == 0) {
-      const uint32_t want = (consumed + 1) & 0xFFFFu;
-      const u64* e = myq + (consumed % kResRing) * 2;
-      u64 h0 = 0, h1 = 0;
-      bool got = false;
-      for (;;) {
-        h0 = __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h1 = __hip_atomic_load(e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        got = (uint32_t)(h0 & 0xFFFFu) == want && (uint32_t)(h1 & 0xFFFFu) == want;
-        if (got || me == 0) break;
-        __builtin_amdgcn_s_sleep(2);
-      }
-      if (me == 0 && !got && !s_cmd[7]) __builtin_amdgcn_s_sleep(2);
-      s_cmd[0] = got ? (uint32_t)(h0 >> 24) & 7u : 0u;
-      if (got) {
-        ++consumed;
-        s_cmd[1] = (uint32_t)(h0 >> 16) & 0xFFu;
-        s_cmd[2] = (uint32_t)(h0 >> 27) & 3u;                     // slot
-        s_cmd[6] = (uint32_t)(h0 >> 29) & 0x1FFu;                 // T
-        s_cmd[3] = (uint32_t)(h0 >> 38) & 0xFFFFFu;               // a
-        s_cmd[4] = (uint32_t)(h1 >> 16) & 0xFFFFFu;               // b
-        s_cmd[5] = (uint32_t)(h1 >> 36) & 0xFFFFFu;               // X
-      }
-      s_nmt = 0;
-      s_nrec = 0;
-      s_nkeys = 0;
-      s_cnt[0] = 0;
-      s_cnt[1] = 0;
-    }
-    __syncthreads();
-    const uint32_t op = s_cmd[0];
-    if (op == 0) continue;  // the leader's workgroup: nothing queued for it yet
-    if (op == kOpAbort) return;  // the launch aborted before any merge: nothing to write back
-    if (op != kOpMerge && op != kOpUnmerge) {
-      exit_op = op;
-      break;
-    }
-    const uint32_t pi = s_cmd[1], slot = s_cmd[2];
-    const int32_t a = (int32_t)s_cmd[3], b = (int32_t)s_cmd[4], X = (int32_t)s_cmd[5];
-    const uint32_t T = s_cmd[6];
-    if (p.dbg && threadIdx.x == 0) {
-      p.dbg[me * 4] = 2;
-      p.dbg[me * 4 + 1] = (uint32_t)X;
-      p.dbg[me * 4 + 2] = pi;
-      p.dbg[me * 4 + 3] = T;
-    }
-    const uint32_t lm_bit = 1u << ((uint32_t)X & 7u);
-    if (op == kOpUnmerge) {  // undo merge X, a wrong guess (the host undoes them newest first)
-      for (uint32_t i = wid; i < nt; i += kRW)
-        if (s_lm[i] & lm_bit) res_unmerge_tile(tile_ptr(i), &s_len[i], s_sig + (size_t)i * sw, &s_sigadd[i], st,
-                                      a, b, X, lane, rplan.sm);
-      __syncthreads();
-      continue;
-    }
-    const ResSlot& sl = p.sl[slot];
-
-    // ---- the merge over this workgroup's tiles (wave per tile)
-    u64 n_merged = 0, n_written = 0;
-    auto note = [&](uint32_t i, uint32_t m) {
-      if (lane == 0) s_lm[i] = m ? (s_lm[i] | lm_bit) : (s_lm[i] & ~lm_bit);
-      if (m) {
-        n_merged += m;
-        if (lane == 0) s_mt[atomicAdd(&s_nmt, 1u)] = t0 + i;
-      }
-    };
-    if constexpr (kLdsTok) {
-      for (uint32_t i = wid; i < nt; i += kRW) {
-        const uint32_t m = res_merge_tile<kWeighted>(tile_ptr(i), &s_len[i], s_sig + (size_t)i * sw,
-                                                     &s_sigadd[i], st, s_w, r0, a, b, X, h, sl, p.slot_cap, lane,
-                                                     &n_written, rplan);
-        note(i, m);
-      }
-    } else {
-      // tokens in HBM: a software pipeline per wave, the next candidate tile's tokens load while
-      // this one merges (tiles the signature rules out are only noted)
-      auto skip_to = [&](uint32_t i) {
-        for (; i < nt; i += kRW) {
-          if (res_sig_test(s_sig + (size_t)i * sw, a, b, rplan.sm)) break;
-          note(i, 0);
-        }
-        return i;
-      };
-      uint32_t i = skip_to(wid);
-      TileRegs cur;
-      if (i < nt) res_load_tile(tile_ptr(i), lane, &cur);
-      while (i < nt) {
-        const uint32_t j = skip_to(i + kRW);
-        TileRegs nxt;
-        if (j < nt) res_load_tile(tile_ptr(j), lane, &nxt);
-        const uint32_t m = res_merge_body<kWeighted>(tile_ptr(i), cur, &s_len[i], s_sig + (size_t)i * sw,
-                                                     &s_sigadd[i], st, s_w, r0, a, b, X, h, sl, p.slot_cap, lane,
-                                                     &n_written, rplan);
-        note(i, m);
-        cur = nxt;
-        i = j;
-      }
-    }
-    if (lane == 0) {
-      if (n_merged) atomicAdd(&s_cnt[0], n_merged);
-      if (n_written) atomicAdd(&s_cnt[1], n_written);
-    }
-    __syncthreads();
-    // ---- publish this participant's deltas, clearing the LDS hash.  Few keys: a region the
-    // gatherer reads and combines.  Many keys (the early merges touch most neighbours in every
-    // workgroup): straight into the slot's global tables (device-scope Σ and min, the first
-    // toucher lists the key), so the gatherer only reads the combined keys instead of combining
-    // every participant's records in one workgroup.
-    {
-      uint32_t mine = 0;
-      for (int i = threadIdx.x; i < kResDeltaW; i += kRT) mine += h.key[i] != kEmpty32 ? 1u : 0u;
-      mine = wave_scan_add(mine);
-      if (lane == 63 && mine) atomicAdd(&s_nkeys, mine);
-      __syncthreads();
-      const bool to_global = s_nkeys > p.region_keys;
-      u64* rr = sl.rrec + (size_t)pi * kDeltaLdsW * 3;
-      for (int i = threadIdx.x; i < kResDeltaW; i += kRT) {
-        const uint32_t key = h.key[i];
-        if (key == kEmpty32) continue;
-        if (to_global) {
-          delta_global(sl, key, h.sum[i], h.ft[i]);
-        } else {
-          const uint32_t k = atomicAdd(&s_nrec, 1u);
-          __hip_atomic_store(rr + 3 * k, (u64)key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(rr + 3 * k + 1, h.sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(rr + 3 * k + 2, h.ft[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        h.key[i] = kEmpty32;
-        h.sum[i] = 0;
-        h.ft[i] = kEmpty64;
-      }
-      if (to_global && threadIdx.x == 0) h.spill = 1;
-      const uint32_t nmt = s_nmt;
-      for (uint32_t i = threadIdx.x; i < nmt; i += kRT)
-        __hip_atomic_store(sl.rtile + (size_t)pi * kResMaxTiles + i, s_mt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      u64* hd = reinterpret_cast<u64*>(sl.rhdr + (size_t)pi * kRegHdr);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's region stores (and spills) are done
-      __syncthreads();
-      // the header: two 8-byte words, each tagged with X, stored last; the gatherer polls them
-      // (so no ticket and no second drain: the workgroup goes straight on to its next command)
-      //   word 0: X 20 | records 12 | matched tiles 16 | spill 1   word 1: X 20 | merged 22 | written 22
-      if (threadIdx.x == 0) {
-        const u64 x20 = (u64)(uint32_t)X & 0xFFFFFu;
-        const u64 w0 = x20 | ((u64)s_nrec << 20) | ((u64)nmt << 32) | ((u64)(h.spill ? 1u : 0u) << 48);
-        const u64 w1 = x20 | ((s_cnt[0] & 0x3FFFFFull) << 20) | ((s_cnt[1] & 0x3FFFFFull) << 42);
-        __hip_atomic_store(hd, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(hd + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        h.spill = 0;
-      }
-    }
-    if (me != kResGatherWg) continue;
-    __syncthreads();
-    // ---- the gatherer: gather the regions to the host, raise the slot's flag
-    uint32_t n = 0, nm = 0;
-    if (threadIdx.x == 0)  // the dispatch stamp (per-merge device time), loaded beside the headers
-      s_tlead = __hip_atomic_load(reinterpret_cast<const u64*>(p.cmd + ((uint32_t)X % kResRing) * 8 + 6),
-                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    {
-      u64 merged = 0, written = 0;
-      uint32_t spill = 0, my_nrec = 0, my_nmt = 0;
-      if (threadIdx.x == 0) {
-        s_cnt[0] = 0;
-        s_cnt[1] = 0;
-        s_nrec = 0;
-        s_nout = 0;
-      }
-      __syncthreads();
-      const uint32_t g = threadIdx.x;
-      if (g < T) {  // thread g waits for participant g's header, then takes its counts and resets it
-        u64* hd = reinterpret_cast<u64*>(sl.rhdr + (size_t)g * kRegHdr);
-        const uint32_t x20 = (uint32_t)X & 0xFFFFFu;
-        u64 v0, v1;
-        for (;;) {
-          v0 = __hip_atomic_load(hd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          v1 = __hip_atomic_load(hd + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (((uint32_t)v0 & 0xFFFFFu) == x20 && ((uint32_t)v1 & 0xFFFFFu) == x20) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        my_nrec = (uint32_t)(v0 >> 20) & 0xFFFu;
-        my_nmt = (uint32_t)(v0 >> 32) & 0xFFFFu;
-        spill = (uint32_t)(v0 >> 48) & 1u;
-        merged = (v1 >> 20) & 0x3FFFFFull;
-        written = (v1 >> 42) & 0x3FFFFFull;
-        __hip_atomic_store(hd, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // drained before the flag
-        __hip_atomic_store(hd + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (p.stamps) {  // diagnostic: all regions published
-        __syncthreads();
-        if (threadIdx.x == 0) s_ts[0] = __builtin_amdgcn_s_memrealtime();
-      }
-      // per-wave totals first (each participant's counts fit 22 bits): one LDS atomic per wave,
-      // not one per participant on the same address
-      const uint32_t wm = wave_scan_add((uint32_t)merged), ww = wave_scan_add((uint32_t)written);
-      const bool any_spill = __any(spill != 0);
-      const uint32_t ir = wave_scan_add(my_nrec), im = wave_scan_add(my_nmt);
-      if (lane == 63) {
-        if (wm) atomicAdd(&s_cnt[0], (u64)wm);
-        if (ww) atomicAdd(&s_cnt[1], (u64)ww);
-        if (any_spill) atomicOr(&s_nrec, 1u);
-        s_wtot[0][wid] = ir;
-        s_wtot[1][wid] = im;
-      }
-      __syncthreads();
-      uint32_t br = 0, bm = 0;
-      for (int w = 0; w < wid; ++w) {
-        br += s_wtot[0][w];
-        bm += s_wtot[1][w];
-      }
-      if (g < T) {
-        s_pre[g] = br + ir - my_nrec;
-        s_pmt[g] = bm + im - my_nmt;
-      }
-      if (g == T - 1) {
-        s_pre[T] = br + ir;
-        s_pmt[T] = bm + im;
-      }
-      __syncthreads();
-      n = s_pre[T];
-      nm = s_pmt[T];
-      if (p.stamps && threadIdx.x == 0) s_ts[1] = __builtin_amdgcn_s_memrealtime();
-      auto owner = [&](const uint32_t* pre, uint32_t i) {
-        uint32_t lo = 0, hi = T;
-        while (hi - lo > 1) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if (pre[mid] <= i) lo = mid;
-          else hi = mid;
-        }
-        return lo;
-      };
-      for (uint32_t i0 = 0; i0 < n; i0 += kRT * kGB) {
-        u64 r[kGB][3];
-#pragma unroll
-        for (int k = 0; k < kGB; ++k) {
-          const uint32_t i = i0 + k * kRT + threadIdx.x;
-          if (i < n) {
-            const uint32_t o = owner(s_pre, i);
-            const u64* src = sl.rrec + ((size_t)o * kDeltaLdsW + (i - s_pre[o])) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) r[k][c] = __hip_atomic_load(src + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        if (p.stamps && i0 == 0) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __syncthreads();
-          if (threadIdx.x == 0) s_ts[2] = __builtin_amdgcn_s_memrealtime();
-        }
-#pragma unroll
-        for (int k = 0; k < kGB; ++k) {  // combine the participants' records per key in the LDS hash
-          const uint32_t i = i0 + k * kRT + threadIdx.x;
-          if (i >= n) continue;
-          const uint32_t key = (uint32_t)r[k][0];
-          uint32_t hs = (key * 2654435761u) >> (32 - __builtin_ctz(kResDeltaW));
-          bool done = false;
-          for (int probe = 0; probe < 16 && !done; ++probe) {
-            const uint32_t prev = atomicCAS(&h.key[hs], kEmpty32, key);
-            if (prev == kEmpty32 || prev == key) {
-              atomicAdd(&h.sum[hs], r[k][1]);
-              atomicMin(&h.ft[hs], r[k][2]);
-              done = true;
-            } else {
-              hs = (hs + 1) & (kResDeltaW - 1);
-            }
-          }
-          if (!done) sys_record(sl.out + atomicAdd(&s_nout, 1u), key, r[k][1], r[k][2]);  // the host combines these
-        }
-      }
-      if (p.stamps && threadIdx.x == 0) s_ts[3] = __builtin_amdgcn_s_memrealtime();
-      __syncthreads();
-      for (int i = threadIdx.x; i < kResDeltaW; i += kRT) {
-        const uint32_t key = h.key[i];
-        if (key == kEmpty32) continue;
-        sys_record(sl.out + atomicAdd(&s_nout, 1u), key, h.sum[i], h.ft[i]);
-        h.key[i] = kEmpty32;
-        h.sum[i] = 0;
-        h.ft[i] = kEmpty64;
-      }
-      __syncthreads();
-      n = s_nout;
-      if (nm > p.mt_dense) nm = kAllTiles;  // X is in most tiles: the host marks it everywhere
-      if (nm != kAllTiles) {
-        // the matched tiles as a bitmap over every tile, built in this workgroup's LDS (the
-        // gatherer owns no tiles: its dynamic area is free), so the host takes X's tile set as
-        // is instead of sorting a list of up to ntiles / 2 entries
-        uint32_t* s_bits = reinterpret_cast<uint32_t*>(s_dyn);
-        for (uint32_t i = threadIdx.x; i < p.mt_words; i += kRT) s_bits[i] = 0;
-        __syncthreads();
-        constexpr int kMB = 8;  // tile ids in flight per thread
-        for (uint32_t i0 = 0; i0 < nm; i0 += kRT * kMB) {
-          uint32_t t[kMB];
-#pragma unroll
-          for (int k = 0; k < kMB; ++k) {
-            const uint32_t i = i0 + k * kRT + threadIdx.x;
-            t[k] = kAllTiles;
-            if (i < nm) {
-              const uint32_t o = owner(s_pmt, i);
-              t[k] = __hip_atomic_load(sl.rtile + (size_t)o * kResMaxTiles + (i - s_pmt[o]), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < kMB; ++k)
-            if (t[k] != kAllTiles) atomicOr(&s_bits[t[k] >> 5], 1u << (t[k] & 31));
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < p.mt_words; i += kRT) sys_store(sl.hmlist + i, s_bits[i]);
-      }
-      if (s_nrec) {  // spilled deltas in the global tables: all of them follow the records
-        __syncthreads();
-        if (threadIdx.x == 0) s_cmd[7] = atomicAdd(sl.dcount, 0u);
-        __syncthreads();
-        const uint32_t ngl = s_cmd[7];
-        for (uint32_t i = threadIdx.x; i < ngl; i += kRT) {
-          const uint32_t key = atomicOr(&sl.dlist[i], 0u);
-          const u64 sum = atomicExch(&sl.dsum[key], 0ull);
-          const u64 ft = atomicExch(&sl.dft[key], kEmpty64);
-          sys_record(sl.out + n + i, key, sum, ft);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) atomicExch(sl.dcount, 0u);
-        n += ngl;
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const u64 t_leader = s_tlead;
-      sys_store(&sl.hstats[0], s_cnt[0]);
-      sys_store(&sl.hstats[1], s_cnt[1]);
-      sys_store(&sl.hstats[2], (u64)__builtin_amdgcn_s_memrealtime() - t_leader);
-      if (p.stamps) {  // diagnostic: the gatherer's phases, relative to the leader's dispatch
-        for (int k = 0; k < 4; ++k) sys_store(&sl.hstats[3 + k], s_ts[k] - t_leader);
-        sys_store(&sl.hstats[7], (u64)s_pre[T]);  // records before the combine
-        sys_store(&sl.hstats[8], t_leader);        // raw dispatch tick (the host's per-merge log)
-      }
-      sys_store(&sl.hcount[0], n);
-      sys_store(&sl.hcount[2], nm);
-      sys_flag(&sl.hcount[1], (uint32_t)X);  // the host clears the flag before posting to the slot
-    }
-  }
-  // ---- STOP (or the leader's time-out): the tiles go back to HBM
-  for (uint32_t i = wid; i < nt; i += kRW) {
-    const uint32_t len = s_len[i];
-    if constexpr (kLdsTok) {
-      int32_t* dst = p.tok + s_toff[i];
-      const int32_t* src = s_res + s_lofs[i];
-      const uint32_t n4 = (len + 3u) >> 2;
-      for (uint32_t q = (uint32_t)lane; q < n4; q += 64) {
-        int4 x = *reinterpret_cast<const int4*>(src + 4 * q);
-        if (4 * q + 1 >= len) x.y = kPad;
-        if (4 * q + 2 >= len) x.z = kPad;
-        if (4 * q + 3 >= len) x.w = kPad;
-        *reinterpret_cast<int4*>(dst + 4 * q) = x;
-      }
-    }
-    if (lane == 0) p.tile_len[t0 + i] = len;
-  }
-  if (threadIdx.x == 0 && exit_op != kOpStop) {
-    __threadfence_system();
-    __hip_atomic_store(&p.status[0], exit_op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
 // Multi-GPU (K4 after the all-gather): the gathered buckets -> one host-visible record list.
 // Rank r contributes the records that are valid in its bucket: min(count, bucket) — or, when
 // its spilled deltas still wait for k_collect, min(k_collect offset, bucket); the rest goes
@@ -2173,630 +912,7 @@ __global__ __launch_bounds__(kThreads) void k_sig_build(const int32_t* tok, cons
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// K1: pair count
-struct CountParams {
-  const int32_t* tok;
-  const uint64_t* tile_off;
-  const uint32_t* tile_len;
-  uint32_t ntiles;
-  const uint64_t* weight;
-  int32_t unk;
-  u64* tkey;
-  u64* tcnt;
-  u64* tft;
-  u64 tmask;
-  uint32_t* overflow;
-};
-
-struct PairLds {
-  u64 key[kPairLds];
-  u64 cnt[kPairLds];
-  u64 ft[kPairLds];
-};
-
-__device__ __forceinline__ void pair_global(const CountParams& p, u64 key, u64 c, u64 ft) {
-  u64 s = mix64(key) & p.tmask;
-  for (u64 probe = 0; probe <= p.tmask; ++probe) {
-    const u64 prev = atomicCAS(&p.tkey[s], kEmpty64, key);
-    if (prev == kEmpty64 || prev == key) {
-      atomicAdd(&p.tcnt[s], c);
-      atomicMin(&p.tft[s], ft);
-      return;
-    }
-    s = (s + 1) & p.tmask;
-  }
-  atomicOr(p.overflow, 1u);
-}
-
-__device__ __forceinline__ void pair_emit(PairLds& h, const CountParams& p, u64 key, u64 c, u64 ft) {
-  uint32_t s = (uint32_t)(mix64(key) >> 53);  // 11 bits
-  for (int probe = 0; probe < 16; ++probe) {
-    const u64 prev = atomicCAS(&h.key[s], kEmpty64, key);
-    if (prev == kEmpty64 || prev == key) {
-      atomicAdd(&h.cnt[s], c);
-      atomicMin(&h.ft[s], ft);
-      return;
-    }
-    s = (s + 1) & (kPairLds - 1);
-  }
-  pair_global(p, key, c, ft);
-}
-
-template <bool kWeighted>
-__global__ __launch_bounds__(kThreads) void k_pair_count(CountParams p) {
-  __shared__ PairLds h;
-  __shared__ ScanLds s_scan;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < kPairLds; i += kThreads) {
-    h.key[i] = kEmpty64;
-    h.cnt[i] = 0;
-    h.ft[i] = kEmpty64;
-  }
-  __syncthreads();
-  const int p0 = tid * kPer;
-  for (uint32_t tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
-    const uint32_t len = p.tile_len[tile];
-    const int32_t* base = p.tok + p.tile_off[tile];
-    u64 c_hdr = 0;
-    for (uint32_t cs = 0; cs < len; cs += kChunk) {
-      const uint32_t cl = min((uint32_t)kChunk, len - cs);
-      int32_t v[kPer];
-      load_chunk(base, cs, cl, p0, v);
-      const int32_t nx = next_token(base, cs, len, p0, v[0]);
-      u64 hl = 0;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j)
-        if (is_hdr(v[j]) && p0 + j < (int)cl) hl = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(v[j]);
-      u64 hdr_ex, hdr_tot;
-      int cx, ct;
-      block_scan_hdr_cnt(hl, 0, s_scan, &hdr_ex, &cx, &hdr_tot, &ct);
-      u64 hdr = hdr_ex > c_hdr ? hdr_ex : c_hdr;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        const int32_t x = v[j];
-        const int32_t y = j + 1 < kPer ? v[j + 1] : nx;
-        if (is_hdr(x)) {
-          if (p0 + j < (int)cl) hdr = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(x);
-          continue;
-        }
-        if (is_hdr(y) || x == p.unk || y == p.unk) continue;
-        const uint32_t hidx = (uint32_t)(hdr >> 32) - 1u;
-        const uint32_t rank = (uint32_t)hdr;
-        const u64 w = kWeighted ? p.weight[rank] : 1ull;
-        const u64 key = ((u64)(uint32_t)x << 32) | (uint32_t)y;
-        pair_emit(h, p, key, w, ((u64)rank << 32) | (u64)(cs + p0 + j - hidx - 1u));
-      }
-      c_hdr = hdr_tot > c_hdr ? hdr_tot : c_hdr;
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < kPairLds; i += kThreads)
-    if (h.key[i] != kEmpty64) pair_global(p, h.key[i], h.cnt[i], h.ft[i]);
-}
-
-__global__ __launch_bounds__(kThreads) void k_pair_collect(const u64* tkey, const u64* tcnt, const u64* tft, u64 cap,
-                                                            PairCount* out, uint32_t out_cap, uint32_t* n) {
-  for (u64 i = (u64)blockIdx.x * kThreads + threadIdx.x; i < cap; i += (u64)gridDim.x * kThreads) {
-    const u64 k = tkey[i];
-    if (k == kEmpty64) continue;
-    PairCount pc;
-    pc.a = (int32_t)(uint32_t)(k >> 32);
-    pc.b = (int32_t)(uint32_t)k;
-    pc.count = tcnt[i];
-    pc.ft = tft[i];
-    const uint32_t i_out = atomicAdd(n + 1, 1u);
-    if (i_out < out_cap) out[i_out] = pc;
-    else atomicOr(n, 2u);
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K1 when every id is a byte (the initial count: ids < 256, unk skipped): a dense 256 x 256
-// table.  One wave per tile (16 tokens per lane, DPP header scan), 512-thread workgroups for
-// memory-level parallelism, a 4096-slot LDS pair hash per workgroup (first touch updated only
-// when smaller), spills and the final flush go straight to the dense HBM table (no probing).
-constexpr int kDenseThreads = 512;
-constexpr int kDenseWaves = kDenseThreads / 64;
-constexpr int kDenseLds = 4096;
-constexpr uint32_t kDensePairs = 256u * 256u;
-
-struct DenseCountParams {
-  const int32_t* tok;
-  const uint64_t* tile_off;
-  const uint32_t* tile_len;
-  uint32_t ntiles;
-  const uint64_t* weight;
-  int32_t unk;
-  u64* cnt;  // kDensePairs, zeroed
-  u64* ft;   // kDensePairs, all ones
-};
-
-// Counts are u64 for weighted (types) tiles and u32 for unweighted (stream) ones: a workgroup
-// never sees 2^32 occurrences, and 32-bit LDS atomics are the cheaper ones.
-template <class C>
-struct DenseLds {
-  uint32_t key[kDenseLds];
-  C cnt[kDenseLds];
-  u64 ft[kDenseLds];
-};
-
-template <class C>
-__device__ __forceinline__ void dense_emit(DenseLds<C>& h, const DenseCountParams& p, uint32_t key, C w, u64 ft) {
-  uint32_t s = (key * 2654435761u) >> (32 - 12);
-  for (int probe = 0; probe < 8; ++probe) {
-    uint32_t k = h.key[s];
-    if (k == kEmpty32) {
-      k = atomicCAS(&h.key[s], kEmpty32, key);
-      if (k == kEmpty32) k = key;
-    }
-    if (k == key) {
-      atomicAdd(&h.cnt[s], w);
-      if (ft < h.ft[s]) atomicMin(&h.ft[s], ft);
-      return;
-    }
-    s = (s + 1) & (kDenseLds - 1);
-  }
-  atomicAdd(&p.cnt[key], (u64)w);
-  atomicMin(&p.ft[key], ft);
-}
-
-template <bool kWeighted>
-__global__ __launch_bounds__(kDenseThreads) void k_pair_dense(DenseCountParams p) {
-  typedef typename std::conditional<kWeighted, u64, uint32_t>::type C;
-  __shared__ DenseLds<C> h;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int p0 = lane * kPer;
-  for (int i = threadIdx.x; i < kDenseLds; i += kDenseThreads) {
-    h.key[i] = kEmpty32;
-    h.cnt[i] = 0;
-    h.ft[i] = kEmpty64;
-  }
-  __syncthreads();
-  for (uint32_t t = blockIdx.x * kDenseWaves + wid; t < p.ntiles; t += gridDim.x * kDenseWaves) {
-    const uint32_t len = p.tile_len[t];
-    const int32_t* base = p.tok + p.tile_off[t];
-    u64 c_hdr = 0;  // ((index + 1) << 32) | rank of the last header so far
-    for (uint32_t cs = 0; cs < len; cs += kWaveTok) {
-      const uint32_t cl = min((uint32_t)kWaveTok, len - cs);
-      int32_t v[kPer];
-      load_chunk(base, cs, cl, p0, v);
-      const int32_t nx = next_token(base, cs, len, p0, v[0]);
-      uint32_t hmask = 0;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j)
-        if (is_hdr(v[j]) && p0 + j < (int)cl) hmask |= 1u << j;
-      u64 hl = 0;
-      if (hmask) {
-        const int j = 31 - __clz(hmask);
-        hl = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(v[j]);
-      }
-      const u64 hinc = wave_scan_max64(hl);
-      u64 hdr = wave_prev64(hinc);
-      hdr = hdr > c_hdr ? hdr : c_hdr;
-      uint32_t w_rank = ~0u;
-      C w = 1;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        const int32_t x = v[j];
-        const int32_t y = j + 1 < kPer ? v[j + 1] : nx;
-        if (is_hdr(x)) {
-          hdr = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(x);
-          continue;
-        }
-        if (is_hdr(y) || x == p.unk || y == p.unk) continue;
-        const uint32_t hidx = (uint32_t)(hdr >> 32) - 1u;
-        const uint32_t rank = (uint32_t)hdr;
-        if (kWeighted && rank != w_rank) {
-          w = (C)p.weight[rank];
-          w_rank = rank;
-        }
-        const uint32_t key = ((uint32_t)x << 8) | (uint32_t)y;
-        dense_emit(h, p, key, w, ((u64)rank << 32) | (u64)(cs + p0 + j - hidx - 1u));
-      }
-      const u64 htot = lane_read64(hinc, 63);
-      c_hdr = htot > c_hdr ? htot : c_hdr;
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kDenseLds; i += kDenseThreads) {
-    const uint32_t k = h.key[i];
-    if (k == kEmpty32) continue;
-    atomicAdd(&p.cnt[k], (u64)h.cnt[i]);
-    atomicMin(&p.ft[k], h.ft[i]);
-  }
-}
-
-// Dense table -> PairCount list (pairs with a count).
-__global__ __launch_bounds__(kThreads) void k_pair_dense_collect(const u64* cnt, const u64* ft, PairCount* out,
-                                                                  uint32_t* n) {
-  for (uint32_t k = blockIdx.x * kThreads + threadIdx.x; k < kDensePairs; k += gridDim.x * kThreads) {
-    if (ft[k] == kEmpty64) continue;
-    PairCount pc;
-    pc.a = (int32_t)(k >> 8);
-    pc.b = (int32_t)(k & 255u);
-    pc.count = cnt[k];
-    pc.ft = ft[k];
-    out[atomicAdd(n, 1u)] = pc;
-  }
-}
-
-// K5 check (debug): the largest count of a collected pair list, and (a, b)'s count.
-__global__ __launch_bounds__(kThreads) void k_pair_max(const PairCount* pc, uint32_t n, int32_t a, int32_t b, u64* r) {
-  u64 mx = 0;
-  for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
-    const PairCount p = pc[i];
-    mx = p.count > mx ? p.count : mx;
-    if (p.a == a && p.b == b) r[1] = p.count;  // one entry per pair: a single writer
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 v = (u64)__shfl_xor((unsigned long long)mx, o);
-    mx = v > mx ? v : mx;
-  }
-  if ((threadIdx.x & 63) == 0 && mx) atomicMax(reinterpret_cast<unsigned long long*>(r), (unsigned long long)mx);
-}
-
-// ------------------------------------------------------------------------------------------
-// K1 bulk (stream layout, every id a byte): pair counts only, over the tiles past the ft tiles
-// (the first occurrence of every type is packed into tiles [0, ft_tiles), where k_pair_dense
-// takes first touch; every other occurrence repeats a type, so only its counts matter).
-//
-// One 1024-thread workgroup per CU keeps the whole 256 x 256 table in LDS as packed 16-bit
-// counters (two pairs per dword, 128 KiB): a pair occurrence is one ds_add_rtn_u32 at a fixed
-// address, no hashing, no probing, nothing in HBM until the end.  A counter never wraps: the one
-// atomic that takes a half from 0x7FFF to 0x8000 (exactly one per crossing, increments are 1)
-// moves 0x8000 to the HBM table and takes it back off the half; meanwhile at most 16 K other
-// increments can land, so a half stays below 0xC000 and never carries into its neighbour.
-// Each lane streams 2 tiles x 16 tokens per iteration (8 x 16 B loads in flight), and the final
-// flush adds the non-zero halves to the HBM table (one u64 atomic per pair per workgroup).
-#ifndef SHRED_HIST_CO
-#define SHRED_HIST_CO 1
-#endif
-#ifndef SHRED_HIST_MODE
-#define SHRED_HIST_MODE 0  // diagnostic 1: no LDS atomics (read ceiling of the access pattern)
-#endif
-constexpr int kHistThreads = 1024;
-constexpr int kHistWaves = kHistThreads / 64;
-constexpr int kHistWords = kDensePairs / 2;
-
-// One pair occurrence (x, y) per element: add 1 to its 16-bit half; `old` gets the dword before
-// the add.  Branch-free so that a lane's 16 atomics issue back to back behind one wait: an
-// inactive element adds 0 to a per-lane dummy word past the table (distinct banks).
-__device__ __forceinline__ void hist_add(uint32_t* h, int32_t x, int32_t y, int32_t unk, int lane, uint32_t& key,
-                                         uint32_t& old, bool& on, uint32_t& sink) {
-  // bitwise, not &&: short-circuit evaluation compiles to a branch per element
-  on = (bool)((unsigned)(x >= kHeaderLimit) & (unsigned)(y >= kHeaderLimit) & (unsigned)(x != unk) &
-              (unsigned)(y != unk));
-  key = ((uint32_t)x << 8) | ((uint32_t)y & 255u);
-#if SHRED_HIST_MODE == 1
-  old = 0;
-  if (on) sink += key;
-#else
-  const uint32_t a = on ? key >> 1 : (uint32_t)(kHistWords + lane);
-  const uint32_t inc = on ? ((key & 1u) ? 0x10000u : 1u) : 0u;
-  old = __hip_atomic_fetch_add(&h[a], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-}
-__device__ __forceinline__ void hist_fix(uint32_t* h, uint32_t key, uint32_t old, bool on, u64* cnt) {
-  const uint32_t half = (key & 1u) ? (old >> 16) : (old & 0xFFFFu);
-  if (on && half == 0x7FFFu) {
-    atomicSub(&h[key >> 1], (key & 1u) ? 0x80000000u : 0x8000u);
-    atomicAdd(&cnt[key], (u64)0x8000);
-  }
-}
-
-// 16 tokens per lane, lane-contiguous (load_chunk order): pairs (v[j], v[j+1]), then (v[15], nx).
-__device__ __forceinline__ void hist_tile(uint32_t* h, const int32_t (&v)[kPer], int32_t nx, int32_t unk, u64* cnt,
-                                          uint32_t& sink) {
-  uint32_t old[kPer], key[kPer];
-  bool on[kPer];
-#pragma unroll
-  for (int j = 0; j < kPer; ++j)
-    hist_add(h, v[j], j + 1 < kPer ? v[j + 1] : nx, unk, threadIdx.x & 63, key[j], old[j], on[j], sink);
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) hist_fix(h, key[j], old[j], on[j], cnt);
-}
-
-// Coalesced order for a tile of <= 1024 tokens: quad k of lane l holds tokens 256 k + 4 l .. +3,
-// so each 16-B load instruction reads 1 KiB contiguous.  The token after a quad is lane l+1's
-// first of the same quad (DPP), or for lane 63 lane 0's first of quad k+1.
-__device__ __forceinline__ void load_tile_co(const int32_t* base, uint32_t len, int lane, int32_t (&v)[kPer]) {
-  const int4* q = reinterpret_cast<const int4*>(base) + lane;
-  int4 x[kPer / 4];
-#pragma unroll
-  for (int k = 0; k < kPer / 4; ++k) x[k] = q[64 * k];
-#pragma unroll
-  for (int k = 0; k < kPer / 4; ++k) {
-    const int p = 256 * k + 4 * lane;
-    v[4 * k] = p < (int)len ? x[k].x : kPad;
-    v[4 * k + 1] = p + 1 < (int)len ? x[k].y : kPad;
-    v[4 * k + 2] = p + 2 < (int)len ? x[k].z : kPad;
-    v[4 * k + 3] = p + 3 < (int)len ? x[k].w : kPad;
-  }
-}
-__device__ __forceinline__ void hist_tile_co(uint32_t* h, const int32_t (&v)[kPer], int lane, int32_t unk, u64* cnt,
-                                             uint32_t& sink) {
-  uint32_t old[kPer], key[kPer];
-  bool on[kPer];
-#pragma unroll
-  for (int k = 0; k < kPer / 4; ++k) {
-    int32_t nx = wave_next(v[4 * k]);
-    if (lane == 63) nx = k + 1 < kPer / 4 ? (int32_t)lane_read((uint32_t)v[4 * k + 4], 0) : kPad;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = 4 * k + e;
-      hist_add(h, v[j], e < 3 ? v[j + 1] : nx, unk, lane, key[j], old[j], on[j], sink);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) hist_fix(h, key[j], old[j], on[j], cnt);
-}
-
-__global__ __launch_bounds__(kHistThreads) void k_pair_hist(const int32_t* tok, const uint64_t* tile_off,
-                                                             const uint32_t* tile_len, uint32_t t0, uint32_t t1,
-                                                             int32_t unk, u64* cnt) {
-  __shared__ uint32_t h[kHistWords + 64];  // + per-lane dummy words
-  for (int i = threadIdx.x; i < kHistWords + 64; i += kHistThreads) h[i] = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int p0 = lane * kPer;
-  const uint32_t stride = gridDim.x * kHistWaves;
-  uint32_t sink = 0;
-  for (uint32_t t = t0 + blockIdx.x * kHistWaves + wid; t < t1; t += 2 * stride) {
-    const uint32_t u = t + stride;
-    const bool two = u < t1;
-    const uint32_t lt = tile_len[t], lu = two ? tile_len[u] : 0u;
-    const int32_t* bt = tok + tile_off[t];
-    const int32_t* bu = tok + (two ? tile_off[u] : tile_off[t]);
-    if (lt <= (uint32_t)kWaveTok && lu <= (uint32_t)kWaveTok) {
-      // both tiles are one wave chunk: all 8 loads in flight together
-      int32_t va[kPer], vb[kPer];
-#if SHRED_HIST_CO
-      load_tile_co(bt, lt, lane, va);
-      load_tile_co(bu, lu, lane, vb);
-      hist_tile_co(h, va, lane, unk, cnt, sink);
-      hist_tile_co(h, vb, lane, unk, cnt, sink);
-#else
-      load_chunk(bt, 0, lt, p0, va);
-      load_chunk(bu, 0, lu, p0, vb);
-      const int32_t na = next_token(bt, 0, lt, p0, va[0]);
-      const int32_t nb = next_token(bu, 0, lu, p0, vb[0]);
-      hist_tile(h, va, na, unk, cnt, sink);
-      hist_tile(h, vb, nb, unk, cnt, sink);
-#endif
-      continue;
-    }
-    for (int k = 0; k < 2; ++k) {  // a tile holding one long word: chunk by chunk
-      const uint32_t len = k ? lu : lt;
-      const int32_t* base = k ? bu : bt;
-      for (uint32_t cs = 0; cs < len; cs += kWaveTok) {
-        int32_t v[kPer];
-        load_chunk(base, cs, min((uint32_t)kWaveTok, len - cs), p0, v);
-        hist_tile(h, v, next_token(base, cs, len, p0, v[0]), unk, cnt, sink);
-      }
-    }
-  }
-#if SHRED_HIST_MODE == 1
-  if (sink == 0x12345678u) h[0] = sink;  // keeps the loads alive in the diagnostic build
-#endif
-  __syncthreads();
-  for (int i = threadIdx.x; i < kHistWords; i += kHistThreads) {
-    const uint32_t w = h[i];
-    if (w & 0xFFFFu) atomicAdd(&cnt[2 * i], (u64)(w & 0xFFFFu));
-    if (w >> 16) atomicAdd(&cnt[2 * i + 1], (u64)(w >> 16));
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K6: final token histogram over ids [0, T) (the unk count lands on unk_id when it is in range)
-template <bool kWeighted>
-__global__ __launch_bounds__(kThreads) void k_token_freq(const int32_t* tok, const uint64_t* tile_off,
-                                                          const uint32_t* tile_len, uint32_t ntiles,
-                                                          const uint64_t* weight, uint32_t T, u64* freq) {
-  __shared__ ScanLds s_scan;
-  const int p0 = threadIdx.x * kPer;
-  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const uint32_t len = tile_len[tile];
-    const int32_t* base = tok + tile_off[tile];
-    u64 c_hdr = 0;
-    for (uint32_t cs = 0; cs < len; cs += kChunk) {
-      const uint32_t cl = min((uint32_t)kChunk, len - cs);
-      int32_t v[kPer];
-      load_chunk(base, cs, cl, p0, v);
-      u64 hl = 0;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j)
-        if (is_hdr(v[j]) && p0 + j < (int)cl) hl = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(v[j]);
-      u64 hdr_ex, hdr_tot;
-      int cx, ct;
-      block_scan_hdr_cnt(hl, 0, s_scan, &hdr_ex, &cx, &hdr_tot, &ct);
-      u64 hdr = hdr_ex > c_hdr ? hdr_ex : c_hdr;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        if (is_hdr(v[j])) {
-          if (p0 + j < (int)cl) hdr = ((u64)(cs + p0 + j + 1) << 32) | hdr_rank(v[j]);
-          continue;
-        }
-        if ((uint32_t)v[j] >= T) continue;
-        atomicAdd(&freq[v[j]], kWeighted ? weight[(uint32_t)hdr] : 1ull);
-      }
-      c_hdr = hdr_tot > c_hdr ? hdr_tot : c_hdr;
-    }
-  }
-}
-
-__global__ void k_sum_len(const uint32_t* tile_len, uint32_t n, u64* out) {
-  u64 s = 0;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) s += tile_len[i];
-  for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
-}
-
-// Achievable-bandwidth probes (the measured ceiling beside the nominal 8 TB/s):
-// a pure streaming read (4 x 16 B per lane in flight, xor-reduced so nothing is elided) and a
-// streaming copy, both grid-stride over 16-B vectors with a few workgroups per CU.
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_hbm_read(const v4u* __restrict__ src, size_t n16, uint32_t* out) {
-  v4u acc = {0, 0, 0, 0};
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + 3 * stride < n16; i += 4 * stride) {
-    const v4u a = __builtin_nontemporal_load(src + i), b = __builtin_nontemporal_load(src + i + stride);
-    const v4u c = __builtin_nontemporal_load(src + i + 2 * stride), d = __builtin_nontemporal_load(src + i + 3 * stride);
-    acc ^= a ^ b ^ c ^ d;
-  }
-  for (; i < n16; i += stride) acc ^= src[i];
-  const uint32_t x = acc.x ^ acc.y ^ acc.z ^ acc.w;
-  if (x == 0x9e3779b9u) out[blockIdx.x] = x;  // practically never taken; keeps the loads live
-}
-
-__global__ __launch_bounds__(256) void k_hbm_copy(const v4u* __restrict__ src, v4u* __restrict__ dst, size_t n16) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n16; i += 2 * stride) {
-    const v4u a = __builtin_nontemporal_load(src + i), b = __builtin_nontemporal_load(src + i + stride);
-    __builtin_nontemporal_store(a, dst + i);
-    __builtin_nontemporal_store(b, dst + i + stride);
-  }
-  for (; i < n16; i += stride) dst[i] = src[i];
-}
-
-inline hipStream_t S(void* s) { return (hipStream_t)s; }
-inline u64* U(uint64_t* p) { return reinterpret_cast<u64*>(p); }
-
-template <class T>
-T* dalloc(size_t n, size_t* acc) {
-  void* p = nullptr;
-  if (n == 0) n = 1;
-  HIP_OK(hipMalloc(&p, n * sizeof(T)));
-  *acc += n * sizeof(T);
-  return (T*)p;
-}
-
 }  // namespace
-
-// ==========================================================================================
-// Diagnostic (tests of k_resident's co-residency check): workgroups of 1024 threads that fill
-// every wave slot of all CUs but `free_cus`, spinning on their own stream until the host raises a
-// flag or `max_seconds` pass (every wave reaches one of the two exits).  Each workgroup marks
-// itself started.
-__global__ __launch_bounds__(1024) void k_occupy(const uint32_t* release, uint32_t* started, uint64_t max_ticks) {
-  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-  if (threadIdx.x == 0) __hip_atomic_store(started + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  for (;;) {
-    if (__hip_atomic_load(release, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) break;
-    if (__builtin_amdgcn_s_memrealtime() - t0 > max_ticks) break;
-    __builtin_amdgcn_s_sleep(64);
-  }
-}
-
-struct Occupier {
-  int ordinal;
-  hipStream_t stream;
-  uint32_t* host;  // pinned: [0] release flag, [1..] started marks
-  void* dev;
-  uint32_t groups;
-};
-
-void* Device::occupy(int ordinal, int free_cus, double max_seconds) {
-  if (max_seconds <= 0 || hipSetDevice(ordinal) != hipSuccess) return nullptr;
-  hipDeviceProp_t pr;
-  HIP_OK(hipGetDeviceProperties(&pr, ordinal));
-  const int per_cu = std::max(1, pr.maxThreadsPerMultiProcessor / 1024);
-  const int groups = per_cu * (pr.multiProcessorCount - free_cus);
-  const size_t lds = 0;
-  if (groups < 1) return nullptr;
-  Occupier* o = new Occupier{ordinal, nullptr, nullptr, nullptr, (uint32_t)groups};
-  HIP_OK(hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking));
-  const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
-  HIP_OK(hipHostMalloc((void**)&o->host, (size_t)(groups + 1) * sizeof(uint32_t), pin));
-  std::memset(o->host, 0, (size_t)(groups + 1) * sizeof(uint32_t));
-  HIP_OK(hipHostGetDevicePointer(&o->dev, o->host, 0));
-  uint32_t* d = static_cast<uint32_t*>(o->dev);
-  k_occupy<<<groups, 1024, lds, o->stream>>>(d, d + 1, (uint64_t)(max_seconds * 1e8));
-  HIP_OK(hipGetLastError());
-  const double t0 = now_seconds();  // until every workgroup runs (or 10 s)
-  for (;;) {
-    uint32_t n = 0;
-    for (int g = 0; g < groups; ++g) n += __atomic_load_n(&o->host[1 + g], __ATOMIC_ACQUIRE);
-    if (n == (uint32_t)groups || now_seconds() - t0 > 10.0) {
-      if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
- std::fprintf(stderr, "[OCCUPY] %u of %d workgroups (1024 threads, %d per CU) running after %.1f ms\n", n, groups, per_cu,
-                     1e3 * (now_seconds() - t0));
-      break;
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(100));
-  }
-  return o;
-}
-
-void Device::release(void* handle) {
-  Occupier* o = static_cast<Occupier*>(handle);
-  if (!o) return;
-  (void)hipSetDevice(o->ordinal);
-  __atomic_store_n(&o->host[0], 1u, __ATOMIC_RELEASE);
-  (void)hipStreamSynchronize(o->stream);
-  (void)hipStreamDestroy(o->stream);
-  (void)hipHostFree(o->host);
-  delete o;
-}
-
-int Device::hbm_probe(int ordinal, size_t bytes, int reps, double* read_gbps, double* copy_gbps) {
-  std::string why;
-  if (!available(&why) || bytes < (1u << 20) || reps < 1) return -1;
-  HIP_OK(hipSetDevice(ordinal));
-  hipDeviceProp_t prop;
-  HIP_OK(hipGetDeviceProperties(&prop, ordinal));
-  const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  const size_t n16 = bytes / 16;
-  v4u *a = nullptr, *b = nullptr;
-  uint32_t* sink = nullptr;
-  if (hipMalloc(&a, n16 * 16) != hipSuccess) return -1;
-  if (hipMalloc(&b, n16 * 16) != hipSuccess) {
-    HIP_OK(hipFree(a));
-    return -1;
-  }
-  const int grid = cus * 8;
-  HIP_OK(hipMalloc(&sink, grid * sizeof(uint32_t)));
-  hipStream_t s;
-  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  HIP_OK(hipMemsetAsync(a, 0x5a, n16 * 16, s));
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  float ms = 0;
-  for (int w = 0; w < 2; ++w) k_hbm_read<<<grid, 256, 0, s>>>(a, n16, sink);
-  HIP_OK(hipEventRecord(e0, s));
-  for (int r = 0; r < reps; ++r) k_hbm_read<<<grid, 256, 0, s>>>(a, n16, sink);
-  HIP_OK(hipEventRecord(e1, s));
-  HIP_OK(hipEventSynchronize(e1));
-  HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-  if (read_gbps) *read_gbps = (double)n16 * 16 * reps / (ms * 1e-3) / 1e9;
-  for (int w = 0; w < 2; ++w) k_hbm_copy<<<grid, 256, 0, s>>>(a, b, n16);
-  HIP_OK(hipEventRecord(e0, s));
-  for (int r = 0; r < reps; ++r) k_hbm_copy<<<grid, 256, 0, s>>>(a, b, n16);
-  HIP_OK(hipEventRecord(e1, s));
-  HIP_OK(hipEventSynchronize(e1));
-  HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-  if (copy_gbps) *copy_gbps = 2.0 * (double)n16 * 16 * reps / (ms * 1e-3) / 1e9;
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  HIP_OK(hipStreamDestroy(s));
-  HIP_OK(hipFree(a));
-  HIP_OK(hipFree(b));
-  HIP_OK(hipFree(sink));
-  return 0;
-}
-
-bool Device::available(std::string* why) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n == 0) {
-    if (why) *why = e != hipSuccess ? std::string("hipGetDeviceCount: ") + hipGetErrorString(e) : "no HIP device";
-    return false;
-  }
-  return true;
-}
 
 Device::Device(int device_ordinal) : ordinal_(device_ordinal) {
   HIP_OK(hipSetDevice(ordinal_));
@@ -3059,9 +1175,7 @@ void Device::index_sync() {
   wl_kms_seen_ = ws.kernel_ms;
   if (wl_->tiles_dirty() && ntiles_) {
     wl_->sync_tiles(tok_, tile_off_, tile_len_);
-    const int grid = (int)std::min<size_t>((ntiles_ + kWaves - 1) / kWaves, (size_t)cu_count_ * 8);
-    k_sig_build<<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, sig_);
-    HIP_OK(hipGetLastError());
+    rebuild_signatures();
   }
 }
 
@@ -3081,32 +1195,6 @@ void Device::hybrid_switch(int32_t X) {
   switch_ms_ += 1e3 * (now_seconds() - t0);
 }
 
-// The resident launch aborted before dispatching anything (some workgroups never became
-// resident: another kernel or process holds CUs).  Resident is off for this device from here on;
-// the merges posted to it run again, in order, on the indexed loop (or the launch path).  The
-// launch's missing workgroups may start only once those CUs free up, and they hold its stream
-// until then, so all further work moves to a fresh stream.
-void Device::resident_abort_fallback() {
-  std::vector<ResPost> inflight;
-  inflight.swap(res_posted_);
-  res_running_ = false;
-  resident_ok_ = false;
-  ++res_aborts_;
-  for (int32_t& x : res_abandoned_) x = -1;
-  retired_streams_.push_back(stream_);
-  hipStream_t s;
-  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  stream_ = s;
-  if (wl_) wl_->set_stream(stream_);
-  if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
-    std::fprintf(stderr, "[RESIDENT] launch aborted (not every workgroup resident): %zu merges move to the %s\n",
-                 inflight.size(), wl_ && wl_->ready() ? "indexed loop" : "launch path");
-  for (const ResPost& rp : inflight) {
-    const int32_t ab[2] = {rp.a, rp.b};
-    merge_chain(ab, 1, rp.X);
-  }
-}
-
 // A tile-path merge ran after the loop's last merge: the loop takes the tiles' words.
 void Device::index_refresh() {
   park();
@@ -3124,9 +1212,7 @@ void Device::reset_tokens() {
   HIP_OK(hipMemcpyAsync(tok_, tok0_, (tok_elems_ + 4) * sizeof(int32_t), hipMemcpyDeviceToDevice, S(stream_)));
   if (ntiles_) {
     HIP_OK(hipMemcpyAsync(tile_len_, tile_len0_, ntiles_ * sizeof(uint32_t), hipMemcpyDeviceToDevice, S(stream_)));
-    const int grid = (int)std::min<size_t>((ntiles_ + kWaves - 1) / kWaves, (size_t)cu_count_ * 8);
-    k_sig_build<<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, sig_);
-    HIP_OK(hipGetLastError());
+    rebuild_signatures();
   }
   live_tokens_est_ = live_tokens0_;
   max_id_seen_ = max_id0_;
@@ -3147,19 +1233,11 @@ void Device::reset_tokens() {
   }
 }
 
-uint64_t Device::live_tokens() {
-  HIP_OK(hipSetDevice(ordinal_));
-  park();
-  if (!ntiles_) return 0;
-  u64* d = dalloc<u64>(1, &bytes_alloc_);
-  HIP_OK(hipMemsetAsync(d, 0, sizeof(u64), S(stream_)));
-  k_sum_len<<<64, 256, 0, S(stream_)>>>(tile_len_, (uint32_t)ntiles_, d);
-  u64 h = 0;
-  HIP_OK(hipMemcpyAsync(&h, d, sizeof(u64), hipMemcpyDeviceToHost, S(stream_)));
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  HIP_OK(hipFree(d));
-  bytes_alloc_ -= sizeof(u64);
-  return h;
+// Every tile's pair signature from its tokens in HBM (k_merge / k_unmerge test them).
+void Device::rebuild_signatures() {
+  const int grid = (int)std::min<size_t>((ntiles_ + kWaves - 1) / kWaves, (size_t)cu_count_ * 8);
+  k_sig_build<<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, sig_);
+  HIP_OK(hipGetLastError());
 }
 
 // Sizes one merge slot's tables for ids < need.  Only called for the slot about to be
@@ -3203,167 +1281,6 @@ void Device::ensure_slots(MergeSlot& s, uint32_t need) {
   }
   s.cap = cap;
   HIP_OK(hipStreamSynchronize(S(stream_)));
-}
-
-void Device::count_pairs(int32_t unk_id, std::vector<PairCount>* out) {
-  HIP_OK(hipSetDevice(ordinal_));
-  park();
-  out->clear();
-  if (!ntiles_) {
-    if (xchg_.world > 1) dist_merge_pairs(out);
-    return;
-  }
-  const uint64_t live = live_tokens();
-  if (max_id_seen_ < kBaseVocab) {  // every id in the stream is a byte or unk (skipped)
-    count_pairs_dense(unk_id, live, out);
-    if (xchg_.world > 1) dist_merge_pairs(out);
-    return;
-  }
-  // distinct pairs <= live tokens and <= (ids in play)^2
-  const uint64_t ids = (uint64_t)std::max<int32_t>(max_id_seen_, kBaseVocab) + 2;
-  uint64_t bound = std::min<uint64_t>(live, ids * ids);
-  uint64_t cap = 1024;
-  while (cap < 2 * bound && cap < (1ull << 27)) cap *= 2;
-  size_t acc = 0;
-  u64* tkey = dalloc<u64>(cap, &acc);
-  u64* tcnt = dalloc<u64>(cap, &acc);
-  u64* tft = dalloc<u64>(cap, &acc);
-  uint32_t* flags = dalloc<uint32_t>(2, &acc);
-  HIP_OK(hipMemsetAsync(tkey, 0xFF, cap * sizeof(u64), S(stream_)));
-  HIP_OK(hipMemsetAsync(tcnt, 0, cap * sizeof(u64), S(stream_)));
-  HIP_OK(hipMemsetAsync(tft, 0xFF, cap * sizeof(u64), S(stream_)));
-  HIP_OK(hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), S(stream_)));
-  CountParams cp{tok_, tile_off_, tile_len_, (uint32_t)ntiles_, weight_, unk_id, tkey, tcnt, tft, cap - 1, flags};
-  const int grid = (int)std::min<size_t>(ntiles_, (size_t)cu_count_ * 2);
-  if (timing_) HIP_OK(hipEventRecord((hipEvent_t)ev_[2], S(stream_)));
-  if (layout_ == Layout::kStream) k_pair_count<false><<<grid, kThreads, 0, S(stream_)>>>(cp);
-  else k_pair_count<true><<<grid, kThreads, 0, S(stream_)>>>(cp);
-  HIP_OK(hipGetLastError());
-  if (timing_) HIP_OK(hipEventRecord((hipEvent_t)ev_[3], S(stream_)));
-  const uint32_t out_cap = (uint32_t)std::min<uint64_t>(cap, bound + 1);
-  PairCount* dout = dalloc<PairCount>(out_cap, &acc);
-  k_pair_collect<<<512, kThreads, 0, S(stream_)>>>(tkey, tcnt, tft, cap, dout, out_cap, flags);
-  HIP_OK(hipGetLastError());
-  uint32_t hflags[2];
-  HIP_OK(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, S(stream_)));
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  if (hflags[0]) fatal("pair table overflow in k_pair_count / k_pair_collect");
-  if (pmq_) {
-    reduce_pair_max(dout, hflags[1]);
-  } else {
-    out->resize(hflags[1]);
-    if (hflags[1])
-      HIP_OK(hipMemcpy(out->data(), dout, hflags[1] * sizeof(PairCount), hipMemcpyDeviceToHost));
-  }
-  if (timing_) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[2], (hipEvent_t)ev_[3]));
-    times_.count_ms += ms;
-    times_.count_launches += 1;
-    // 4 B per token and per word header (the boundary), 8 B weight per word in the types
-    // layout, 12 B of tile descriptor per tile
-    times_.count_bytes += 4.0 * (double)live + 12.0 * (double)ntiles_ +
-                          (layout_ == Layout::kTypes ? 8.0 * (double)nentries_ : 0.0);
-  }
-  for (void* p : {(void*)tkey, (void*)tcnt, (void*)tft, (void*)flags, (void*)dout}) HIP_OK(hipFree(p));
-  if (xchg_.world > 1) dist_merge_pairs(out);
-}
-
-// K1 with every id a byte: dense tables, no hashing in HBM.
-void Device::count_pairs_dense(int32_t unk_id, uint64_t live, std::vector<PairCount>* out) {
-  size_t acc = 0;
-  u64* cnt = dalloc<u64>(kDensePairs, &acc);
-  u64* ft = dalloc<u64>(kDensePairs, &acc);
-  uint32_t* n = dalloc<uint32_t>(1, &acc);
-  PairCount* dout = dalloc<PairCount>(kDensePairs, &acc);
-  HIP_OK(hipMemsetAsync(cnt, 0, kDensePairs * sizeof(u64), S(stream_)));
-  HIP_OK(hipMemsetAsync(ft, 0xFF, kDensePairs * sizeof(u64), S(stream_)));
-  HIP_OK(hipMemsetAsync(n, 0, sizeof(uint32_t), S(stream_)));
-  // stream layout: first touch (and counts) from the ft tiles, counts alone from the rest
-  const size_t ft_tiles = layout_ == Layout::kStream ? ft_tiles_ : ntiles_;
-  DenseCountParams dp{tok_, tile_off_, tile_len_, (uint32_t)ft_tiles, weight_, unk_id, cnt, ft};
-  int per_cu = 0;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_pair_dense<true>),
-                                                      kDenseThreads, 0));
-  // >= SHRED_DENSE_TOK tokens per workgroup: each one flushes its LDS table with HBM atomics
-  const uint64_t ft_live = ft_tiles == ntiles_ ? live : ft_live_tokens_;
-  const size_t by_tokens = (size_t)(ft_live / SHRED_DENSE_TOK) + 1;
-  const int grid = (int)std::min<size_t>(std::min<size_t>((ft_tiles + kDenseWaves - 1) / kDenseWaves, by_tokens),
-                                         (size_t)cu_count_ * (size_t)std::max(1, per_cu));
-  if (timing_) HIP_OK(hipEventRecord((hipEvent_t)ev_[2], S(stream_)));
-  if (ft_tiles > 0) {
-    if (layout_ == Layout::kStream) k_pair_dense<false><<<grid, kDenseThreads, 0, S(stream_)>>>(dp);
-    else k_pair_dense<true><<<grid, kDenseThreads, 0, S(stream_)>>>(dp);
-    HIP_OK(hipGetLastError());
-  }
-  const bool bulk = ft_tiles < ntiles_;
-  if (bulk) {
-    if (timing_) HIP_OK(hipEventRecord((hipEvent_t)ev_[4], S(stream_)));
-    const size_t hist_grid = std::min<size_t>((ntiles_ - ft_tiles + kHistWaves - 1) / kHistWaves, (size_t)cu_count_);
-    k_pair_hist<<<(int)hist_grid, kHistThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ft_tiles,
-                                                                (uint32_t)ntiles_, unk_id, cnt);
-    HIP_OK(hipGetLastError());
-  }
-  if (timing_) HIP_OK(hipEventRecord((hipEvent_t)ev_[3], S(stream_)));
-  k_pair_dense_collect<<<64, kThreads, 0, S(stream_)>>>(cnt, ft, dout, n);
-  HIP_OK(hipGetLastError());
-  uint32_t hn = 0;
-  HIP_OK(hipMemcpyAsync(&hn, n, sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream_)));
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  if (pmq_) {
-    reduce_pair_max(dout, hn);
-  } else {
-    out->resize(hn);
-    if (hn) HIP_OK(hipMemcpy(out->data(), dout, hn * sizeof(PairCount), hipMemcpyDeviceToHost));
-  }
-  if (timing_) {
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[2], (hipEvent_t)ev_[3]));
-    times_.count_ms += ms;
-    times_.count_launches += 1;
-    // 4 B per token and per word header (the boundary), 8 B weight per word in the types
-    // layout, 12 B of tile descriptor per tile
-    times_.count_bytes += 4.0 * (double)live + 12.0 * (double)ntiles_ +
-                          (layout_ == Layout::kTypes ? 8.0 * (double)nentries_ : 0.0);
-    if (bulk) {  // k_pair_hist alone: 4 B per token (headers = word boundaries) + 12 B per tile
-      HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[4], (hipEvent_t)ev_[3]));
-      times_.hist_ms += ms;
-      times_.hist_launches += 1;
-      times_.hist_bytes += 4.0 * (double)(live - ft_live) + 12.0 * (double)(ntiles_ - ft_tiles);
-    }
-  }
-  for (void* q : {(void*)cnt, (void*)ft, (void*)n, (void*)dout}) HIP_OK(hipFree(q));
-}
-
-void Device::reduce_pair_max(const PairCount* dout, uint32_t n) {
-  size_t acc = 0;
-  u64* r = dalloc<u64>(2, &acc);
-  HIP_OK(hipMemsetAsync(r, 0, 2 * sizeof(u64), S(stream_)));
-  if (n) k_pair_max<<<(int)std::min<uint32_t>((n + kThreads - 1) / kThreads, 1024), kThreads, 0, S(stream_)>>>(
-      dout, n, pmq_->a, pmq_->b, r);
-  HIP_OK(hipGetLastError());
-  u64 h[2];
-  HIP_OK(hipMemcpyAsync(h, r, sizeof(h), hipMemcpyDeviceToHost, S(stream_)));
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  HIP_OK(hipFree(r));
-  pmq_->max_freq = h[0];
-  pmq_->ab_freq = h[1];
-}
-
-// K5 check: one rank reduces its fresh K1 histogram on the device; under RCCL the ranks' lists
-// are merged first (a pair's count is a sum over ranks), then reduced on the host.
-void Device::pair_max(int32_t unk_id, int32_t a, int32_t b, uint64_t* max_freq, uint64_t* ab_freq) {
-  if (xchg_.world > 1) {
-    Backend::pair_max(unk_id, a, b, max_freq, ab_freq);
-    return;
-  }
-  PairMaxQuery q{a, b, 0, 0};
-  pmq_ = &q;
-  std::vector<PairCount> none;
-  count_pairs(unk_id, &none);
-  pmq_ = nullptr;
-  *max_freq = q.max_freq;
-  *ab_freq = q.ab_freq;
 }
 
 // Folds completed sampled k_merge launches into times_ (block: wait for all of them).
@@ -3433,27 +1350,7 @@ void Device::merge_chain(const int32_t* ab, int n, int32_t X0) {
     words_stale_ = true;  // the tile path changes the tiles behind the loop's words
   }
   if (n == 1 && run_count_ == 0 && ntiles_ && resident_eligible() && X0 < (1 << 20)) {  // k_resident (ids: 20 bits)
-    if (res_posted_.size() >= (size_t)kResSlots) fatal("merge_chain: every resident slot has a merge in flight");
-    const int slot = res_running_ && __atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpAbort ? -1
-                                                                                                    : pick_resident_slot();
-    if (slot < 0) {  // the launch aborted (not co-resident): this merge and those in flight go elsewhere
-      resident_abort_fallback();
-      merge_chain(ab, n, X0);
-      return;
-    }
-    bool grow = false;
-    for (const MergeSlot& s2 : slot_) grow |= !s2.dsum || (uint32_t)X0 + 2 > s2.cap;
-    if (grow) {  // the delta tables grow: only between launches
-      if (!res_posted_.empty()) fatal("merge_chain: delta tables too small with a resident merge in flight");
-      park();
-      for (MergeSlot& s2 : slot_) ensure_slots(s2, (uint32_t)X0 + 2);
-      uint32_t cap = 0;
-      for (const MergeSlot& s2 : slot_) cap = std::max(cap, s2.cap);
-      for (MergeSlot& s2 : slot_) ensure_slots(s2, cap);
-    }
-    max_id_seen_ = std::max(max_id_seen_, X0);
-    const uint32_t seq = post_resident(kOpMerge, ab[0], ab[1], X0, slot);
-    res_posted_.push_back({X0, ab[0], ab[1], seq, slot, (uint32_t)res_post_parts_[slot].size(), now_seconds()});
+    post_resident_merge(ab, X0);
     return;
   }
   park();
@@ -3792,15 +1689,7 @@ void Device::rollback(int32_t X) {
     return;
   }
   if (!res_posted_.empty()) {  // resident: each wrong guess is expanded back where it matched
-    while (!res_posted_.empty() && res_posted_.back().X >= X) {
-      const ResPost rp = res_posted_.back();
-      res_posted_.pop_back();
-      // no wait: every workgroup takes its commands in order, so the undo follows the guess; the
-      // slot stays out of use until the guess's completion is seen (pick_resident_slot)
-      post_resident(kOpUnmerge, rp.a, rp.b, rp.X, rp.slot);
-      res_abandoned_[rp.slot] = rp.X;
-      ++rollbacks_;
-    }
+    undo_resident_from(X);
     return;
   }
   park();
@@ -3884,29 +1773,6 @@ void Device::unmerge_launch(ChainRun& run_, const uint32_t* tiles, size_t n_tile
   HIP_OK(hipGetLastError());
 }
 
-void Device::token_freq(size_t T, std::vector<uint64_t>* freq) {
-  HIP_OK(hipSetDevice(ordinal_));
-  park();
-  freq->assign(T, 0);
-  if (!ntiles_ || !T) {
-    if (xchg_.world > 1) dist_allreduce_host(freq->data(), T, false);
-    return;
-  }
-  size_t acc = 0;
-  u64* d = dalloc<u64>(T, &acc);
-  HIP_OK(hipMemsetAsync(d, 0, T * sizeof(u64), S(stream_)));
-  const int grid = (int)std::min<size_t>(ntiles_, (size_t)cu_count_ * 4);
-  if (layout_ == Layout::kStream)
-    k_token_freq<false><<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, weight_, (uint32_t)T, d);
-  else
-    k_token_freq<true><<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, weight_, (uint32_t)T, d);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(freq->data(), d, T * sizeof(u64), hipMemcpyDeviceToHost, S(stream_)));
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  HIP_OK(hipFree(d));
-  if (xchg_.world > 1) dist_allreduce_host(freq->data(), T, false);
-}
-
 void Device::download_tokens(std::vector<int32_t>* out) {
   HIP_OK(hipSetDevice(ordinal_));
   park();
@@ -3920,188 +1786,6 @@ void Device::download_tokens(std::vector<int32_t>* out) {
   HIP_OK(hipMemcpyAsync(lens.data(), tile_len_, ntiles_ * sizeof(uint32_t), hipMemcpyDeviceToHost, S(stream_)));
   HIP_OK(hipStreamSynchronize(S(stream_)));
   for (size_t t = 0; t < ntiles_; ++t) out->insert(out->end(), all.begin() + off[t], all.begin() + off[t] + lens[t]);
-}
-
-// ==========================================================================================
-// k_resident host side: plan (which workgroup holds which tiles in LDS), launch, post, collect,
-// roll back, park.  See the kernel's comment for the protocol.
-void Device::free_resident() {
-  drain_retired();
-  for (void* p : {(void*)res_wg_tiles_, (void*)res_wg_rank_, (void*)res_tile_lofs_, (void*)res_cmd_, (void*)res_q_,
-                  (void*)res_dbg_, (void*)res_stamps_, (void*)res_arrive_})
-    if (p) HIP_OK(hipFree(p));
-  res_wg_tiles_ = res_wg_rank_ = res_tile_lofs_ = res_cmd_ = res_arrive_ = nullptr;
-  res_q_ = nullptr;
-  res_dbg_ = nullptr;
-  res_stamps_ = nullptr;
-  resident_ok_ = false;
-}
-
-void Device::plan_resident(const TiledStream& ts) {
-  free_resident();
-  if (layout_ != Layout::kTypes || ntiles_ == 0) return;
-  const uint32_t G = (uint32_t)std::min(cu_count_, kMaxMergeGroups);
-  if (G < kResFirstWorker + 1) return;
-  const uint32_t W = G - kResFirstWorker;  // workers 2 .. G-1 (0 dispatches, 1 gathers)
-  int max_lds = 0;
-  HIP_OK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ordinal_));
-  hipFuncAttributes fa, fh;
-  HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_resident<true, true>)));
-  HIP_OK(hipFuncGetAttributes(&fh, reinterpret_cast<const void*>(&k_resident<true, false>)));
-  // dynamic LDS per workgroup: tokens in LDS (256 threads) / tokens in HBM (kResThreadsHbm threads,
-  // more staging); the dynamic region follows the statics unpadded: its 16-B accesses need a 16-B base
-  const long budget = (long)max_lds - (long)fa.sharedSizeBytes - 64;
-  const long budget_hbm = (long)max_lds - (long)fh.sharedSizeBytes - 64;
-  if (budget <= 0 || fa.sharedSizeBytes % 16 != 0 || fh.sharedSizeBytes % 16 != 0) return;
-  // per tile: first and last word rank (tiles hold whole words in rank order), LDS words
-  const size_t T = ntiles_;
-  std::vector<uint32_t> rfirst(T), rlast(T), words(T);
-  for (size_t t = 0; t < T; ++t) {
-    const uint32_t len = ts.len[t];
-    if (len > (uint32_t)kWaveTok || len == 0) return;  // a long word: k_merge handles those
-    const int32_t* tk = ts.tok.data() + ts.off[t];
-    if (tk[0] >= kHeaderLimit) return;
-    rfirst[t] = (uint32_t)(tk[0] - kHeaderBase);
-    uint32_t last = rfirst[t];
-    for (uint32_t i = 1; i < len; ++i)
-      if (tk[i] < kHeaderLimit) last = (uint32_t)(tk[i] - kHeaderBase);
-    rlast[t] = last;
-    if (t && rfirst[t] != rlast[t - 1] + 1) return;
-    words[t] = (len + 3u) & ~3u;
-  }
-  // The LDS plan, largest first: tokens + weights + 4096-bit signatures in LDS; tokens in HBM;
-  // then (big tables: C5 at 100 GB has 68,905 tiles of 4.1 M words) the weights in HBM too, and
-  // the signatures halved, then quartered (a looser filter: more tiles scanned per merge).
-  // SHREDWORD_RESIDENT_SIG_WORDS / SHREDWORD_RESIDENT_W_GLOBAL force a smaller plan (tests).
-  uint32_t sig_min = (uint32_t)kResSigWords / 4;
-  uint32_t sig_cap = (uint32_t)kResSigWords;
-  if (const char* e = std::getenv("SHREDWORD_RESIDENT_SIG_WORDS")) {
-    const uint32_t v = (uint32_t)std::atoi(e);
-    if (v == 32 || v == 64 || v == 128) sig_cap = sig_min = v;
-  }
-  const bool force_wg = std::getenv("SHREDWORD_RESIDENT_W_GLOBAL") != nullptr;
-  const bool force_hbm = std::getenv("SHREDWORD_RESIDENT_HBM") != nullptr || force_wg || sig_cap < (uint32_t)kResSigWords;
-  std::vector<uint32_t> wg_tiles, wg_rank, lofs;
-  uint32_t tok_words = 0, nr_max = 0, sw = 0;
-  size_t shm = 0;
-  bool lds_tok = false, w_global = false, fit = false;
-  for (int plan = 0; plan < 8 && !fit; ++plan) {
-    // plan 0: tokens in LDS; 1: tokens in HBM; 2..: weights in HBM, signatures sig_cap >> (plan - 2)
-    lds_tok = plan == 0;
-    w_global = plan >= 2;
-    sw = plan >= 2 ? sig_cap >> (plan - 2) : sig_cap;
-    if (sw < sig_min) break;
-    if ((lds_tok && force_hbm) || (!w_global && force_wg) || (!w_global && sw != sig_cap)) continue;
-    const long bud = lds_tok ? budget : budget_hbm;
-    // contiguous ranges balanced by LDS bytes: tile t goes to worker 2 + floor((prefix + cost/2) * W / total)
-    auto cost = [&](size_t t) {  // tokens (LDS bytes, or the scan work when they stay in HBM) + weights + signature
-      return 4.0 * words[t] + (w_global ? 0.0 : 8.0 * (rlast[t] - rfirst[t] + 1)) + 4.0 * sw;
-    };
-    double total = 0;
-    for (size_t t = 0; t < T; ++t) total += cost(t);
-    wg_tiles.assign(G + 1, 0);
-    wg_rank.assign(G + 1, 0);
-    lofs.assign(T, 0);
-    res_owner_.assign(T, 0);
-    double pre = 0;
-    uint32_t w = kResFirstWorker;
-    for (size_t t = 0; t < T; ++t) {
-      const double c = cost(t);
-      uint32_t want = kResFirstWorker + (uint32_t)std::min<double>(W - 1, std::floor((pre + c / 2) * W / total));
-      if (want < w) want = w;
-      while (w < want) wg_tiles[++w] = (uint32_t)t;
-      res_owner_[t] = w;
-      pre += c;
-    }
-    while (w < G) wg_tiles[++w] = (uint32_t)T;
-    tok_words = 0;
-    nr_max = 0;
-    uint32_t nt_max = 0;
-    res_wg_ntiles_.assign(G, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-      const uint32_t a = wg_tiles[g], b = wg_tiles[g + 1];
-      res_wg_ntiles_[g] = b - a;
-      nt_max = std::max(nt_max, b - a);
-      uint32_t o = 0;
-      for (uint32_t t = a; t < b; ++t) {
-        lofs[t] = o;
-        o += words[t];
-      }
-      tok_words = std::max(tok_words, o);
-      wg_rank[g] = a < b ? rfirst[a] : (a < T ? rfirst[a] : rlast[T - 1] + 1);
-      const uint32_t r_end = a < b ? rlast[b - 1] + 1 : wg_rank[g];
-      nr_max = std::max(nr_max, r_end - wg_rank[g]);
-    }
-    wg_rank[G] = rlast[T - 1] + 1;
-    if (nt_max > kResMaxTiles) continue;
-    tok_words += (uint32_t)kWaveTok;  // every lane reads its 16 tokens of a full chunk from any tile start
-    nr_max = w_global ? 0u : (nr_max + 1u) & ~1u;
-    if (!lds_tok) tok_words = 0;
-    shm = (size_t)tok_words * 4 + (size_t)nr_max * 8 + (size_t)nt_max * sw * 4;
-    shm = std::max(shm, 4 * ((T + 31) / 32));  // the gatherer's matched-tile bitmap
-    shm = (shm + 15) & ~(size_t)15;
-    fit = (long)shm <= bud;
-  }
-  if (!fit) return;
-  res_lds_tok_ = lds_tok;
-  res_sig_words_ = sw;
-  res_w_global_ = w_global;
-  res_grid_ = G;
-  res_tok_words_ = tok_words;
-  res_w_words_ = nr_max;
-  res_shm_ = shm;
-  res_all_.clear();
-  for (uint32_t g = kResFirstWorker; g < G; ++g) res_all_.push_back(g);
-  res_wg_first_ = wg_tiles;
-  res_wg_tiles_ = dalloc<uint32_t>(G + 1, &bytes_alloc_);
-  res_wg_rank_ = dalloc<uint32_t>(G + 1, &bytes_alloc_);
-  res_tile_lofs_ = dalloc<uint32_t>(T, &bytes_alloc_);
-  res_cmd_ = dalloc<uint32_t>(kResRing * 8, &bytes_alloc_);
-  res_q_ = dalloc<uint64_t>((size_t)G * kResRing * 2, &bytes_alloc_);
-  res_arrive_ = dalloc<uint32_t>(16, &bytes_alloc_);
-  HIP_OK(hipMemcpy(res_wg_tiles_, wg_tiles.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(res_wg_rank_, wg_rank.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(res_tile_lofs_, lofs.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemset(res_cmd_, 0, kResRing * 8 * sizeof(uint32_t)));
-  if (std::getenv("SHREDWORD_RESIDENT_DEBUG")) {
-    res_dbg_ = dalloc<uint32_t>((size_t)G * 4, &bytes_alloc_);
-    HIP_OK(hipMemset(res_dbg_, 0, (size_t)G * 16));
-  }
-  if (const char* e = std::getenv("SHREDWORD_RESIDENT_STAMPS")) {
-    res_stamps_ = dalloc<uint64_t>((size_t)G * 8, &bytes_alloc_);
-    HIP_OK(hipMemset(res_stamps_, 0, (size_t)G * 64));
-    res_stamp_detail_ = std::atoi(e) >= 2;
-  }
-  if (!res_mbox_) {
-    const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
-    HIP_OK(hipHostMalloc(&res_mbox_, sizeof(ResMbox), pin));
-    std::memset(res_mbox_, 0, sizeof(ResMbox));
-    HIP_OK(hipHostGetDevicePointer(&res_mbox_dev_, res_mbox_, 0));
-    HIP_OK(hipHostMalloc((void**)&res_status_, 64, pin));
-    std::memset(res_status_, 0, 64);
-    HIP_OK(hipHostGetDevicePointer(&res_status_dev_, res_status_, 0));
-    for (auto& e : res_ev_) {
-      hipEvent_t ev;
-      HIP_OK(hipEventCreate(&ev));
-      e = ev;
-    }
-  }
-  const void* kfn = res_lds_tok_ ? reinterpret_cast<const void*>(&k_resident<true, true>)
-                                 : reinterpret_cast<const void*>(&k_resident<true, false>);
-  HIP_OK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  int per_cu = 0;  // the persistent grid must be co-resident: at least one workgroup per CU
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, res_lds_tok_ ? 256 : kResThreadsHbm, shm));
-  if (per_cu < 1 || (long)per_cu * cu_count_ < (long)G) return;
-  resident_ok_ = true;
-  if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
-    std::fprintf(stderr, "[RESIDENT] plan: grid %u, %zu B of LDS per workgroup, %d per CU; tokens in %s, weights in %s, "
-                 "%u-bit tile signatures\n", G, (size_t)shm, per_cu, res_lds_tok_ ? "LDS" : "HBM",
-                 res_w_global_ ? "HBM" : "LDS", 32u * res_sig_words_);
-}
-
-void Device::set_resident(bool on) {
-  park();
-  resident_on_ = on;
 }
 
 // Both slots' delta tables cover ids up to max_id before a launch needs them (a launch holds
@@ -4121,282 +1805,6 @@ void Device::reserve_ids(int32_t max_id) {
   uint32_t cap = 0;
   for (const MergeSlot& s : slot_) cap = std::max(cap, s.cap);
   for (MergeSlot& s : slot_) ensure_slots(s, cap);
-}
-
-void Device::start_resident() {
-  ResParams rp;
-  rp.tok = tok_;
-  rp.tile_off = tile_off_;
-  rp.tile_len = tile_len_;
-  rp.weight = weight_;
-  rp.wg_tiles = res_wg_tiles_;
-  rp.wg_rank = res_wg_rank_;
-  rp.tile_lofs = res_tile_lofs_;
-  rp.tok_words = res_tok_words_;
-  rp.w_words = res_w_words_;
-  rp.sig_words = res_sig_words_;
-  rp.w_global = res_w_global_ ? 1u : 0u;
-  rp.mbox = (const ResMbox*)res_mbox_dev_;
-  rp.cmd = res_cmd_;
-  rp.q = reinterpret_cast<u64*>(res_q_);
-  rp.status = (uint32_t*)res_status_dev_;
-  rp.arrive = res_arrive_;
-  rp.arrive_polls = res_arrive_polls_;
-  rp.seq0 = seq_ + 1;
-  rp.leader_polls = 1u << 23;  // ~10 s without a command: the launch ends itself (the host relaunches)
-  rp.keys_per_merge = keys_per_merge_;
-  rp.slot_cap = min_slot_cap();
-  rp.region_keys = res_region_keys_;
-  rp.mt_dense = (uint32_t)(ntiles_ / 2);
-  rp.mt_words = (uint32_t)((ntiles_ + 31) / 32);
-  for (int k = 0; k < kResSlots; ++k) {
-    MergeSlot& sl = slot_[k];
-    ResSlot& r = rp.sl[k];
-    r.dsum = U(sl.dsum);
-    r.dft = U(sl.dft);
-    r.dlist = sl.dlist;
-    r.dcount = sl.dcount;
-    r.done = sl.dcount + 1;
-    r.out = (DeltaRecord*)sl.dev_recs;
-    r.hcount = (uint32_t*)sl.dev_count;
-    r.hstats = (u64*)((char*)sl.dev_count + 16);
-    r.hmlist = (uint32_t*)sl.dev_mlist;
-    r.rhdr = sl.rhdr;
-    r.rrec = U(sl.rrec);
-    r.rtile = sl.rtile;
-    // region headers carry the merge id k_resident polls for: none may hold a stale one
-    if (sl.rhdr) HIP_OK(hipMemsetAsync(sl.rhdr, 0, (size_t)kMaxMergeGroups * kRegHdr * sizeof(uint32_t), S(stream_)));
-  }
-  for (int32_t& x : res_abandoned_) x = -1;
-  rp.dbg = res_dbg_;
-  rp.stamps = U(res_stamps_);
-  res_status_[0] = 0;
-  res_status_[2] = 0;
-  HIP_OK(hipMemsetAsync(res_q_, 0, (size_t)res_grid_ * kResRing * 2 * sizeof(uint64_t), S(stream_)));
-  HIP_OK(hipMemsetAsync(res_arrive_, 0, sizeof(uint32_t), S(stream_)));
-  HIP_OK(hipEventRecord((hipEvent_t)res_ev_[0], S(stream_)));
-  // a plain launch: one workgroup per CU by its LDS footprint, checked against the occupancy
-  // query at plan time (plan_resident), so every workgroup is resident together
-  if (res_lds_tok_) k_resident<true, true><<<res_grid_, 256, res_shm_, S(stream_)>>>(rp);
-  else k_resident<true, false><<<res_grid_, kResThreadsHbm, res_shm_, S(stream_)>>>(rp);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord((hipEvent_t)res_ev_[1], S(stream_)));
-  res_running_ = true;
-  res_merges_ = 0;
-  ++res_launches_;
-}
-
-// Posts one command to the resident launch (relaunching it first if it ended on its time-out).
-// Merge and unmerge commands name their participants; a merge's are kept by slot for its undo.
-uint32_t Device::post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int slot) {
-  if (res_running_ && __atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpTimeout) {
-    if (!res_posted_.empty()) fatal("k_resident ended on its time-out with merges in flight");
-    HIP_OK(hipStreamSynchronize(S(stream_)));
-    res_running_ = false;
-  }
-  if (!res_running_ && op != kOpStop) start_resident();
-  uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t np = res_grid_;
-  if (op == kOpMerge) {
-    std::vector<uint32_t>& pp = res_post_parts_[slot];
-    if (skip_) index_.owners(a, b, res_wg_first_, &pp);
-    if (!skip_ || pp.empty()) pp = res_all_;
-    for (uint32_t o : pp) visited_tiles_ += res_wg_ntiles_[o];
-    slot_[slot].host_count[1] = 0xFFFFFFFFu;  // the merge raises X here
-  }
-  if (op == kOpMerge || op == kOpUnmerge) {
-    const std::vector<uint32_t>& pp = res_post_parts_[slot];
-    for (uint32_t o : pp) mask[o >> 5] |= 1u << (o & 31);
-    np = (uint32_t)pp.size();
-    if (op == kOpMerge) {  // the gatherer completes every merge
-      mask[0] |= 1u << kResGatherWg;
-      ++np;
-    }
-  }
-  const uint32_t seq = ++seq_;
-  uint64_t* g = static_cast<ResMbox*>(res_mbox_)->cmd[seq % kResRing].g;
-  auto put = [&](int k, uint32_t v) { __atomic_store_n(&g[k], (uint64_t)seq | ((uint64_t)v << 32), __ATOMIC_RELAXED); };
-  put(kCmdOp, op);
-  put(kCmdA, (uint32_t)a);
-  put(kCmdB, (uint32_t)b);
-  put(kCmdX, (uint32_t)X);
-  put(kCmdSlotN, (uint32_t)slot | (np << 8));
-  for (int k = 0; k < 8; ++k) put(kCmdMask + k, mask[k]);
-  std::atomic_thread_fence(std::memory_order_release);
-  return seq;
-}
-
-// A slot for the next resident merge: none with a posted merge, and none whose undone guess has
-// not completed yet (its completion still writes the slot and raises the slot's flag with the
-// same merge id the next merge may carry).
-int Device::pick_resident_slot() {
-  for (;;) {
-    int wait_slot = -1;
-    for (int k = 0; k < kResSlots; ++k) {
-      const int s = (res_next_slot_ + k) % kResSlots;
-      bool used = false;
-      for (const ResPost& rp : res_posted_) used |= rp.slot == s;
-      if (used) continue;
-      if (res_abandoned_[s] >= 0) {
-        if (__atomic_load_n(slot_[s].host_count + 1, __ATOMIC_ACQUIRE) != (uint32_t)res_abandoned_[s]) {
-          if (wait_slot < 0) wait_slot = s;
-          continue;
-        }
-        res_abandoned_[s] = -1;
-      }
-      res_next_slot_ = (s + 1) % kResSlots;
-      return s;
-    }
-    if (wait_slot < 0) fatal("k_resident: no free merge slot");
-    if (!wait_resident(slot_[wait_slot], res_abandoned_[wait_slot])) return -1;  // the launch aborted
-  }
-}
-
-bool Device::wait_resident(const MergeSlot& sl, int32_t X) {
-  volatile uint32_t* flag = sl.host_count + 1;
-  const double t0 = now_seconds();
-  unsigned spins = 0;
-  while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != (uint32_t)X) {
-    __builtin_ia32_pause();
-    if (++spins % 4096 != 0) continue;
-    if (__atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpAbort) return false;
-    if (__atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpTimeout)
-      fatal("k_resident ended on its time-out before a posted merge completed");
-    if (res_dbg_ && now_seconds() - t0 > 3.0) resident_dump("no flag after 3 s");
-    if (now_seconds() - t0 > 120.0) {
-      const hipError_t e = hipStreamQuery(S(stream_));
-      if (e != hipSuccess && e != hipErrorNotReady) HIP_OK(e);
-      if (now_seconds() - t0 > 600.0) fatal("k_resident did not signal completion within 600 s");
-    }
-  }
-  return true;
-}
-
-size_t Device::collect_resident(int32_t X, const DeltaRecord** recs) {
-  if (res_posted_.empty() || res_posted_.front().X != X) fatal("collect: merge X is not the oldest posted merge");
-  const double tw = now_seconds();
-  if (!wait_resident(slot_[res_posted_.front().slot], X)) {  // not co-resident: nothing ran
-    resident_abort_fallback();
-    return collect(X, recs);
-  }
-  const ResPost rp = res_posted_.front();
-  res_posted_.erase(res_posted_.begin());
-  MergeSlot& sl = slot_[rp.slot];
-  {  // host clock: post -> flag seen, and the part of it spent waiting here
-    const double t1 = now_seconds();
-    res_post_flag_us_ += 1e6 * (t1 - rp.t_post);
-    res_post_flag_last_ = 1e6 * (t1 - rp.t_post);
-    res_host_wait_ += 1e6 * (t1 - tw);
-    res_parts_sum_ += rp.nparts;
-  }
-  const u64* hs = (const u64*)(sl.host_count + 4);
-  const size_t n = sl.host_count[0];
-  const uint32_t nm = sl.host_count[2];
-  if (nm == kAllTiles) index_.set_all(X);
-  else index_.set_tiles_bits(X, sl.host_mlist, nm);  // the gatherer's bitmap (k_resident)
-  res_lat_us_ += 1e-2 * (double)hs[2];  // s_memrealtime: 100 MHz
-  res_lat_n_ += 1;
-  if (res_stamps_ && merge_log_)  // diagnostic: host post / flag-seen clock beside the device's dispatch / flag
-    std::fprintf(merge_log_, "S %d %u %.2f %.2f %.2f %llu %llu %zu %u\n", X, rp.nparts, 1e6 * rp.t_post, 1e6 * tw,
-                 1e6 * (rp.t_post + 1e-6 * res_post_flag_last_), (unsigned long long)hs[8],
-                 (unsigned long long)(hs[8] + hs[2]), (size_t)sl.host_count[0], nm);
-  if (res_stamps_) {
-    for (int k = 0; k < 4; ++k) res_ph_[k] += 1e-2 * (double)hs[3 + k];
-    res_phase_[4] += (double)hs[7];
-    res_phase_[3] += 1e-2 * (double)hs[2];
-    res_phase_n_ += 1;
-  }
-  if (timing_) {
-    times_.merge_bytes += 4.0 * (double)live_tokens_est_;
-    times_.res_bytes += 4.0 * (double)live_tokens_est_;
-    times_.res_k3_bytes += 8.0 * (double)hs[1];  // hs[1]: tokens the merge's matched tiles hold after it
-    times_.res_merges += 1;
-  }
-  ++res_merges_;
-  if (hybrid_ && !idx_phase_ && index_on_ && wl_ && wl_->ready()) {
-    // entries merged per merge is far from monotone (a frequent pair of a few common words sits
-    // between pairs spread over many words): switch once a whole window of merges stayed small
-    sw_win_[sw_n_++ % kSwitchWindow] = hs[0];
-    uint64_t mx = 0;
-    for (uint64_t v : sw_win_) mx = std::max(mx, v);
-    if (sw_n_ >= kSwitchWindow && mx < switch_occ_) switch_pending_ = true;
-  }
-  live_tokens_est_ -= hs[0];
-  records_total_ += n;
-  records_max_ = std::max<uint64_t>(records_max_, n);
-  *recs = sl.host_recs;
-  return n;
-}
-
-// Diagnostic (SHREDWORD_RESIDENT_DEBUG=1): the state of a stuck resident launch, then exit.
-void Device::resident_dump(const char* why) {
-  const uint32_t G = res_grid_;
-  hipStream_t s;
-  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  std::vector<uint32_t> dbg(4 * G), cmd(kResRing * 8);
-  std::vector<uint64_t> q((size_t)G * kResRing * 2);
-  HIP_OK(hipMemcpyAsync(dbg.data(), res_dbg_, dbg.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(cmd.data(), res_cmd_, cmd.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(q.data(), res_q_, q.size() * 8, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  std::fprintf(stderr, "[RESIDENT] %s: seq_=%u status=%u posted=%zu flags=%u/%u\n", why, seq_, res_status_[0],
-               res_posted_.size(), slot_[0].host_count[1], slot_[1].host_count[1]);
-  for (int k = 2; k < kResSlots; ++k) std::fprintf(stderr, "[RESIDENT] flag[%d]=%u\n", k, slot_[k].host_count[1]);
-  for (const ResPost& rp : res_posted_)
-    std::fprintf(stderr, "[RESIDENT]   posted X=%d seq=%u slot=%d np=%u\n", rp.X, rp.seq, rp.slot, rp.nparts);
-  for (uint32_t g = 0; g < G; ++g) {
-    std::fprintf(stderr, "[RESIDENT] wg %u: phase %u seq %u pi %u T %u | q", g, dbg[4 * g], dbg[4 * g + 1], dbg[4 * g + 2],
-                 dbg[4 * g + 3]);
-    for (uint32_t k = 0; k < kResRing; ++k) {
-      const uint64_t v = q[((size_t)g * kResRing + k) * 2];
-      std::fprintf(stderr, " %u:%u", (uint32_t)(v & 0xFFFF), (uint32_t)(v >> 24) & 7u);
-    }
-    std::fprintf(stderr, "\n");
-  }
-  std::fflush(stderr);
-  std::_Exit(3);
-}
-
-void Device::park() {
-  index_sync();
-  if (!res_running_) return;
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!res_posted_.empty()) fatal("park: a resident merge was not collected");
-  post_resident(kOpStop, 0, 0, 0, 0);
-  HIP_OK(hipStreamSynchronize(S(stream_)));
-  res_running_ = false;
-  for (int32_t& x : res_abandoned_) x = -1;  // every command ran
-  for (MergeSlot& s2 : slot_)  // flags carried merge ids: the launch path compares launch numbers
-    if (s2.host_count) s2.host_count[1] = 0xFFFFFFFFu;
-  res_status_[0] = 0;
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)res_ev_[0], (hipEvent_t)res_ev_[1]));
-  res_ms_ += ms;
-  if (timing_ && res_merges_) {  // one launch: its wall time is the merge loop's device time
-    times_.merge_ms += ms;
-    times_.merge_launches += res_merges_;
-    times_.res_ms += ms;
-  }
-  if (res_merges_ && std::getenv("SHREDWORD_RESIDENT_REPORT")) {
-    const double n = (double)res_merges_;
-    std::fprintf(stderr, "[RESIDENT] %llu merges in %.2f ms | host: post->flag %.2f us, waited %.2f us | participants %.1f",
-                 (unsigned long long)res_merges_, ms, res_post_flag_us_ / n, res_host_wait_ / n, res_parts_sum_ / n);
-    if (res_phase_n_)
-      std::fprintf(stderr,
-                   " | device after dispatch: all published %.2f prefix %.2f loaded %.2f combined %.2f flag %.2f",
-                   res_ph_[0] / res_phase_n_, res_ph_[1] / res_phase_n_,
-                   res_ph_[2] / res_phase_n_, res_ph_[3] / res_phase_n_, res_phase_[3] / res_phase_n_);
-    if (res_phase_n_) std::fprintf(stderr, " | records before combine %.1f", res_phase_[4] / res_phase_n_);
-    std::fprintf(stderr, "\n");
-  }
-  res_post_flag_us_ = res_host_wait_ = res_parts_sum_ = 0;
-  res_phase_[0] = res_phase_[1] = res_phase_[2] = res_phase_[3] = res_phase_[4] = 0;
-  for (double& x : res_ph_) x = 0;
-  res_phase_n_ = 0;
-  // the tiles are back in HBM: their pair signatures for k_merge / k_unmerge
-  const int grid = (int)std::min<size_t>((ntiles_ + kWaves - 1) / kWaves, (size_t)cu_count_ * 8);
-  k_sig_build<<<grid, kThreads, 0, S(stream_)>>>(tok_, tile_off_, tile_len_, (uint32_t)ntiles_, sig_);
-  HIP_OK(hipGetLastError());
 }
 
 }  // namespace shred

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../host/encoder.h"
+#include "encode_common.h"
 
 namespace shred {
 namespace {
@@ -537,15 +538,6 @@ __global__ __launch_bounds__(kThreads) void k_encode_emit(const int32_t* __restr
   }
 }
 
-#define ENC_OK(expr)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      std::fprintf(stderr, "[ERROR]\t encoder: %s: %s\n", #expr, hipGetErrorString(e_));        \
-      return -1;                                                                                \
-    }                                                                                           \
-  } while (0)
-
 }  // namespace
 
 EncodeDevice* EncodeDevice::create(int device, const std::vector<uint64_t>& table, const int32_t* byte_map,
@@ -640,19 +632,6 @@ bool EncodeDevice::reserve(size_t n, std::string* why) {
   cap_bytes_ = cap;
   return true;
 }
-
-namespace {
-// Restores the caller's current device when an encoder call returns.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
 
 int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms) {
   if (kernel_ms) *kernel_ms = 0;

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../host/encoder.h"
+#include "encode_common.h"
 
 namespace shred {
 namespace {
@@ -204,25 +205,6 @@ __global__ void k_span_ends(int64_t* __restrict__ line, u64 L, u64 T) {
     line[0] = 0;  // (L == 0 only for an empty text, where T == 0)
   }
 }
-
-#define ENC_OK(expr)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      std::fprintf(stderr, "[ERROR]\t encoder: %s: %s\n", #expr, hipGetErrorString(e_));        \
-      return -1;                                                                                \
-    }                                                                                           \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 typedef hipcub::TransformInputIterator<u64, IdLength, const int32_t*> LengthIter;
 

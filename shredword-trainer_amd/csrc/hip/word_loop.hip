@@ -30,23 +30,11 @@
 
 #include "../host/common.h"
 #include "../host/word_loop.h"
+#include "hip_common.h"
 
 namespace shred {
 
-#define WL_OK(expr)                                                                         \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      std::fprintf(stderr, "[ERROR]\t HIP %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), \
-                   __FILE__, __LINE__);                                                     \
-      std::fflush(stderr);                                                                  \
-      std::abort();                                                                         \
-    }                                                                                       \
-  } while (0)
-
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kWlThreads = 512;
 constexpr int kDh = 2048;               // LDS delta hash slots
@@ -110,8 +98,6 @@ __device__ __forceinline__ void wl_stamp(uint32_t* xs, int i, unsigned long long
 constexpr uint32_t kDeltaBucketsDev = 1024;  // the reference's FREQ_CHANGE_BUCKETS (bpe.cpp:16)
 constexpr uint32_t kRing = 64;          // command ring entries
 constexpr uint32_t kOpMerge = 1, kOpStop = 2, kOpTimeout = 3, kOpUnmerge = 4;
-constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
-constexpr u64 kEmpty64 = ~0ull;
 constexpr uint32_t kNoList = 0xFFFFFFFFu;
 // dstate words: [1] pool top, [3] error
 constexpr int kStPoolTop = 1, kStError = 3;
@@ -249,14 +235,6 @@ struct WlParams {
   SelParams sel;  // k_word_loop<true> only
 };
 
-__device__ __forceinline__ u64 mix64(u64 k) {
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
 __device__ __forceinline__ u64 pair_key(int32_t a, int32_t b) { return ((u64)(uint32_t)a << 32) | (uint32_t)b; }
 __device__ __forceinline__ uint32_t sel_idx_home(u64 k) { return (uint32_t)(mix64(k) >> 40) & (kSelIdx - 1); }
 // position of key in the frontier, or -1 (also for a dead entry never compacted: those are found
@@ -288,9 +266,6 @@ __device__ __forceinline__ bool sel_idx_insert(SelLds<true>& F, u64 k, uint32_t 
   return false;
 }
 
-__device__ __forceinline__ uint32_t slot_of(int32_t id, uint32_t cap) {
-  return (uint32_t)id < cap ? (uint32_t)id + 1u : 0u;
-}
 // filter bit of neighbour id on side s (0: left of M, 1: right of M)
 __device__ __forceinline__ u64 nbit(int32_t id, uint32_t s) {
   const uint32_t v = (uint32_t)id * 2u + s;
@@ -399,29 +374,10 @@ struct MergeCtx {
 // keys in 29,000 indexed merges).
 constexpr int kProbesDefault = 32;
 
-// Sum of a u32 over the wave by DPP row shifts and row broadcasts (lane 63 holds it), read back
-// as a scalar.  Call it with every lane active (0 from lanes that add nothing).  A per-lane
+// Wave sums and prefix sums are hip_common.h's wave_sum / wave_scan_add (DPP row shifts and row
+// broadcasts).  Call them with every lane active (0 from lanes that add nothing).  A per-lane
 // atomicAdd on one LDS word instead compiles to a loop over the active lanes (the compiler's
 // iterative atomic combine: ~7 scalar instructions a lane), microseconds a merge at 64 lanes.
-// Inclusive prefix sum of a u32 over the wave (same DPP steps; every lane active).
-__device__ __forceinline__ uint32_t wave_scan32(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);
-  return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
 
 template <int kProbes>
 __device__ __forceinline__ u64 occurrence(const WlParams& p, DeltaH& h, const MergeCtx& c, bool has_l, int32_t prev,
@@ -616,26 +572,8 @@ __device__ __forceinline__ uint32_t unmerge_run(int32_t* t, uint32_t L, int32_t 
   return L + nx;
 }
 
-// Inclusive wave max of a u64 on DPP row shifts and row broadcasts (identity 0; lane 63 holds
-// the wave's max): a few cycles a step instead of an LDS round trip per __shfl.
-template <int kCtrl, int kRowMask = 0xf, bool kBound = true>
-__device__ __forceinline__ u64 wl_dpp64(u64 x) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, kCtrl, kRowMask, 0xf, kBound);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), kCtrl, kRowMask, 0xf, kBound);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 wl_max64(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 wave_max64(u64 x) {
-  x = wl_max64(x, wl_dpp64<0x111>(x));
-  x = wl_max64(x, wl_dpp64<0x112>(x));
-  x = wl_max64(x, wl_dpp64<0x114>(x));
-  x = wl_max64(x, wl_dpp64<0x118>(x));
-  x = wl_max64(x, wl_dpp64<0x142, 0xa, false>(x));
-  x = wl_max64(x, wl_dpp64<0x143, 0xc, false>(x));
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), 63);
-  return ((u64)hi << 32) | lo;
-}
+// The wave's max of a u64 (identity 0), as a scalar.
+__device__ __forceinline__ u64 wave_max64(u64 x) { return lane_read64(wave_scan_max64(x), 63); }
 
 __device__ __forceinline__ uint32_t wave_incl_add(uint32_t x) {
   const int lane = threadIdx.x & 63;
@@ -722,12 +660,6 @@ __device__ __forceinline__ void fin_gather(const WlParams& p, DeltaH& h, LoopS& 
   }
 }
 
-__device__ __forceinline__ u64 rl64(u64 x, uint32_t j) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)j);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)j);
-  return ((u64)hi << 32) | lo;
-}
-
 // finalize_changes for n <= 64 records, by one wave alone (no barrier, no LDS atomics): lane i
 // holds record i; the combine and the ranks are scalar loops over the records (readlane
 // broadcasts).  Same output as finalize_changes.  Returns the changes written.
@@ -743,7 +675,7 @@ __device__ uint32_t finalize_wave(const u64* q, const WlSlotDev& sd, int32_t a, 
   bool lead = mine && hk != kab;
 #pragma unroll 1
   for (uint32_t j = 0; j < n; ++j) {
-    const u64 hj = rl64(hk, j), fj = rl64(ft, j), dj = rl64(d, j);
+    const u64 hj = lane_read64(hk, (int)j), fj = lane_read64(ft, (int)j), dj = lane_read64(d, (int)j);
     const bool same = hj == hk;
     sum += same ? dj : 0ull;
     lead = lead && !(same && fj < ft);
@@ -756,7 +688,7 @@ __device__ uint32_t finalize_wave(const u64* q, const WlSlotDev& sd, int32_t a, 
   for (u64 rest = lm; rest; rest &= rest - 1) {
     const uint32_t j = (uint32_t)__builtin_ctzll(rest);
     const uint32_t bj = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)hk, (int)j) & (kDeltaBucketsDev - 1);
-    const u64 fj = rl64(ft, j);
+    const u64 fj = lane_read64(ft, (int)j);
     r += (bj < bk || (bj == bk && fj > ft)) ? 1u : 0u;
   }
   if (lead) {
@@ -1250,8 +1182,8 @@ __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
         }
       }
       if (const u64 sm = __ballot(pass)) {  // statistics: wave sums, one LDS add each per wave
-        const uint32_t w_occ = wave_sum32(occ), w_rd = wave_sum32(pass ? 1u + L : 0u);
-        const uint32_t w_wr = wave_sum32(occ ? 1u + nl : 0u);
+        const uint32_t w_occ = wave_sum(occ), w_rd = wave_sum(pass ? 1u + L : 0u);
+        const uint32_t w_wr = wave_sum(occ ? 1u + nl : 0u);
         if (lane == 0) {
           atomicAdd(&S.occ, (u64)w_occ);
           atomicAdd(&S.scan, (uint32_t)__popcll(sm));
@@ -1285,7 +1217,7 @@ __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
           uint32_t bw = s_kbits[lane];
           s_kbits[lane] = 0;
           const uint32_t nb = (uint32_t)__popc(bw);
-          const uint32_t incl = wave_scan32(nb);
+          const uint32_t incl = wave_scan_add(nb);
           const uint32_t nk = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
           uint32_t ri = incl - nb;
           WL_ST(if (lane == 0) S.xs[13] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_cmd);)
@@ -1361,13 +1293,13 @@ __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
             cks += lo * hand_weight(2u * lane) + hi * hand_weight(2u * lane + 1u);
           }
           {  // the wave's sum (DPP row shifts and broadcasts, lane 63), then the tagged granules
-            cks += wl_dpp64<0x111>(cks);
-            cks += wl_dpp64<0x112>(cks);
-            cks += wl_dpp64<0x114>(cks);
-            cks += wl_dpp64<0x118>(cks);
-            cks += wl_dpp64<0x142, 0xa, false>(cks);
-            cks += wl_dpp64<0x143, 0xc, false>(cks);
-            cks = rl64(cks, 63);
+            cks += dpp64<0x111>(cks);
+            cks += dpp64<0x112>(cks);
+            cks += dpp64<0x114>(cks);
+            cks += dpp64<0x118>(cks);
+            cks += dpp64<0x142, 0xa, false>(cks);
+            cks += dpp64<0x143, 0xc, false>(cks);
+            cks = lane_read64(cks, 63);
           }
           if (lane == 0) {
             const u64 t_r0 = __builtin_amdgcn_s_memrealtime();
@@ -1500,8 +1432,8 @@ __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     {  // statistics: wave sums, one LDS add each per wave
-      const uint32_t w_occ = wave_sum32(my_occ), w_scan = wave_sum32(my_scan);
-      const uint32_t w_rd = wave_sum32(my_rd), w_wr = wave_sum32(my_wr);
+      const uint32_t w_occ = wave_sum(my_occ), w_scan = wave_sum(my_scan);
+      const uint32_t w_rd = wave_sum(my_rd), w_wr = wave_sum(my_wr);
       if (lane == 0 && w_scan) {
         atomicAdd(&S.occ, (u64)w_occ);
         atomicAdd(&S.scan, w_scan);
@@ -2036,12 +1968,10 @@ __global__ void k_sel_export(const u64* tab, u64 cap, PairCount* out, uint32_t* 
 template <class T>
 T* wl_alloc(size_t n, size_t* acc) {
   void* p = nullptr;
-  WL_OK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+  HIP_OK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
   *acc += std::max<size_t>(n, 1) * sizeof(T);
   return static_cast<T*>(p);
 }
-
-inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 
 constexpr uint32_t kRunPad = 4 * kStripV + 4;  // ints past the last run (its 16-B loads may overrun)
 
@@ -2049,14 +1979,14 @@ constexpr uint32_t kRunPad = 4 * kStripV + 4;  // ints past the last run (its 16
 
 // ==========================================================================================
 WordLoop::WordLoop(int ordinal, void* stream, int32_t unk_id) : ordinal_(ordinal), stream_(stream), unk_(unk_id) {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
-  WL_OK(hipHostMalloc(&ring_, sizeof(WlCmd) * kRing, pin));
+  HIP_OK(hipHostMalloc(&ring_, sizeof(WlCmd) * kRing, pin));
   std::memset(ring_, 0, sizeof(WlCmd) * kRing);
-  WL_OK(hipHostGetDevicePointer(&ring_dev_, ring_, 0));
-  WL_OK(hipHostMalloc((void**)&status_, 64, pin));
+  HIP_OK(hipHostGetDevicePointer(&ring_dev_, ring_, 0));
+  HIP_OK(hipHostMalloc((void**)&status_, 64, pin));
   std::memset(status_, 0, 64);
-  WL_OK(hipHostGetDevicePointer(&status_dev_, status_, 0));
+  HIP_OK(hipHostGetDevicePointer(&status_dev_, status_, 0));
   // the idle bound (polls without a command before the launch ends itself); tests shrink it to
   // race the time-out against the posts
   if (const char* e = std::getenv("SHREDWORD_WL_IDLE_POLLS")) idle_polls_ = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -2069,7 +1999,7 @@ WordLoop::WordLoop(int ordinal, void* stream, int32_t unk_id) : ordinal_(ordinal
   if (const char* e = std::getenv("SHREDWORD_SELECT_REPORT")) sel_report_ = std::atoi(e) != 0;
   for (auto& e : ev_) {
     hipEvent_t ev;
-    WL_OK(hipEventCreate(&ev));
+    HIP_OK(hipEventCreate(&ev));
     e = ev;
   }
 }
@@ -2094,7 +2024,7 @@ void WordLoop::free_all() {
   void* ptrs[] = {wtok_, wtok0_, woff_, tile_first_, tile_nw_, pool_, dkey_, dval_, init_key_, init_val_,
                   lst_, lseq_, dsum_, dft_, dlist_, dstate_};
   for (void* p : ptrs)
-    if (p) WL_OK(hipFree(p));
+    if (p) HIP_OK(hipFree(p));
   wtok_ = wtok0_ = nullptr;
   woff_ = tile_first_ = tile_nw_ = lseq_ = dlist_ = dstate_ = nullptr;
   pool_ = dkey_ = dval_ = init_key_ = init_val_ = lst_ = dsum_ = dft_ = nullptr;
@@ -2105,7 +2035,7 @@ void WordLoop::free_all() {
 }
 
 bool WordLoop::upload(const TiledStream& ts, const uint64_t* d_weight) {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (running_) stop();
   free_all();
   // the words of the tile stream in rank order (types layout: one entry per distinct word), each
@@ -2211,13 +2141,13 @@ bool WordLoop::upload(const TiledStream& ts, const uint64_t* d_weight) {
   tile_first_ = wl_alloc<uint32_t>(ntiles_, &bytes_);
   tile_nw_ = wl_alloc<uint32_t>(ntiles_, &bytes_);
   hipStream_t s = S(stream_);
-  WL_OK(hipMemcpyAsync(wtok0_, wtok.data(), (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  WL_OK(hipMemcpyAsync(woff_, woff.data(), woff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(wtok0_, wtok.data(), (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(woff_, woff.data(), woff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   k_wl_set_weights<<<(int)std::min<uint32_t>((nwords_ + 255) / 256, 4096), 256, 0, s>>>(wtok0_, woff_, nwords_, weight_);
-  WL_OK(hipGetLastError());
-  WL_OK(hipMemcpyAsync(tile_first_, tfirst.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  WL_OK(hipMemcpyAsync(tile_nw_, tnw.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  WL_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(tile_first_, tfirst.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(tile_nw_, tnw.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   // pool: the initial index (<= one entry per adjacent pair), the words-of lists (a merge lists
   // the words it shortened: Σ over a run <= Σ (length - 1)) and the pair groups (<= 2 entries
   // per occurrence merged: Σ <= 2 Σ (length - 1)); undone guesses release theirs (each is the
@@ -2225,8 +2155,8 @@ bool WordLoop::upload(const TiledStream& ts, const uint64_t* d_weight) {
   pool_cap_ = 3 * ntok_ + 4096;
   pool_ = wl_alloc<u64>(2 * pool_cap_, &bytes_);  // WEnt: entry + signature
   dstate_ = wl_alloc<uint32_t>(8, &bytes_);
-  WL_OK(hipMemsetAsync(dstate_, 0, 8 * sizeof(uint32_t), s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemsetAsync(dstate_, 0, 8 * sizeof(uint32_t), s));
+  HIP_OK(hipStreamSynchronize(s));
   reserve(kBaseVocab + 1);
   build_index();
   ready_ = true;
@@ -2242,17 +2172,17 @@ void WordLoop::build_index() {
   uint32_t* pbase = wl_alloc<uint32_t>((size_t)nwords_ + 2, &acc);
   uint32_t* pcnt = wl_alloc<uint32_t>((size_t)nwords_ + 2, &acc);
   k_wl_pair_counts<<<(int)std::min<uint32_t>((nwords_ + 256) / 256, 4096), 256, 0, s>>>(wtok_, woff_, nwords_, pcnt);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   {
     size_t tb = 0;
-    WL_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pcnt, pbase, (int)nwords_ + 1, s));
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pcnt, pbase, (int)nwords_ + 1, s));
     void* t0 = wl_alloc<uint8_t>(tb, &acc);
-    WL_OK(hipcub::DeviceScan::ExclusiveSum(t0, tb, pcnt, pbase, (int)nwords_ + 1, s));
-    WL_OK(hipStreamSynchronize(s));
-    WL_OK(hipFree(t0));
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t0, tb, pcnt, pbase, (int)nwords_ + 1, s));
+    HIP_OK(hipStreamSynchronize(s));
+    HIP_OK(hipFree(t0));
   }
   uint32_t npairs = 0;
-  WL_OK(hipMemcpy(&npairs, pbase + nwords_, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(&npairs, pbase + nwords_, sizeof(uint32_t), hipMemcpyDeviceToHost));
   const uint64_t n = std::max<uint64_t>(npairs, 1);
   u64* kin = wl_alloc<u64>(n, &acc);
   u64* kout = wl_alloc<u64>(n, &acc);
@@ -2264,49 +2194,49 @@ void WordLoop::build_index() {
   uint32_t* kidx = wl_alloc<uint32_t>(n + 1, &acc);
   const int grid = 2048;
   if (npairs == 0) {
-    WL_OK(hipMemsetAsync(kin, 0xFF, sizeof(u64), s));
-    WL_OK(hipMemsetAsync(vin, 0, sizeof(uint32_t), s));
+    HIP_OK(hipMemsetAsync(kin, 0xFF, sizeof(u64), s));
+    HIP_OK(hipMemsetAsync(vin, 0, sizeof(uint32_t), s));
   }
   k_wl_emit_pairs<<<grid, 256, 0, s>>>(wtok_, woff_, pbase, nwords_, unk_, kin, vin);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   size_t tmp_bytes = 0, tb2 = 0;
-  WL_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
-  WL_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, keep, pos, (int)n + 1, s));
+  HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, keep, pos, (int)n + 1, s));
   tmp_bytes = std::max(tmp_bytes, tb2);
   void* tmp = wl_alloc<uint8_t>(tmp_bytes, &acc);
-  WL_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
-  WL_OK(hipMemsetAsync(keep + n, 0, sizeof(uint32_t), s));
-  WL_OK(hipMemsetAsync(head + n, 0, sizeof(uint32_t), s));
+  HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
+  HIP_OK(hipMemsetAsync(keep + n, 0, sizeof(uint32_t), s));
+  HIP_OK(hipMemsetAsync(head + n, 0, sizeof(uint32_t), s));
   k_wl_mark<<<grid, 256, 0, s>>>(kout, vout, n, keep, head);
-  WL_OK(hipGetLastError());
-  WL_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, keep, pos, (int)n + 1, s));
-  WL_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, head, kidx, (int)n + 1, s));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, keep, pos, (int)n + 1, s));
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, head, kidx, (int)n + 1, s));
   uint32_t tot[2] = {0, 0};
-  WL_OK(hipMemcpyAsync(&tot[0], pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  WL_OK(hipMemcpyAsync(&tot[1], kidx + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemcpyAsync(&tot[0], pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&tot[1], kidx + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
   init_pool_n_ = tot[0];
   init_keys_n_ = tot[1];
   if (init_pool_n_ > pool_cap_) fatal("WordLoop: the initial index exceeds the pool");
-  if (init_key_) WL_OK(hipFree(init_key_));
-  if (init_val_) WL_OK(hipFree(init_val_));
+  if (init_key_) HIP_OK(hipFree(init_key_));
+  if (init_val_) HIP_OK(hipFree(init_val_));
   init_key_ = wl_alloc<u64>(init_keys_n_, &bytes_);
   init_val_ = wl_alloc<u64>(init_keys_n_, &bytes_);
   k_wl_scatter<<<grid, 256, 0, s>>>(kout, vout, n, keep, pos, head, kidx, woff_, reinterpret_cast<WEnt*>(pool_),
                                     init_key_, init_val_);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   k_wl_counts<<<256, 256, 0, s>>>(init_val_, init_keys_n_, init_pool_n_);
-  WL_OK(hipGetLastError());
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(s));
   for (void* p : {(void*)kin, (void*)kout, (void*)vin, (void*)vout, (void*)keep, (void*)head, (void*)pos, (void*)kidx,
                   tmp, (void*)pbase, (void*)pcnt})
-    WL_OK(hipFree(p));
+    HIP_OK(hipFree(p));
   // the directory: at most half full
   uint64_t want = 1024;
   while (want < 2 * init_keys_n_) want <<= 1;
   if (want != dir_cap_) {
-    if (dkey_) WL_OK(hipFree(dkey_));
-    if (dval_) WL_OK(hipFree(dval_));
+    if (dkey_) HIP_OK(hipFree(dkey_));
+    if (dval_) HIP_OK(hipFree(dval_));
     dir_cap_ = want;
     dkey_ = wl_alloc<u64>(dir_cap_, &bytes_);
     dval_ = wl_alloc<u64>(dir_cap_, &bytes_);
@@ -2318,19 +2248,19 @@ void WordLoop::build_index() {
 void WordLoop::restore_index() {
   hipStream_t s = S(stream_);
   std::fill(lists_.begin(), lists_.end(), 0ull);  // no words-of lists: every merge looks its pair up
-  WL_OK(hipMemsetAsync(dkey_, 0xFF, dir_cap_ * sizeof(u64), s));
+  HIP_OK(hipMemsetAsync(dkey_, 0xFF, dir_cap_ * sizeof(u64), s));
   if (init_keys_n_) {
     k_wl_dir_init<<<1024, 256, 0, s>>>(init_key_, init_val_, init_keys_n_, dkey_, dval_, dir_cap_ - 1);
-    WL_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
   }
-  if (lseq_) WL_OK(hipMemsetAsync(lseq_, 0xFF, id_cap_ * sizeof(uint32_t), s));
+  if (lseq_) HIP_OK(hipMemsetAsync(lseq_, 0xFF, id_cap_ * sizeof(uint32_t), s));
   const uint32_t st[8] = {0, (uint32_t)init_pool_n_, 0, 0, 0, 0, 0, 0};
-  WL_OK(hipMemcpyAsync(dstate_, st, sizeof(st), hipMemcpyHostToDevice, s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemcpyAsync(dstate_, st, sizeof(st), hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
 }
 
 bool WordLoop::load_current(const TiledStream& ts) {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (!ready_ || !posted_.empty()) return false;
   stop();
   std::vector<int32_t> wtok(nint_ + kRunPad, 0);
@@ -2354,43 +2284,43 @@ bool WordLoop::load_current(const TiledStream& ts) {
   }
   if (!open || w + 1 != nwords_) return false;
   hipStream_t s = S(stream_);
-  WL_OK(hipMemcpyAsync(wtok_, wtok.data(), wtok.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(wtok_, wtok.data(), wtok.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
   k_wl_set_weights<<<(int)std::min<uint32_t>((nwords_ + 255) / 256, 4096), 256, 0, s>>>(wtok_, woff_, nwords_, weight_);
-  WL_OK(hipGetLastError());
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(s));
   build_index();
   dirty_ = false;
   return true;
 }
 
 void WordLoop::load_tiles(const int32_t* tok, const uint64_t* tile_off, const uint32_t* tile_len) {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (!ready_) return;
   if (!posted_.empty()) fatal("WordLoop::load_tiles with a merge in flight");
   stop();
   const int grid = (int)std::min<uint32_t>((ntiles_ + 255) / 256, 4096);
   k_tiles_to_words<<<std::max(grid, 1), 256, 0, S(stream_)>>>(tok, tile_off, tile_len, ntiles_, woff_, wtok_);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   build_index();
   dirty_ = false;
 }
 
 void WordLoop::reset_words() {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (!ready_) return;
   if (!posted_.empty()) fatal("WordLoop::reset_words with a merge in flight");
   stop();
-  WL_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, S(stream_)));
+  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, S(stream_)));
   dirty_ = false;
 }
 
 void WordLoop::reset() {
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (!ready_) return;
   if (!posted_.empty()) fatal("WordLoop::reset with a merge in flight");
   stop();
   hipStream_t s = S(stream_);
-  WL_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   restore_index();
   dirty_ = false;
 }
@@ -2402,13 +2332,13 @@ void WordLoop::ensure_slots(uint32_t cap) {
   // 3.1 us coherent + ordered flag, 2.3 us non-coherent + checksummed, round 6)
   const unsigned pin = hipHostMallocMapped | hipHostMallocNonCoherent;
   for (Slot& sl : slot_) {
-    if (sl.host_recs) WL_OK(hipHostFree(sl.host_recs));
-    WL_OK(hipHostMalloc((void**)&sl.host_recs, (size_t)rec_cap * sizeof(DeltaRecord), pin));
-    WL_OK(hipHostGetDevicePointer(&sl.dev_recs, sl.host_recs, 0));
+    if (sl.host_recs) HIP_OK(hipHostFree(sl.host_recs));
+    HIP_OK(hipHostMalloc((void**)&sl.host_recs, (size_t)rec_cap * sizeof(DeltaRecord), pin));
+    HIP_OK(hipHostGetDevicePointer(&sl.dev_recs, sl.host_recs, 0));
     if (!sl.host_hdr) {
-      WL_OK(hipHostMalloc((void**)&sl.host_hdr, 256, pin));
+      HIP_OK(hipHostMalloc((void**)&sl.host_hdr, 256, pin));
       std::memset(sl.host_hdr, 0, 256);
-      WL_OK(hipHostGetDevicePointer(&sl.dev_hdr, sl.host_hdr, 0));
+      HIP_OK(hipHostGetDevicePointer(&sl.dev_hdr, sl.host_hdr, 0));
     }
     sl.rec_cap = rec_cap;
   }
@@ -2425,25 +2355,25 @@ void WordLoop::reserve(int32_t max_id) {
   while (cap < need) cap *= 2;
   hipStream_t s = S(stream_);
   for (void* p : {(void*)dsum_, (void*)dft_, (void*)dlist_})
-    if (p) WL_OK(hipFree(p));
+    if (p) HIP_OK(hipFree(p));
   const size_t keys = 4 * ((size_t)cap + 1);
   dsum_ = wl_alloc<u64>(keys, &bytes_);
   dft_ = wl_alloc<u64>(keys, &bytes_);
   dlist_ = wl_alloc<uint32_t>(keys, &bytes_);
-  WL_OK(hipMemsetAsync(dsum_, 0, keys * sizeof(u64), s));
-  WL_OK(hipMemsetAsync(dft_, 0xFF, keys * sizeof(u64), s));
+  HIP_OK(hipMemsetAsync(dsum_, 0, keys * sizeof(u64), s));
+  HIP_OK(hipMemsetAsync(dft_, 0xFF, keys * sizeof(u64), s));
   // the words-of lists (ids past the old capacity have none)
   u64* nl = wl_alloc<u64>(cap, &bytes_);
   uint32_t* ns = wl_alloc<uint32_t>(cap, &bytes_);
 
-  WL_OK(hipMemsetAsync(ns, 0xFF, (size_t)cap * sizeof(uint32_t), s));
+  HIP_OK(hipMemsetAsync(ns, 0xFF, (size_t)cap * sizeof(uint32_t), s));
 
   if (lseq_) {
-    WL_OK(hipMemcpyAsync(nl, lst_, (size_t)id_cap_ * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    WL_OK(hipMemcpyAsync(ns, lseq_, (size_t)id_cap_ * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(nl, lst_, (size_t)id_cap_ * sizeof(u64), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(ns, lseq_, (size_t)id_cap_ * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
 
-    WL_OK(hipStreamSynchronize(s));
-    for (void* q : {(void*)lst_, (void*)lseq_}) WL_OK(hipFree(q));
+    HIP_OK(hipStreamSynchronize(s));
+    for (void* q : {(void*)lst_, (void*)lseq_}) HIP_OK(hipFree(q));
   }
   lst_ = nl;
   lseq_ = ns;
@@ -2452,7 +2382,7 @@ void WordLoop::reserve(int32_t max_id) {
   cap_ = cap;
   lists_.resize(cap, 0ull);
   ensure_slots(cap);
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipStreamSynchronize(s));
 }
 
 void WordLoop::launch(uint32_t seq0) {
@@ -2489,14 +2419,14 @@ void WordLoop::launch(uint32_t seq0) {
     p.sl[k].rec_cap = slot_[k].rec_cap;
   }
   status_[0] = 0;
-  WL_OK(hipEventRecord((hipEvent_t)ev_[0], S(stream_)));
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[0], S(stream_)));
   switch (probes_) {  // SHREDWORD_WL_PROBES (tests): 0 / 1 force the delta hash's HBM spill path
     case 0: k_word_loop<false, 0><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
     case 1: k_word_loop<false, 1><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
     default: k_word_loop<false, kProbesDefault><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
   }
-  WL_OK(hipGetLastError());
-  WL_OK(hipEventRecord((hipEvent_t)ev_[1], S(stream_)));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[1], S(stream_)));
   running_ = true;
   ++st_.launches;
 }
@@ -2505,7 +2435,7 @@ void WordLoop::launch(uint32_t seq0) {
 // check and its ring store, so commands can be waiting: the loop published the first command it
 // did not take (status_[1]), and a new launch resumes there (the ring still holds them).
 void WordLoop::recover_timeout() {
-  WL_OK(hipStreamSynchronize(S(stream_)));
+  HIP_OK(hipStreamSynchronize(S(stream_)));
   running_ = false;
   const uint32_t next = __atomic_load_n(&status_[1], __ATOMIC_ACQUIRE);
   if (next != seq_ + 1) {  // posted commands were not taken
@@ -2575,7 +2505,7 @@ void WordLoop::wait_flag(const Slot& sl, uint32_t seq) {
     }
     if (now_seconds() - t0 > 60.0) {
       const hipError_t e = hipStreamQuery(S(stream_));
-      if (e != hipSuccess && e != hipErrorNotReady) WL_OK(e);
+      if (e != hipSuccess && e != hipErrorNotReady) HIP_OK(e);
       if (now_seconds() - t0 > 300.0) fatal("k_word_loop did not signal completion within 300 s");
     }
   }
@@ -2662,16 +2592,16 @@ void WordLoop::rollback(int32_t X) {
 
 void WordLoop::stop() {
   if (!running_) return;
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   if (!posted_.empty()) fatal("WordLoop::stop with a merge in flight");
   post(kOpStop, 0, 0, 0);
-  WL_OK(hipStreamSynchronize(S(stream_)));
+  HIP_OK(hipStreamSynchronize(S(stream_)));
   running_ = false;
   float ms = 0;
-  WL_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
+  HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
   st_.kernel_ms += ms;
   uint32_t ds[8];
-  WL_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
 
   if (std::getenv("SHREDWORD_WL_REPORT") && st_.merges)
     std::fprintf(stderr, "[WL] %llu merges: device %.2f us a merge, of it the flag's system release %.2f us, "
@@ -2694,7 +2624,7 @@ void WordLoop::stop() {
 void WordLoop::sel_free() {
   void* ptrs[] = {ptab_, fr_[0], fr_[1], sst_dev_, thr_, sout_, upd_, shist_, scol_};
   for (void* q : ptrs)
-    if (q) WL_OK(hipFree(q));
+    if (q) HIP_OK(hipFree(q));
   ptab_ = thr_ = sout_ = nullptr;
   fr_[0] = fr_[1] = sst_dev_ = upd_ = shist_ = scol_ = nullptr;
   pcap_ = sout_cap_ = upd_cap_ = scol_cap_ = 0;
@@ -2707,12 +2637,12 @@ void WordLoop::sel_free() {
 bool WordLoop::sel_rebuild(uint64_t min_freq) {
   const double t0 = now_seconds();
   hipStream_t s = S(stream_);
-  WL_OK(hipMemsetAsync(shist_, 0, kSelBuckets * sizeof(uint32_t), s));
+  HIP_OK(hipMemsetAsync(shist_, 0, kSelBuckets * sizeof(uint32_t), s));
   k_sel_hist<<<1024, 512, 0, s>>>(ptab_, pcap_, min_freq, shist_);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   std::vector<uint32_t> hist(kSelBuckets);
-  WL_OK(hipMemcpyAsync(hist.data(), shist_, kSelBuckets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemcpyAsync(hist.data(), shist_, kSelBuckets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
   uint64_t acc = 0;
   uint32_t bstar = kSelBuckets;
   for (uint32_t b = kSelBuckets; b-- > 0;) {
@@ -2722,28 +2652,28 @@ bool WordLoop::sel_rebuild(uint64_t min_freq) {
     if (acc >= kSelK) break;
   }
   uint32_t st[kSelStats] = {};
-  WL_OK(hipMemcpyAsync(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost, s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemcpyAsync(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
   u64 thr[2] = {~0ull, 0ull};
   uint32_t nf = 0;
   if (acc > 0) {
     if (acc > scol_cap_) {
-      if (scol_) WL_OK(hipFree(scol_));
+      if (scol_) HIP_OK(hipFree(scol_));
       scol_cap_ = std::max<uint64_t>(2 * acc, 1 << 16);
       scol_ = wl_alloc<uint32_t>(scol_cap_ + 1, &bytes_);
     }
     uint32_t* ncol = scol_ + scol_cap_;
-    WL_OK(hipMemsetAsync(ncol, 0, sizeof(uint32_t), s));
+    HIP_OK(hipMemsetAsync(ncol, 0, sizeof(uint32_t), s));
     k_sel_collect<<<1024, 512, 0, s>>>(ptab_, pcap_, min_freq, bstar, scol_, ncol, scol_cap_);
-    WL_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     uint32_t nc = 0;
-    WL_OK(hipMemcpyAsync(&nc, ncol, sizeof(nc), hipMemcpyDeviceToHost, s));
-    WL_OK(hipStreamSynchronize(s));
+    HIP_OK(hipMemcpyAsync(&nc, ncol, sizeof(nc), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
     if (nc != acc) fatal("tiebreak=device: the frontier's collect disagrees with its histogram");
     if (nc <= kSelK) {  // every pair of the top buckets: the threshold is their lowest count
       nf = nc;
       k_sel_pick<<<64, 256, 0, s>>>(scol_, nullptr, nf, fr_[0]);
-      WL_OK(hipGetLastError());
+      HIP_OK(hipGetLastError());
       thr[0] = std::max<u64>(sel_bucket_lo(bstar), min_freq);
       thr[1] = ~0ull;
     } else {  // the top kSelK in (count desc, key asc) order: sort by key, then stably by count
@@ -2755,44 +2685,44 @@ bool WordLoop::sel_rebuild(uint64_t min_freq) {
       uint32_t* idx = wl_alloc<uint32_t>(nc, &acc2);
       uint32_t* idx2 = wl_alloc<uint32_t>(nc, &acc2);
       k_sel_gather<<<256, 256, 0, s>>>(scol_, nc, ptab_, key, negc, idx);
-      WL_OK(hipGetLastError());
+      HIP_OK(hipGetLastError());
       size_t tb = 0, tb2 = 0;
-      WL_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
-      WL_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
+      HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
+      HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
       void* tmp = wl_alloc<uint8_t>(std::max(tb, tb2), &acc2);
-      WL_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
+      HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
       // counts in key order, then a stable sort by ~count
       k_sel_gather<<<256, 256, 0, s>>>(scol_, nc, ptab_, key, negc, idx);  // key/negc of slot order
-      WL_OK(hipGetLastError());
+      HIP_OK(hipGetLastError());
       std::vector<uint32_t> order(nc);
       std::vector<u64> kc(nc), nn(nc);
-      WL_OK(hipMemcpyAsync(order.data(), idx2, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      WL_OK(hipMemcpyAsync(nn.data(), negc, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
-      WL_OK(hipMemcpyAsync(kc.data(), key, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
-      WL_OK(hipStreamSynchronize(s));
+      HIP_OK(hipMemcpyAsync(order.data(), idx2, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(nn.data(), negc, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipMemcpyAsync(kc.data(), key, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
       // (host) ~count in key order, sorted stably on the device
       std::vector<u64> nk(nc);
       for (uint32_t i = 0; i < nc; ++i) nk[i] = nn[order[i]];
-      WL_OK(hipMemcpyAsync(negc, nk.data(), nc * sizeof(u64), hipMemcpyHostToDevice, s));
-      WL_OK(hipMemcpyAsync(idx, order.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      WL_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
+      HIP_OK(hipMemcpyAsync(negc, nk.data(), nc * sizeof(u64), hipMemcpyHostToDevice, s));
+      HIP_OK(hipMemcpyAsync(idx, order.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
       nf = kSelK;
       k_sel_pick<<<64, 256, 0, s>>>(scol_, idx2, nf, fr_[0]);
-      WL_OK(hipGetLastError());
+      HIP_OK(hipGetLastError());
       uint32_t last = 0;
-      WL_OK(hipMemcpyAsync(&last, idx2 + (nf - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      WL_OK(hipStreamSynchronize(s));
+      HIP_OK(hipMemcpyAsync(&last, idx2 + (nf - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipStreamSynchronize(s));
       thr[0] = ~nn[last];
       thr[1] = kc[last];
-      for (void* q : {(void*)key, (void*)key2, (void*)negc, (void*)negc2, (void*)idx, (void*)idx2, tmp}) WL_OK(hipFree(q));
+      for (void* q : {(void*)key, (void*)key2, (void*)negc, (void*)negc2, (void*)idx, (void*)idx2, tmp}) HIP_OK(hipFree(q));
     }
   }
   st[kSelNF] = nf;
   st[kSelBuf] = 0;
   st[kSelStatus] = 0;
-  WL_OK(hipMemcpyAsync(sst_dev_, st, sizeof(st), hipMemcpyHostToDevice, s));
-  WL_OK(hipMemcpyAsync(thr_, thr, sizeof(thr), hipMemcpyHostToDevice, s));
-  WL_OK(hipStreamSynchronize(s));
+  HIP_OK(hipMemcpyAsync(sst_dev_, st, sizeof(st), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(thr_, thr, sizeof(thr), hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
   sst_.rebuilds += 1;
   sst_.rebuild_ms += 1e3 * (now_seconds() - t0);
   sst_.frontier_max = std::max<uint64_t>(sst_.frontier_max, nf);
@@ -2803,7 +2733,7 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
                          std::vector<SelectedMerge>* out) {
   out->clear();
   if (!ready_ || !posted_.empty()) return -1;
-  WL_OK(hipSetDevice(ordinal_));
+  HIP_OK(hipSetDevice(ordinal_));
   stop();
   if (n_max == 0) return 0;
   reserve(X0 + (int32_t)n_max);
@@ -2831,7 +2761,7 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
     shist_ = wl_alloc<uint32_t>(kSelBuckets, &bytes_);
   }
   if (2ull * n_max > sout_cap_) {
-    if (sout_) WL_OK(hipFree(sout_));
+    if (sout_) HIP_OK(hipFree(sout_));
     sout_cap_ = 2ull * n_max;
     sout_ = wl_alloc<u64>(sout_cap_, &bytes_);
   }
@@ -2839,20 +2769,20 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
   // when one more merge might not fit)
   const uint64_t need_log = std::max<uint64_t>(1ull << 22, 16ull * ((uint64_t)cap_ + 2));
   if (need_log > upd_cap_) {
-    if (upd_) WL_OK(hipFree(upd_));
+    if (upd_) HIP_OK(hipFree(upd_));
     upd_cap_ = need_log;
     upd_ = wl_alloc<uint32_t>(4 * upd_cap_, &bytes_);  // (key, delta) u64 pairs
   }
-  WL_OK(hipMemsetAsync(sst_dev_, 0, kSelWords * sizeof(uint32_t), s));
+  HIP_OK(hipMemsetAsync(sst_dev_, 0, kSelWords * sizeof(uint32_t), s));
   SelParams q{};
   auto table_from = [&](const PairCount* dp, size_t np, uint64_t cap) {  // a fresh table holding dp
     if (cap != pcap_) {
-      if (ptab_) WL_OK(hipFree(ptab_));
+      if (ptab_) HIP_OK(hipFree(ptab_));
       pcap_ = cap;
       ptab_ = wl_alloc<u64>(2 * pcap_, &bytes_);
     }
     k_sel_clear<<<1024, 256, 0, s>>>(ptab_, pcap_);
-    WL_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     q.tab = ptab_;
     q.pmask = pcap_ - 1;
     q.fr[0] = fr_[0];
@@ -2869,23 +2799,23 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
     q.fill_max = (uint32_t)std::min<uint64_t>(3 * pcap_ / 4, 0xFFFFFFF0ull);
     if (const char* e = std::getenv("SHREDWORD_SEL_PROBE")) q.probe = (uint32_t)std::atoi(e);
     uint32_t zero = 0;
-    WL_OK(hipMemcpyAsync(sst_dev_ + kSelIns, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
-    WL_OK(hipMemcpyAsync(sst_dev_ + kSelErr, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(sst_dev_ + kSelIns, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(sst_dev_ + kSelErr, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
     if (np) {
       k_sel_insert<<<512, 256, 0, s>>>(dp, np, q);
-      WL_OK(hipGetLastError());
+      HIP_OK(hipGetLastError());
     }
-    WL_OK(hipStreamSynchronize(s));
+    HIP_OK(hipStreamSynchronize(s));
     uint32_t err = 0;  // a pair that found no slot within the probe bound would be a lost count
-    WL_OK(hipMemcpy(&err, sst_dev_ + kSelErr, sizeof(err), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&err, sst_dev_ + kSelErr, sizeof(err), hipMemcpyDeviceToHost));
     if (err) fatal("tiebreak=device: the pair table's initial pairs overran the probe bound");
   };
   {
     size_t acc = 0;
     PairCount* dp = pairs.empty() ? nullptr : wl_alloc<PairCount>(pairs.size(), &acc);
-    if (dp) WL_OK(hipMemcpyAsync(dp, pairs.data(), pairs.size() * sizeof(PairCount), hipMemcpyHostToDevice, s));
+    if (dp) HIP_OK(hipMemcpyAsync(dp, pairs.data(), pairs.size() * sizeof(PairCount), hipMemcpyHostToDevice, s));
     table_from(dp, pairs.size(), want);
-    if (dp) WL_OK(hipFree(dp));
+    if (dp) HIP_OK(hipFree(dp));
   }
   sst_.table_slots = pcap_;
   uint32_t m = 0;
@@ -2913,23 +2843,23 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
     int stalls = 0;
     for (;;) {
       p.seq0 = seq_ + 1;
-      WL_OK(hipEventRecord((hipEvent_t)ev_[0], s));
+      HIP_OK(hipEventRecord((hipEvent_t)ev_[0], s));
       switch (probes_) {
         case 0: k_word_loop<true, 0><<<1, kWlThreads, 0, s>>>(p); break;
         case 1: k_word_loop<true, 1><<<1, kWlThreads, 0, s>>>(p); break;
         default: k_word_loop<true, kProbesDefault><<<1, kWlThreads, 0, s>>>(p); break;
       }
-      WL_OK(hipGetLastError());
-      WL_OK(hipEventRecord((hipEvent_t)ev_[1], s));
-      WL_OK(hipStreamSynchronize(s));
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipEventRecord((hipEvent_t)ev_[1], s));
+      HIP_OK(hipStreamSynchronize(s));
       float ms = 0;
-      WL_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
+      HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
       sst_.kernel_ms += ms;
       sst_.launches += 1;
       uint32_t st[kSelWords];
-      WL_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
       uint32_t ds[8];
-      WL_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
       if (ds[kStError]) {
         std::fprintf(stderr, "[ERROR]\t k_word_loop<true>: error code %u\n", ds[kStError]);
         fatal("tiebreak=device merge loop failed");
@@ -2945,10 +2875,10 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
       if (logn) {
         const double tl = now_seconds();
         k_sel_apply_log<<<1024, 256, 0, s>>>(reinterpret_cast<const u64*>(upd_), logn, q);
-        WL_OK(hipGetLastError());
-        WL_OK(hipMemsetAsync(sst_dev_ + kSelLogW, 0, sizeof(u64), s));
-        WL_OK(hipMemcpyAsync(st + kSelIns, sst_dev_ + kSelIns, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        WL_OK(hipStreamSynchronize(s));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemsetAsync(sst_dev_ + kSelLogW, 0, sizeof(u64), s));
+        HIP_OK(hipMemcpyAsync(st + kSelIns, sst_dev_ + kSelIns, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
         sst_.log_ms += 1e3 * (now_seconds() - tl);
         sst_.log_entries += logn;
       }
@@ -2970,21 +2900,21 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
         size_t acc = 0;
         PairCount* dp = wl_alloc<PairCount>(pcap_, &acc);
         uint32_t* dn = wl_alloc<uint32_t>(1, &acc);
-        WL_OK(hipMemsetAsync(dn, 0, sizeof(uint32_t), s));
+        HIP_OK(hipMemsetAsync(dn, 0, sizeof(uint32_t), s));
         k_sel_export<<<1024, 256, 0, s>>>(ptab_, pcap_, dp, dn);
-        WL_OK(hipGetLastError());
+        HIP_OK(hipGetLastError());
         uint32_t np = 0;
-        WL_OK(hipMemcpyAsync(&np, dn, sizeof(np), hipMemcpyDeviceToHost, s));
-        WL_OK(hipStreamSynchronize(s));
+        HIP_OK(hipMemcpyAsync(&np, dn, sizeof(np), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
         // the exported pairs must survive the old table's release: keep them in their own buffer
         const uint64_t grown = 4 * pcap_;
         u64* old = ptab_;
         ptab_ = nullptr;
         pcap_ = 0;
         table_from(dp, np, grown);
-        WL_OK(hipFree(old));
-        WL_OK(hipFree(dp));
-        WL_OK(hipFree(dn));
+        HIP_OK(hipFree(old));
+        HIP_OK(hipFree(dp));
+        HIP_OK(hipFree(dn));
         ++sst_.grows;
         p.sel = q;
         if (!sel_rebuild(min_freq)) break;
@@ -2994,7 +2924,7 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
       if (!sel_rebuild(min_freq)) break;
     }
     uint32_t st[kSelWords];
-    WL_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
     const u64* t64 = reinterpret_cast<const u64*>(st + kSelStats);
     sst_.select_us += 1e-2 * (double)t64[0];
     sst_.merge_us += 1e-2 * (double)t64[1];
@@ -3017,7 +2947,7 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
   sst_.table_slots = pcap_;
   sst_.merges += m;
   std::vector<u64> o(2 * (size_t)m);
-  if (m) WL_OK(hipMemcpy(o.data(), sout_, o.size() * sizeof(u64), hipMemcpyDeviceToHost));
+  if (m) HIP_OK(hipMemcpy(o.data(), sout_, o.size() * sizeof(u64), hipMemcpyDeviceToHost));
   out->resize(m);
   for (uint32_t i = 0; i < m; ++i)
     (*out)[i] = SelectedMerge{(int32_t)(uint32_t)(o[2 * i] >> 32), (int32_t)(uint32_t)o[2 * i], o[2 * i + 1]};
@@ -3026,7 +2956,7 @@ int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32
 
 uint64_t WordLoop::pool_used() const {
   uint32_t v = 0;
-  if (dstate_) WL_OK(hipMemcpy(&v, dstate_ + kStPoolTop, sizeof(v), hipMemcpyDeviceToHost));
+  if (dstate_) HIP_OK(hipMemcpy(&v, dstate_ + kStPoolTop, sizeof(v), hipMemcpyDeviceToHost));
   return v;
 }
 
@@ -3036,7 +2966,7 @@ void WordLoop::sync_tiles(int32_t* tok, const uint64_t* tile_off, uint32_t* tile
   const int grid = (int)std::min<uint32_t>((ntiles_ + 3) / 4, 4096);
   k_words_to_tiles<<<std::max(grid, 1), 256, 0, S(stream_)>>>(wtok_, woff_, tile_first_, tile_nw_, ntiles_, tok,
                                                            tile_off, tile_len);
-  WL_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   dirty_ = false;
 }
 

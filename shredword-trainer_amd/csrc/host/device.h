@@ -9,7 +9,9 @@
 //   dsum/dft  u64 per (neighbour slot, category): summed weight and min first-touch of the
 //             current merge's neighbour-pair deltas; dlist/dcount: the touched keys.  Two sets
 //             (merge parity), so a speculative merge X+1 can run while merge X is consumed.
-// No HIP type appears here so host C++ can include it; bpe_device.hip implements it.
+// No HIP type appears here so host C++ can include it.  Three units implement it: bpe_device.hip
+// (tables, launch path, the choice between the merge paths), resident_loop.hip (k_resident) and
+// pair_count.hip (K1, K6, probes).
 #pragma once
 
 #include <algorithm>
@@ -284,6 +286,7 @@ class Device : public Backend {
   void unmerge_run(ChainRun& run, int j0);
   void unmerge_launch(ChainRun& run, const uint32_t* tiles, size_t n_tiles, int j0 = 0);
   void flush_timing(bool block);
+  void rebuild_signatures();  // k_sig_build over every tile (bpe_device.hip)
 
   int ordinal_ = 0;
   void* stream_ = nullptr;
@@ -389,7 +392,7 @@ class Device : public Backend {
   uint64_t wl_ms_seen_ = 0;        // merges already folded into times_
   double wl_kms_seen_ = 0;         // launch time already folded into times_
 
-  // ---- k_resident state (bpe_device.hip "K2+K3 resident")
+  // ---- k_resident state (resident_loop.hip "K2+K3 resident")
   struct ResPost {          // a merge posted to the resident loop and not yet collected
     int32_t X, a, b;
     uint32_t seq;
@@ -404,6 +407,10 @@ class Device : public Backend {
   uint32_t post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int slot);
   bool wait_resident(const MergeSlot& sl, int32_t X);  // false: the launch aborted
   int pick_resident_slot();
+  // what merge_chain and rollback need of the resident loop
+  bool resident_aborted() const;
+  void post_resident_merge(const int32_t* ab, int32_t X0);
+  void undo_resident_from(int32_t X);
   size_t collect_resident(int32_t X, const DeltaRecord** recs);
   [[noreturn]] void resident_dump(const char* why);
   bool resident_on_ = true;       // option (SHREDWORD_RESIDENT / set_option resident)
