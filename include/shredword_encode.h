@@ -102,6 +102,52 @@ int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n,
                                   void* starts, void* line_off, size_t line_cap, size_t* num_lines,
                                   void* stream, double* kernel_ms);
 
+/* ---- ids back to bytes on the GPU, per row ---------------------------------------------------
+ *
+ *   ids        n int32.
+ *   row_off    NULL with rows == 0: one row holding all ids.  Otherwise rows + 1 int64 entries in
+ *              the line_off format above: row_off[0] == 0, non-decreasing, row_off[rows] == n;
+ *              row r holds ids[row_off[r] : row_off[r+1]].  Empty rows are allowed.
+ *   sep        -1 for none, or a byte 0..255 written after every row, the last and empty rows
+ *              included (with row_off == NULL one separator ends the single row).  line_off from
+ *              shred_encode_spans with sep = '\n' gives one '\n'-terminated line per row.
+ *   unk        unk_len == -1 is strict: an id outside [0, 256 + num_merges) fails the call with
+ *              -1, as shred_decode does.  0 <= unk_len <= SHRED_DECODE_MAX_UNK: each such id
+ *              decodes to these unk_len bytes (0 drops it).
+ *   byte_off   NULL, or rows + 1 int64 (1 + 1 when row_off is NULL): byte_off[r] is the offset in
+ *              out of row r's first byte, byte_off[rows] the total.  Row r without its separator
+ *              is out[byte_off[r] : byte_off[r+1] - (sep >= 0)].
+ *
+ * Returns the byte count needed.  If out is NULL or cap is smaller than that, nothing is written
+ * to out or byte_off (the sizing call: only the length passes run); otherwise exactly that many
+ * bytes are written and nothing past them.  Errors, with nothing written to out or byte_off:
+ * -1 bad argument, unk_len out of range, HIP error, or a strict-mode id outside the vocabulary;
+ * -5 the vocabulary's bytes exceed SHRED_DECODE_MAX_VOCAB_BYTES; -6 row_off is not
+ * 0 = row_off[0] <= ... <= row_off[rows] = n.  (A HIP error after the first piece of
+ * shred_decode_rows leaves the earlier pieces' bytes in out.)
+ *
+ * The vocabulary (4 B per id + its bytes) and the decode scratch (12 B per id, 16 B with rows and
+ * a separator) are allocated on the first decode call and freed with the encoder, so the encode
+ * calls' footprints are unchanged.
+ */
+
+/* All buffers on the encoder's device (row_off is validated there); queued on `stream` (NULL =
+ * the encoder's own) and synchronised before return.  kernel_ms (may be NULL) receives the
+ * device time of the decode passes. */
+int64_t shred_decode_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                            void* out, size_t cap, void* byte_off, int sep, const uint8_t* unk, int unk_len,
+                            void* stream, double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of a fixed number of ids (cut at
+ * any id, so rows straddle pieces): device memory does not grow with n. */
+int64_t shred_decode_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          uint8_t* out, size_t cap, int64_t* byte_off, int sep, const uint8_t* unk, int unk_len);
+
+/* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
+#define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
+/* Longest replacement for ids outside the vocabulary. */
+#define SHRED_DECODE_MAX_UNK 8
+
 #ifdef __cplusplus
 }
 #endif

@@ -591,6 +591,7 @@ EncodeDevice::~EncodeDevice() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   free_spans();
+  free_decode();
   for (void* p : {(void*)table_, (void*)byte_map_, (void*)misc_, (void*)pad_, (void*)rank_, (void*)tcnt_,
                   (void*)bcnt_, (void*)dtext_, (void*)dout_, (void*)cslot_, scan_tmp_})
     if (p) (void)hipFree(p);

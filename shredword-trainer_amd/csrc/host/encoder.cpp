@@ -34,6 +34,30 @@ std::vector<uint64_t> enc_build_table(const std::vector<int32_t>& first, const s
   return tab;
 }
 
+bool enc_build_arena(const std::vector<int32_t>& first, const std::vector<int32_t>& second,
+                     std::vector<uint32_t>* off, std::vector<uint8_t>* bytes) {
+  const size_t M = first.size(), V = 256 + M;
+  off->clear();
+  bytes->clear();
+  std::vector<uint64_t> o(V + 1);
+  for (size_t i = 0; i <= 256; ++i) o[i] = i;
+  for (size_t m = 0; m < M; ++m) {
+    const size_t a = (size_t)first[m], b = (size_t)second[m];  // ids below 256 + m (split_merges)
+    o[256 + m + 1] = o[256 + m] + (o[a + 1] - o[a]) + (o[b + 1] - o[b]);
+    if (o[256 + m + 1] > kDecMaxVocabBytes) return false;
+  }
+  off->assign(o.begin(), o.end());
+  bytes->resize((size_t)o[V]);
+  for (size_t i = 0; i < 256; ++i) (*bytes)[i] = (uint8_t)i;
+  for (size_t m = 0; m < M; ++m) {
+    const size_t a = (size_t)first[m], b = (size_t)second[m];
+    uint8_t* dst = bytes->data() + o[256 + m];
+    std::memcpy(dst, bytes->data() + o[a], (size_t)(o[a + 1] - o[a]));
+    std::memcpy(dst + (o[a + 1] - o[a]), bytes->data() + o[b], (size_t)(o[b + 1] - o[b]));
+  }
+  return true;
+}
+
 }  // namespace shred
 
 struct ShredEncoder {
@@ -42,6 +66,7 @@ struct ShredEncoder {
   std::vector<std::string> tokens;  // bytes of every id (256 + merges)
   std::vector<int32_t> lens;        // source bytes of every id, from the merge list alone
   bool spans_ok = true;             // no byte maps to an id >= 256
+  uint64_t vocab_bytes = 0;         // bytes of all tokens (the device decoder's arena)
   std::unique_ptr<shred::EncodeDevice> dev;
 };
 
@@ -73,6 +98,7 @@ ShredEncoder* make(std::vector<int32_t> first, std::vector<int32_t> second, cons
   for (size_t m = 0; m < M; ++m)
     e->lens[256 + m] = (int32_t)std::min<int64_t>((int64_t)e->lens[first[m]] + e->lens[second[m]], INT32_MAX);
   for (int b = 0; b < 256; ++b) e->spans_ok = e->spans_ok && e->byte_map[b] < 256;
+  for (const std::string& t : e->tokens) e->vocab_bytes += t.size();
   std::string why;
   e->dev.reset(shred::EncodeDevice::create(device, shred::enc_build_table(first, second), e->byte_map, &why));
   if (!e->dev) {
@@ -229,6 +255,47 @@ int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint
     need += t.size();
   }
   return (int64_t)need;
+}
+
+namespace {
+// What both row decoders refuse before any work: 0, -1 or -5.
+int decode_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows, int sep,
+                const uint8_t* unk, int unk_len) {
+  if (!enc || (n && !ids) || (!row_off && rows) || sep < -1 || sep > 255) return -1;
+  if (unk_len < -1 || unk_len > SHRED_DECODE_MAX_UNK || (unk_len > 0 && !unk)) return -1;
+  if (enc->vocab_bytes > SHRED_DECODE_MAX_VOCAB_BYTES) return -5;
+  return 0;
+}
+}  // namespace
+
+int64_t shred_decode_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                            void* out, size_t cap, void* byte_off, int sep, const uint8_t* unk, int unk_len,
+                            void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  if (const int r = decode_args(enc, ids, n, row_off, rows, sep, unk, unk_len)) return r;
+  return enc->dev->decode((const int32_t*)ids, n, (const int64_t*)row_off, rows, (uint8_t*)out, cap,
+                          (int64_t*)byte_off, sep, unk, unk_len, enc->first, enc->second, stream, kernel_ms);
+}
+
+int64_t shred_decode_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          uint8_t* out, size_t cap, int64_t* byte_off, int sep, const uint8_t* unk, int unk_len) {
+  if (const int r = decode_args(enc, ids, n, row_off, rows, sep, unk, unk_len)) return r;
+  if (row_off) {
+    if (row_off[0] != 0 || row_off[rows] < 0 || (uint64_t)row_off[rows] != n) return -6;
+    for (size_t r = 0; r < rows; ++r)
+      if (row_off[r] > row_off[r + 1]) return -6;
+  }
+  // the length pass of host ids: the sizing call and the capacity check need no device
+  uint64_t need = sep >= 0 ? (row_off ? rows : 1) : 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (ids[i] >= 0 && (size_t)ids[i] < enc->tokens.size()) need += enc->tokens[ids[i]].size();
+    else if (unk_len < 0) return -1;
+    else need += (uint64_t)unk_len;
+  }
+  if (!out || cap < need) return (int64_t)need;
+  const int64_t r = enc->dev->decode_host(ids, n, row_off, rows, out, byte_off, sep, unk, unk_len, enc->first,
+                                          enc->second);
+  return r < 0 ? r : (int64_t)need;
 }
 
 }  // extern "C"

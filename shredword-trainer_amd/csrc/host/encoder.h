@@ -23,6 +23,14 @@ inline uint64_t enc_slot(uint64_t key) { return (key * 0x9E3779B97F4A7C15ull) >>
 // Builds the table; the first (lowest-rank) entry of a repeated pair wins, like the replay.
 std::vector<uint64_t> enc_build_table(const std::vector<int32_t>& first, const std::vector<int32_t>& second);
 
+// The decoder's vocabulary: off[i] .. off[i + 1] are the bytes of id i in `bytes` (256 + M ids; id
+// 256 + m is first[m]'s bytes followed by second[m]'s).  False, with both left empty, when the
+// bytes exceed kDecMaxVocabBytes.
+constexpr uint64_t kDecMaxVocabBytes = 1ull << 30;  // SHRED_DECODE_MAX_VOCAB_BYTES
+constexpr int kDecMaxUnk = 8;                       // SHRED_DECODE_MAX_UNK
+bool enc_build_arena(const std::vector<int32_t>& first, const std::vector<int32_t>& second,
+                     std::vector<uint32_t>* off, std::vector<uint8_t>* bytes);
+
 class EncodeDevice {
  public:
   // Uploads the table and byte map to `device`; *why says what failed.
@@ -50,6 +58,19 @@ class EncodeDevice {
   // The same on host buffers, in the pieces of encode_host.
   int64_t encode_spans_host(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts,
                             int64_t* line_off, size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens);
+
+  // ---- ids to bytes (decode_device.hip; arguments and results as include/shredword_encode.h
+  // defines them for shred_decode_device / shred_decode_rows).  first / second: the merge list,
+  // from which the device vocabulary is built and uploaded on the first call.  The callers have
+  // checked the arguments' ranges; decode_host's have also checked row_off, the ids (strict mode)
+  // and cap on the host, so it returns the bytes written or -1.
+  int64_t decode(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, uint8_t* out, size_t cap,
+                 int64_t* byte_off, int sep, const uint8_t* unk, int unk_len, const std::vector<int32_t>& first,
+                 const std::vector<int32_t>& second, void* stream, double* kernel_ms);
+  static constexpr size_t kDecodePiece = size_t(1) << 25;  // ids per piece of decode_host
+  int64_t decode_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, uint8_t* out,
+                      int64_t* byte_off, int sep, const uint8_t* unk, int unk_len,
+                      const std::vector<int32_t>& first, const std::vector<int32_t>& second);
 
  private:
   EncodeDevice() = default;
@@ -107,6 +128,33 @@ class EncodeDevice {
   size_t sp_hstarts_cap_ = 0, sp_hline_cap_ = 0;
   int64_t* sp_hstarts_ = nullptr;
   int64_t* sp_hline_ = nullptr;
+
+  // decode passes (decode_device.hip): allocated on the first decode call, never by the encode calls
+  struct DecodeCall;  // one call's arguments, as the kernels take them
+  bool reserve_decode(size_t n, size_t rows, const std::vector<int32_t>& first, const std::vector<int32_t>& second);
+  // Length passes over n device ids and their row_off (nullptr, or rows + 1 entries whose end
+  // points are checked when c.ends): Q into dec_q_, *total = the bytes needed.  0, -1, -6.
+  int decode_lengths(const DecodeCall& c, void* stream, uint64_t* total);
+  // byte_off (nullptr, or as the header defines it, plus c.base) and the total bytes into out.
+  int decode_expand(const DecodeCall& c, uint64_t total, uint8_t* out, int64_t* byte_off, void* stream);
+  void free_decode();  // called by the destructor
+  uint32_t dec_vocab_ = 0;           // 256 + M
+  uint32_t* dec_tok_off_ = nullptr;  // 256 + M + 1 offsets into dec_arena_
+  uint8_t* dec_arena_ = nullptr;     // the bytes of every token
+  size_t dec_ids_ = 0;               // dec_q_ holds dec_ids_ + 1 entries
+  uint64_t* dec_q_ = nullptr;        // Q[k]: output offset of token k; Q[n] = the total
+  size_t dec_marks_ = 0;             // dec_mark_ holds dec_marks_ + 1 entries
+  uint32_t* dec_mark_ = nullptr;     // rows that end just before id k (separators in front of it)
+  void* dec_tmp_ = nullptr;          // hipCUB scan scratch
+  size_t dec_tmp_bytes_ = 0;
+  uint64_t* dec_err_ = nullptr;      // device: [0] an id outside the vocabulary, [1] bad row_off
+  uint64_t* dec_host_ = nullptr;     // pinned: total, the two error words
+  void* dec_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  // host-path staging: ids, row offsets, byte offsets, output bytes of a piece
+  size_t dec_hids_cap_ = 0, dec_hrow_cap_ = 0, dec_hout_cap_ = 0;
+  int32_t* dec_hids_ = nullptr;
+  int64_t* dec_hrow_ = nullptr;      // 2 x dec_hrow_cap_: row offsets, then byte offsets
+  uint8_t* dec_hout_ = nullptr;
 };
 
 }  // namespace shred

@@ -163,3 +163,10 @@ lib.shred_encode_spans.restype = c_int64
 lib.shred_encode_spans_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                           c_size_t, POINTER(c_size_t), c_void_p, POINTER(c_double)]
 lib.shred_encode_spans_device.restype = c_int64
+# ids back to bytes, per row
+lib.shred_decode_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                    c_int, c_char_p, c_int, c_void_p, POINTER(c_double)]
+lib.shred_decode_device.restype = c_int64
+lib.shred_decode_rows.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                  c_int, c_char_p, c_int]
+lib.shred_decode_rows.restype = c_int64

@@ -17,6 +17,11 @@ import numpy as np
 from .cbase import lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
+MAX_UNK = 8      # SHRED_DECODE_MAX_UNK
+# decode_device.hip: output bytes per workgroup of the expansion kernel (kTile), ids per workgroup of
+# the strict-mode id check (kChunk)
+DECODE_TILE = 4096
+DECODE_CHUNK = 4096
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -178,6 +183,82 @@ class BPEEncoder:
         out = np.empty(max(1, need), dtype=np.uint8)
         lib.shred_decode(self.enc, a.ctypes.data, a.size, out.ctypes.data, out.size)
         return out[:need].tobytes()
+
+    @staticmethod
+    def _decode_args(sep, unk):
+        if sep is not None and (not isinstance(sep, (bytes, bytearray)) or len(sep) != 1):
+            raise ValueError("sep must be None or one byte")
+        if unk is not None and (not isinstance(unk, (bytes, bytearray)) or len(unk) > MAX_UNK):
+            raise ValueError(f"unk must be None or at most {MAX_UNK} bytes")
+        return (-1 if sep is None else sep[0]), (None if unk is None else bytes(unk)), (-1 if unk is None else len(unk))
+
+    @staticmethod
+    def _check_decode(r: int) -> int:
+        if r == -6:
+            raise ValueError("row_offsets must be 0 = row_offsets[0] <= ... <= row_offsets[rows] = len(ids)")
+        if r == -5:
+            raise RuntimeError("the vocabulary's bytes exceed the device decoder's limit")
+        if r < 0:
+            raise RuntimeError(f"decode failed (code {r})")
+        return r
+
+    def decode_rows(self, ids, row_offsets=None, sep=None, unk=None):
+        """-> (bytes, byte_offsets).  Row r holds ids[row_offsets[r]:row_offsets[r + 1]] (the
+        line_offsets format of encode_lines; None: one row of all ids).  sep: None or one byte
+        written after every row, empty rows included.  unk: None (an id outside the vocabulary
+        raises ValueError) or at most 8 bytes that every such id decodes to (b"" drops it).
+        byte_offsets (int64, rows + 1 entries): row r without its separator is
+        bytes[byte_offsets[r]:byte_offsets[r + 1] - len(sep or b"")].  Decoded on the GPU."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        row = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+        if row is not None and row.size == 0:
+            raise ValueError("row_offsets must hold rows + 1 entries")
+        s, u, ul = self._decode_args(sep, unk)
+        rows = 0 if row is None else row.size - 1
+        args = (self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data, rows)
+        need = lib.shred_decode_rows(*args, None, 0, None, s, u, ul)
+        if need == -1 and unk is None:
+            raise ValueError("id outside the vocabulary")
+        self._check_decode(need)
+        out = np.empty(max(1, need), dtype=np.uint8)
+        boff = np.empty((rows if row is not None else 1) + 1, dtype=np.int64)
+        r = self._check_decode(lib.shred_decode_rows(*args, out.ctypes.data, need, boff.ctypes.data, s, u, ul))
+        return out[:r].tobytes(), boff
+
+    def decode_lines(self, ids, line_offsets, unk=None):
+        """The inverse of encode_lines up to the delimiters inside a line: -> list of bytes, one per row."""
+        data, boff = self.decode_rows(ids, line_offsets, sep=b"\n", unk=unk)
+        return [data[boff[i]:boff[i + 1] - 1] for i in range(boff.size - 1)]
+
+    def decode_device(self, ids, row_offsets=None, sep=None, unk=None, stream=None):
+        """ids: 1-D int32 torch tensor on the encoder's GPU, row_offsets: None or a 1-D int64 tensor
+        there (the views encode_spans_device returns fit) -> (uint8 tensor, int64 byte_offsets
+        tensor, device milliseconds of the decode passes); arguments as decode_rows."""
+        import torch
+        for name, t, dt in (("ids", ids, torch.int32), ("row_offsets", row_offsets, torch.int64)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} CUDA tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the encoder on cuda:{self.device}")
+        if row_offsets is not None and row_offsets.numel() == 0:
+            raise ValueError("row_offsets must hold rows + 1 entries")
+        s, u, ul = self._decode_args(sep, unk)
+        rows = 0 if row_offsets is None else row_offsets.numel() - 1
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(), rows)
+        ms0, ms1 = ctypes.c_double(), ctypes.c_double()
+        need = lib.shred_decode_device(*args, None, 0, None, s, u, ul, st, ctypes.byref(ms0))
+        if need == -1 and unk is None:
+            raise ValueError("id outside the vocabulary (or a device error; see stderr)")
+        self._check_decode(need)
+        out = torch.empty(max(1, need), dtype=torch.uint8, device=ids.device)
+        boff = torch.empty((rows if row_offsets is not None else 1) + 1, dtype=torch.int64, device=ids.device)
+        r = self._check_decode(lib.shred_decode_device(*args, out.data_ptr(), need, boff.data_ptr(), s, u, ul, st,
+                                                       ctypes.byref(ms1)))
+        return out[:r], boff, ms1.value
 
     def destroy(self):
         if getattr(self, "enc", None):
