@@ -495,6 +495,7 @@ int Engine::train_device(Backend& be, double t0) {
       pairs.clear();
       be.count_pairs(unk_, &pairs);
     }
+    if (pairs.empty()) break;  // no pair, no merge: a corpus without a word has no tiles and no loop to ask
     const int want = std::min(chunk, target - n);
     std::vector<SelectedMerge> part;
     const int got = be.device_select(pairs, X0 + n, want, min_freq_, &part);
