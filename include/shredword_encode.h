@@ -143,6 +143,78 @@ int64_t shred_decode_device(ShredEncoder* enc, const void* ids, size_t n, const 
 int64_t shred_decode_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
                           uint8_t* out, size_t cap, int64_t* byte_off, int sep, const uint8_t* unk, int unk_len);
 
+/* ---- rows of ids to rectangular model inputs on the GPU: padded batches, packed sequences ------
+ *
+ * Inputs of both forms:
+ *   ids         n int32.
+ *   row_off     rows + 1 int64 in the line_off format: 0 = row_off[0] <= ... <= row_off[rows] = n,
+ *               else the call returns -6.  NULL with rows == 0: all ids form one row (the outputs
+ *               below then have 1 row, and row_start 1 + 1 entries).  len_r = row_off[r+1] - row_off[r].
+ *   bos, eos    each NULL for none, or a host pointer to one int32 id.  Any int32 value is allowed:
+ *               the ids are never looked up in the vocabulary.  add = (bos != NULL) + (eos != NULL).
+ *   max_len     0: unlimited.  Otherwise every emitted row holds at most max_len ids, the added
+ *               ones included; max_len < add returns -1.
+ *               keep_r = len_r when unlimited, else min(len_r, max_len - add).
+ *   trunc_side  0 keeps the first keep_r ids of a row, 1 the last keep_r.
+ *
+ * Emitted row r is [bos] + kept ids + [eos], of length e_r = add + keep_r.  E[r] is the sum of
+ * e_r' over r' < r, E[rows] = T.  An empty row emits only its added ids; with add == 0 it emits
+ * nothing, so E repeats a value.
+ *
+ * Pad (width = W, pad_id, pad_side): out is [rows, W] int32, row-major.
+ *   pad_side 0  out[r, c] = emitted id c for c < e_r, else pad_id.
+ *   pad_side 1  emitted id j goes to out[r, W - e_r + j]; everything to its left is pad_id.
+ *   lengths     NULL, or rows int32: lengths[r] = e_r.
+ *   mask        NULL, or [rows, W] uint8: 1 where a token sits, 0 where padding sits.
+ *   Returns max_r e_r (0 for rows == 0).  Nothing is written if out is NULL, or width is smaller
+ *   than that, or cap < rows * width (cap counts int32 entries): the sizing call, only the length
+ *   passes run.  With max_len > 0, width = max_len always suffices.
+ *
+ * Pack (seq_len = L >= 1, pad_id, drop_last): the stream is the concatenation of the emitted rows.
+ *   S = ceil(T / L), or floor(T / L) with drop_last.  out is [S, L] int32, row-major:
+ *   out[p] = stream id p for p < min(T, S * L), and pad_id for T <= p < S * L (a tail that exists
+ *   only without drop_last).
+ *   pos         NULL, or S * L int32: the index of p inside its emitted row (a bos is at 0);
+ *               padding gets 0.
+ *   seg         NULL, or S * L int32: the row index r; padding gets -1.  rows > INT32_MAX returns -1.
+ *   row_start   NULL, or rows + 1 int64: E[0 .. rows], written in full even when drop_last cuts
+ *               the stream.
+ *   Returns S.  Nothing is written if out is NULL or cap < S * L.
+ *
+ * Errors of both, with nothing written: -1 bad argument, HIP error, or an e_r, rows * width or
+ * S * L that does not fit its type (int32, size_t / int64); -6 bad row_off.  (A HIP error after
+ * the first piece of the _rows calls leaves the earlier pieces' output in place.)
+ *
+ * The batch scratch (8 B per row for E, the scan's temporaries, a pinned result word, events) is
+ * allocated on the first batch call and freed with the encoder, so the encode and decode calls'
+ * footprints are unchanged.
+ */
+
+/* All buffers on the encoder's device (row_off is validated there); queued on `stream` (NULL =
+ * the encoder's own) and synchronised before return.  Output pointers need only their element's
+ * alignment (4 bytes; 1 for mask), so tensor views fit.  kernel_ms (may be NULL) receives the
+ * device time of the batch passes. */
+int64_t shred_pad_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t width,
+                         int32_t pad_id, int pad_side, void* out, size_t cap, void* lengths, void* mask,
+                         void* stream, double* kernel_ms);
+int64_t shred_pack_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                          const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t seq_len,
+                          int32_t pad_id, int drop_last, void* out, size_t cap, void* pos, void* seg,
+                          void* row_start, void* stream, double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces cut at row boundaries: a piece
+ * takes whole rows while it holds at most a fixed number of ids (and of rows, and for pad of
+ * output entries), so device memory does not grow with n.  A single row longer than a piece is
+ * staged whole: the longest row bounds the device memory.  Without row_off the one row is one piece. */
+int64_t shred_pad_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t width,
+                       int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask);
+int64_t shred_pack_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                        const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t seq_len,
+                        int32_t pad_id, int drop_last, int32_t* out, size_t cap, int32_t* pos, int32_t* seg,
+                        int64_t* row_start);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -1,0 +1,637 @@
+// Rows of token ids to rectangular model inputs on gfx950: padded batches and packed sequences
+// (C ABI and definitions: include/shredword_encode.h, shred_pad_* / shred_pack_*).  The passes use
+// none of the encoder's or the decoder's kernels.
+//
+// Row r keeps keep_r of its len_r ids (from either end) and emits e_r = add + keep_r ids: an
+// optional bos, the kept ids, an optional eos.  E is the exclusive prefix sum of e_r, E[rows] = T.
+//
+//   k_bat_rows       one thread per row_off entry: range, order and end points, and e_r <= INT32_MAX
+//                    (error words, ordinary stores, no atomics);
+//   hipCUB scan      pack only: inclusive sum over k = 0 .. rows of (k ? e_{k-1} : 0) through a
+//                    transform iterator on row_off: E[0 .. rows];
+//   hipCUB reduce    pad only: the maximum of e_r through the same kind of iterator (the width needed);
+//   k_bat_pad        output-centric: one workgroup per kTile consecutive entries of the flat [rows, W]
+//                    array, 4 consecutive entries per lane.  The 64-bit (r, c) split of a lane's first
+//                    entry is done once and then walked (++c, a new row's offsets at c == W), so a
+//                    lane's entries may straddle rows.  The lane that owns c == 0 writes lengths[r];
+//                    the mask bytes come from the same walk.  Pad needs no E: entry (r, c) depends
+//                    on row r alone;
+//   k_bat_row_start  pack: row_start[r] = base + E[r];
+//   k_bat_pack       one workgroup per kTile stream positions.  Its first row by a binary search of
+//                    E: the last r with E[r] <= the tile's first position, which skips the rows that
+//                    emit nothing.  Rounds of kStage rows staged in LDS (E relative to the tile, e_r,
+//                    the index in ids of the row's emitted id 0); every lane makes 4 consecutive
+//                    positions: a binary search of the LDS offsets for the row under its first
+//                    position, then a forward walk.  A round resolves the positions below the E of
+//                    the first row it did not stage, so a tile with more rows than kStage (rows that
+//                    emit nothing, rows of one id) takes more rounds, and a row longer than a tile
+//                    needs no special case.  Entry `rows` of E is staged as a row that emits nothing:
+//                    every position no row covers is padding (pos 0, seg -1).
+//
+// Traffic per output entry.  Pad at fill f = sum e_r / (rows W): writes 4, reads 4 f (the ids):
+// 4 + 4 f bytes, + 1 with the mask; per row 8 (row pass) + 8 (reduce) = 16 B, and each lane reads
+// the two offsets of every row it touches through the caches.  Pack: reads 4 (ids), writes 4: 8
+// bytes, + 4 each for pos and seg; per row 8 (row pass) + 8 (scan reads row_off) = 16 B, and E is
+// written once and read back with row_off by the tiles (24 B per row, through the caches).
+// All global indices are 64-bit; every store is an ordinary vector store.  Output pointers are
+// only element-aligned (tensor views), so the 16-byte (mask: 4-byte) stores have a scalar form.
+#include <hip/hip_runtime.h>
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../host/encoder.h"
+#include "encode_common.h"
+
+namespace shred {
+
+struct EncodeDevice::BatchCall {
+  const int32_t* ids;
+  uint64_t n;
+  const int64_t* row;  // nullptr: one row of all ids (rows == 1); else rows + 1 entries
+  uint64_t rows;
+  bool ends;           // check row[0] == 0 and row[rows] == n (a piece's local offsets: no)
+  BatchOpts o;
+  uint64_t base;       // pack: stream offset of the call's first row (ids of the pieces before)
+  uint64_t row_base;   // pack: index of the call's first row
+};
+
+namespace {
+
+typedef uint64_t u64;
+
+constexpr int kThreads = 256;
+constexpr int kLane = 4;                   // int32 entries per lane: one 16-byte store
+constexpr int kTile = kThreads * kLane;    // output entries per workgroup (BATCH_TILE)
+constexpr int kStage = 512;                // rows staged in LDS per round (BATCH_STAGE)
+constexpr u64 kNoLimit = ~0ull;
+
+// How a row turns into its emitted row; passed to the kernels and the hipCUB iterators by value.
+struct Rows {
+  const int64_t* row;  // nullptr: the one row [0, n)
+  u64 n;
+  u64 keep_max;        // most ids a row keeps: max_len - add, or kNoLimit
+  uint32_t bos_n, eos_n, left;
+  int32_t bos, eos;
+  __host__ __device__ __forceinline__ void bounds(u64 r, u64* a, u64* b) const {
+    *a = row ? (u64)row[r] : 0;
+    *b = row ? (u64)row[r + 1] : n;
+  }
+  __host__ __device__ __forceinline__ u64 keep(u64 a, u64 b) const { return b - a < keep_max ? b - a : keep_max; }
+  __host__ __device__ __forceinline__ u64 emit(u64 r) const {
+    u64 a, b;
+    bounds(r, &a, &b);
+    return (u64)(bos_n + eos_n) + keep(a, b);
+  }
+  // e_r, and the index in ids that emitted id j = 0 would have (the bos sits there, if any): emitted
+  // id j in [bos_n, e_r - eos_n) is ids[src + j].
+  __device__ __forceinline__ void span(u64 r, u64* e, u64* src) const {
+    u64 a, b;
+    bounds(r, &a, &b);
+    const u64 k = keep(a, b);
+    *e = (u64)(bos_n + eos_n) + k;
+    *src = (left ? b - k : a) - (u64)bos_n;
+  }
+  __device__ __forceinline__ int32_t id(const int32_t* __restrict__ ids, u64 e, u64 src, u64 j) const {
+    return j < (u64)bos_n ? bos : (eos_n && j == e - 1) ? eos : ids[src + j];
+  }
+};
+
+Rows rows_of(const EncodeDevice::BatchOpts& o, const int64_t* row, u64 n) {
+  const uint32_t b = o.has_bos ? 1u : 0u, e = o.has_eos ? 1u : 0u;
+  return Rows{row, n, o.max_len ? o.max_len - (b + e) : kNoLimit, b, e, o.trunc_side ? 1u : 0u, o.bos, o.eos};
+}
+
+__global__ __launch_bounds__(kThreads) void k_bat_rows(Rows rw, u64 rows, int ends, u64* __restrict__ err) {
+  const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
+  if (r > rows) return;
+  const int64_t v = rw.row[r];
+  const int64_t prev = r ? rw.row[r - 1] : 0;
+  bool bad = v < 0 || (u64)v > rw.n || prev > v;
+  if (ends && ((r == 0 && v != 0) || (r == rows && (u64)v != rw.n))) bad = true;
+  if (bad) {
+    err[0] = 1;
+    return;
+  }
+  if (r && prev >= 0 && (u64)(rw.bos_n + rw.eos_n) + rw.keep((u64)prev, (u64)v) > (u64)INT32_MAX) err[1] = 1;
+}
+
+// Element k of the scan: the length of emitted row k - 1.
+struct EInput {
+  Rows rw;
+  __host__ __device__ __forceinline__ u64 operator()(u64 k) const { return k ? rw.emit(k - 1) : 0ull; }
+};
+struct WInput {
+  Rows rw;
+  __host__ __device__ __forceinline__ u64 operator()(u64 r) const { return rw.emit(r); }
+};
+typedef hipcub::TransformInputIterator<u64, EInput, hipcub::CountingInputIterator<u64>> EIter;
+typedef hipcub::TransformInputIterator<u64, WInput, hipcub::CountingInputIterator<u64>> WIter;
+
+// First k in [lo, hi) with E[k] > v, or hi.
+__device__ __forceinline__ u64 upper_bound(const u64* __restrict__ E, u64 lo, u64 hi, u64 v) {
+  while (lo < hi) {
+    const u64 mid = lo + ((hi - lo) >> 1);
+    if (E[mid] <= v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// total = rows * W > 0, W >= every e_r.
+template <bool kAligned>
+__global__ __launch_bounds__(kThreads) void k_bat_pad(const int32_t* __restrict__ ids, Rows rw, u64 W, u64 total,
+                                                      int32_t pad_id, uint32_t pad_left, int32_t* __restrict__ out,
+                                                      int32_t* __restrict__ lengths, uint8_t* __restrict__ mask,
+                                                      uint32_t mask_aligned) {
+  const u64 g = (u64)blockIdx.x * kTile + (u64)threadIdx.x * kLane;
+  if (g >= total) return;
+  const int cnt = total - g < (u64)kLane ? (int)(total - g) : kLane;
+  u64 r = g / W, c = g - r * W;
+  u64 e = 0, src = 0, lead = 0;
+  bool fresh = true;
+  int32_t w[kLane] = {0, 0, 0, 0};
+  uint32_t mk = 0;
+#pragma unroll
+  for (int i = 0; i < kLane; ++i) {
+    if (i < cnt) {
+      if (fresh) {
+        rw.span(r, &e, &src);
+        lead = pad_left ? W - e : 0;
+        if (c == 0 && lengths) lengths[r] = (int32_t)e;
+        fresh = false;
+      }
+      int32_t v = pad_id;
+      if (c >= lead && c - lead < e) {
+        v = rw.id(ids, e, src, c - lead);
+        mk |= 1u << (8 * i);
+      }
+      w[i] = v;
+      if (++c == W) {
+        c = 0;
+        ++r;
+        fresh = true;
+      }
+    }
+  }
+  if (kAligned && cnt == kLane) {
+    *reinterpret_cast<int4*>(out + g) = make_int4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLane; ++i)
+      if (i < cnt) out[g + i] = w[i];
+  }
+  if (mask) {
+    if (mask_aligned && cnt == kLane) {
+      *reinterpret_cast<uint32_t*>(mask + g) = mk;
+    } else {
+#pragma unroll
+      for (int i = 0; i < kLane; ++i)
+        if (i < cnt) mask[g + i] = (uint8_t)(mk >> (8 * i));
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_bat_row_start(const u64* __restrict__ E, u64 rows, u64 base,
+                                                            int64_t* __restrict__ row_start) {
+  const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
+  if (r <= rows) row_start[r] = (int64_t)(base + E[r]);
+}
+
+// Positions [0, limit) of the call's stream (E[rows] = T; positions from T on are padding);
+// aligned: bit 0 out, bit 1 pos, bit 2 seg may take 16-byte stores.
+__global__ __launch_bounds__(kThreads) void k_bat_pack(const int32_t* __restrict__ ids, Rows rw, u64 rows,
+                                                       const u64* __restrict__ E, u64 limit, int32_t pad_id,
+                                                       u64 row_base, int32_t* __restrict__ out,
+                                                       int32_t* __restrict__ pos, int32_t* __restrict__ seg,
+                                                       uint32_t aligned) {
+  __shared__ int32_t s_rel[kStage + 1];  // E[k] - tile start, clamped to [-INT32_MAX, kTile]
+  __shared__ int32_t s_e[kStage];        // e_k (0 for the end entry k == rows)
+  __shared__ int64_t s_src[kStage];      // index in ids of the row's emitted id 0
+  __shared__ u64 s_k;
+  const int tid = threadIdx.x;
+  const u64 t0 = (u64)blockIdx.x * kTile;
+  const int tlen = (int)(limit - t0 < (u64)kTile ? limit - t0 : (u64)kTile);
+  if (tid == 0) {  // the last k with E[k] <= t0 (E[0] = 0); k == rows when the tile is all padding
+    const u64 ub = upper_bound(E, 0, rows + 1, t0);
+    s_k = ub ? ub - 1 : 0;
+  }
+  __syncthreads();
+  u64 ks = s_k;
+  const int p0 = tid * kLane;
+  int32_t w[kLane], wp[kLane], ws[kLane];
+#pragma unroll
+  for (int i = 0; i < kLane; ++i) {
+    w[i] = pad_id;
+    wp[i] = 0;
+    ws[i] = -1;
+  }
+  int cur = 0;
+  for (;;) {
+    // entries ks .. ks + m - 1 (k == rows: the end, no row), and the offset of entry ks + m
+    const int m = (int)(rows + 1 - ks < (u64)kStage ? rows + 1 - ks : (u64)kStage);
+    for (int i = tid; i <= m; i += kThreads) {
+      const u64 k = ks + (u64)i;
+      int64_t rel = kTile;
+      if (k <= rows) {
+        rel = (int64_t)(E[k] - t0);
+        rel = rel < -(int64_t)INT32_MAX ? -(int64_t)INT32_MAX : rel > kTile ? (int64_t)kTile : rel;
+      }
+      s_rel[i] = (int32_t)rel;
+      if (i < m) {
+        u64 e = 0, src = 0;
+        if (k < rows) rw.span(k, &e, &src);
+        s_e[i] = (int32_t)e;  // <= INT32_MAX (k_bat_rows)
+        s_src[i] = (int64_t)src;
+      }
+    }
+    __syncthreads();
+    // this round resolves the tile's positions [cur, lim): below the offset of the first entry not staged
+    const int lim = s_rel[m] < tlen ? s_rel[m] : tlen;
+    const int lo = p0 > cur ? p0 : cur, hi = p0 + kLane < lim ? p0 + kLane : lim;
+    if (lo < hi) {
+      int a = 0, b = m;  // first entry past position lo
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (s_rel[mid] <= lo) a = mid + 1; else b = mid;
+      }
+      int j = a - 1;  // >= 0: entry 0 starts at or before cur
+#pragma unroll
+      for (int i = 0; i < kLane; ++i) {
+        const int p = p0 + i;
+        if (p >= lo && p < hi && j >= 0) {
+          while (j + 1 < m && s_rel[j + 1] <= p) ++j;
+          const uint32_t off = (uint32_t)p - (uint32_t)s_rel[j];  // the position's index in its emitted row
+          const uint32_t e = (uint32_t)s_e[j];
+          if (off < e) {
+            w[i] = rw.id(ids, (u64)e, (u64)s_src[j], (u64)off);
+            wp[i] = (int32_t)off;
+            ws[i] = (int32_t)(row_base + ks + (u64)j);
+          }
+        }
+      }
+    }
+    if (lim >= tlen) break;
+    cur = lim;
+    ks += (u64)m;
+    __syncthreads();
+  }
+  if (p0 >= tlen) return;
+  const u64 g = t0 + (u64)p0;
+  const bool full = p0 + kLane <= tlen;
+  if (full && (aligned & 1u)) {
+    *reinterpret_cast<int4*>(out + g) = make_int4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLane; ++i)
+      if (p0 + i < tlen) out[g + i] = w[i];
+  }
+  if (pos) {
+    if (full && (aligned & 2u)) {
+      *reinterpret_cast<int4*>(pos + g) = make_int4(wp[0], wp[1], wp[2], wp[3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < kLane; ++i)
+        if (p0 + i < tlen) pos[g + i] = wp[i];
+    }
+  }
+  if (seg) {
+    if (full && (aligned & 4u)) {
+      *reinterpret_cast<int4*>(seg + g) = make_int4(ws[0], ws[1], ws[2], ws[3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < kLane; ++i)
+        if (p0 + i < tlen) seg[g + i] = ws[i];
+    }
+  }
+}
+
+template <class T>
+bool grow(T** p, size_t* have, size_t want, size_t elem = sizeof(T)) {
+  if (want <= *have) return true;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  if (hipMalloc(p, want * elem) != hipSuccess) return false;
+  *have = want;
+  return true;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Grids are one workgroup per tile / 256 rows.
+bool rows_fit(u64 rows) { return rows / kThreads < 0x7FFFFFFFull; }
+bool tiles_fit(u64 entries) { return entries / kTile < 0x7FFFFFFFull; }
+
+size_t piece_ids() {
+  size_t piece = EncodeDevice::kBatchPiece;
+  if (const char* e = std::getenv("SHREDWORD_BATCH_PIECE"))  // tests: small pieces
+    piece = std::min<size_t>(std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), 1), size_t(1) << 40);
+  return piece;
+}
+
+// The rows [r0, r1) of a piece: whole rows while it holds at most `piece` ids, `piece` rows and
+// 4 x piece output entries at per_row entries a row; at least one row, however long.
+size_t piece_end(const int64_t* row, size_t rows, size_t r0, size_t piece, size_t per_row) {
+  size_t r1 = r0 + 1;
+  while (r1 < rows && r1 - r0 < piece && (u64)(row[r1 + 1] - row[r0]) <= (u64)piece &&
+         (r1 + 1 - r0) * per_row <= 4 * piece)
+    ++r1;
+  return r1;
+}
+
+}  // namespace
+
+void EncodeDevice::free_batch() {
+  for (void* p : {(void*)bat_e_, bat_tmp_, (void*)bat_res_, (void*)bat_hids_, (void*)bat_hrow_, (void*)bat_hout_,
+                  (void*)bat_hmask_})
+    if (p) (void)hipFree(p);
+  if (bat_host_) (void)hipHostFree(bat_host_);
+  for (void* e : bat_ev_)
+    if (e) (void)hipEventDestroy((hipEvent_t)e);
+}
+
+// Scratch grown to the most rows seen: 8 B per row (E) and what the scan and the reduction ask for.
+bool EncodeDevice::reserve_batch(size_t rows) {
+  if (!bat_res_ && hipMalloc(&bat_res_, 32) != hipSuccess) return false;
+  if (!bat_host_ && hipHostMalloc(&bat_host_, 32, hipHostMallocDefault) != hipSuccess) return false;
+  for (void*& e : bat_ev_) {
+    if (e) continue;
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return false;
+    e = ev;
+  }
+  if (bat_e_ == nullptr || rows > bat_rows_) {
+    size_t have = bat_e_ ? bat_rows_ + 1 : 0;
+    if (!grow(&bat_e_, &have, rows + 1)) {
+      bat_rows_ = 0;
+      return false;
+    }
+    bat_rows_ = rows;
+  }
+  const Rows rw{nullptr, 0, kNoLimit, 0, 0, 0, 0, 0};
+  size_t scan = 0, red = 0;
+  if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}), bat_e_,
+                                       (u64)rows + 1) != hipSuccess)
+    return false;
+  if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}), bat_res_ + 2,
+                                (u64)std::max<size_t>(rows, 1)) != hipSuccess)
+    return false;
+  const size_t need = std::max<size_t>(std::max(scan, red), 16);
+  if (need > bat_tmp_bytes_) {
+    if (bat_tmp_) (void)hipFree(bat_tmp_);
+    bat_tmp_ = nullptr;
+    bat_tmp_bytes_ = 0;
+    if (hipMalloc(&bat_tmp_, need) != hipSuccess) return false;
+    bat_tmp_bytes_ = need;
+  }
+  return true;
+}
+
+int EncodeDevice::batch_lengths(const BatchCall& c, bool scan, void* stream, uint64_t* total, uint64_t* widest) {
+  hipStream_t st = (hipStream_t)stream;
+  const Rows rw = rows_of(c.o, c.row, c.n);
+  ENC_OK(hipMemsetAsync(bat_res_, 0, 32, st));
+  if (c.row) {
+    k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(rw, c.rows,
+                                                                                            c.ends ? 1 : 0, bat_res_);
+    ENC_OK(hipGetLastError());
+  } else if (rw.emit(0) > (u64)INT32_MAX) {
+    return -1;
+  }
+  size_t tmp = bat_tmp_bytes_;
+  if (scan) {
+    ENC_OK(hipcub::DeviceScan::InclusiveSum(bat_tmp_, tmp, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
+                                            bat_e_, c.rows + 1, st));
+    ENC_OK(hipMemcpyAsync(bat_host_, bat_e_ + c.rows, 8, hipMemcpyDeviceToHost, st));
+  } else if (c.rows) {
+    ENC_OK(hipcub::DeviceReduce::Max(bat_tmp_, tmp, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
+                                     bat_res_ + 2, c.rows, st));
+  }
+  ENC_OK(hipMemcpyAsync(bat_host_ + 1, bat_res_, 24, hipMemcpyDeviceToHost, st));
+  ENC_OK(hipStreamSynchronize(st));
+  if (bat_host_[1]) return -6;
+  if (bat_host_[2]) return -1;
+  *total = scan ? bat_host_[0] : 0;
+  *widest = bat_host_[3];
+  return 0;
+}
+
+int EncodeDevice::pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out,
+                             int32_t* lengths, uint8_t* mask, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const u64 total = c.rows * width;
+  if (!total) {  // width == 0: every e_r is 0 and no lane owns a column
+    if (lengths && c.rows) ENC_OK(hipMemsetAsync(lengths, 0, c.rows * 4, st));
+    return 0;
+  }
+  const Rows rw = rows_of(c.o, c.row, c.n);
+  const u64 tiles = (total + kTile - 1) / kTile;
+  (aligned16(out) ? k_bat_pad<true> : k_bat_pad<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
+      c.ids, rw, width, total, pad_id, pad_side ? 1u : 0u, out, lengths, mask,
+      (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? 1u : 0u);
+  ENC_OK(hipGetLastError());
+  return 0;
+}
+
+int EncodeDevice::pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out,
+                              int32_t* pos, int32_t* seg, int64_t* row_start, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (row_start) {
+    k_bat_row_start<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(bat_e_, c.rows,
+                                                                                                 c.base, row_start);
+    ENC_OK(hipGetLastError());
+  }
+  if (limit) {
+    const Rows rw = rows_of(c.o, c.row, c.n);
+    const u64 tiles = (limit + kTile - 1) / kTile;
+    const uint32_t al = (aligned16(out) ? 1u : 0u) | (aligned16(pos) ? 2u : 0u) | (aligned16(seg) ? 4u : 0u);
+    k_bat_pack<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(c.ids, rw, c.rows, bat_e_, limit, pad_id, c.row_base,
+                                                                 out, pos, seg, al);
+    ENC_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+int64_t EncodeDevice::pad(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                          size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths,
+                          uint8_t* mask, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  const u64 R = row_off ? rows : 1;
+  if (!rows_fit(R) || (width && R > (u64)INT64_MAX / width)) return -1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  if (!reserve_batch(R)) {
+    std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
+  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(bat_ev_);
+  const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
+  u64 total = 0, widest = 0;
+  ENC_OK(hipEventRecord(ev[0], st));
+  const int r = batch_lengths(c, false, st, &total, &widest);
+  if (r < 0) return r;
+  ENC_OK(hipEventRecord(ev[1], st));
+  float a = 0, b = 0;
+  if (out && width >= widest && cap >= R * width) {
+    if (!tiles_fit(R * width)) return -1;
+    ENC_OK(hipEventRecord(ev[2], st));
+    if (pad_expand(c, width, pad_id, pad_side, out, lengths, mask, st) < 0) return -1;
+    ENC_OK(hipEventRecord(ev[3], st));
+    ENC_OK(hipStreamSynchronize(st));
+    if (kernel_ms) ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
+  } else {
+    ENC_OK(hipStreamSynchronize(st));
+  }
+  if (kernel_ms) {
+    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+    *kernel_ms = (double)a + (double)b;
+  }
+  return (int64_t)widest;
+}
+
+int64_t EncodeDevice::pack(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                           size_t seq_len, int32_t pad_id, bool drop_last, int32_t* out, size_t cap, int32_t* pos,
+                           int32_t* seg, int64_t* row_start, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  const u64 R = row_off ? rows : 1;
+  if (!rows_fit(R)) return -1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  if (!reserve_batch(R)) {
+    std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
+  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(bat_ev_);
+  const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
+  u64 total = 0, widest = 0;
+  ENC_OK(hipEventRecord(ev[0], st));
+  const int r = batch_lengths(c, true, st, &total, &widest);
+  if (r < 0) return r;
+  ENC_OK(hipEventRecord(ev[1], st));
+  const u64 L = seq_len;
+  const u64 S = drop_last ? total / L : total / L + (total % L ? 1 : 0);
+  if (S > (u64)INT64_MAX / L) return -1;
+  float a = 0, b = 0;
+  if (out && cap >= S * L) {
+    if (!tiles_fit(S * L)) return -1;
+    ENC_OK(hipEventRecord(ev[2], st));
+    if (pack_expand(c, S * L, pad_id, out, pos, seg, row_start, st) < 0) return -1;
+    ENC_OK(hipEventRecord(ev[3], st));
+    ENC_OK(hipStreamSynchronize(st));
+    if (kernel_ms) ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
+  } else {
+    ENC_OK(hipStreamSynchronize(st));
+  }
+  if (kernel_ms) {
+    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+    *kernel_ms = (double)a + (double)b;
+  }
+  return (int64_t)S;
+}
+
+// Host rows in pieces of whole rows (piece_end).  A pad piece is a pad of its own rows into rows
+// [r0, r1) of out; the caller has validated row_off and width on the host, so no length pass runs.
+int EncodeDevice::pad_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                           size_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
+                           uint8_t* mask) {
+  const size_t R = row_off ? rows : 1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  const size_t piece = piece_ids();
+  hipStream_t st = (hipStream_t)stream_;
+  std::vector<int64_t> local;
+  for (size_t r0 = 0; r0 < R;) {
+    const size_t r1 = row_off ? piece_end(row_off, R, r0, piece, width) : 1;
+    const size_t m = r1 - r0;
+    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
+    const size_t cells = m * width;
+    if (!tiles_fit(cells) || !grow(&bat_hids_, &bat_hids_cap_, std::max<size_t>(len, 1)) ||
+        !grow(&bat_hrow_, &bat_hrow_cap_, m + 1, 2 * sizeof(int64_t)) ||
+        !grow(&bat_hout_, &bat_hout_cap_, std::max(cells, m), 3 * sizeof(int32_t)) ||
+        (mask && !grow(&bat_hmask_, &bat_hmask_cap_, std::max<size_t>(cells, 1)))) {
+      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
+      return -1;
+    }
+    if (len) ENC_OK(hipMemcpyAsync(bat_hids_, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    if (row_off) {
+      local.resize(m + 1);
+      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
+      ENC_OK(hipMemcpyAsync(bat_hrow_, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    int32_t* dlen = bat_hout_ + bat_hout_cap_;
+    const BatchCall c{bat_hids_, len, row_off ? bat_hrow_ : nullptr, m, false, o, 0, r0};
+    if (pad_expand(c, width, pad_id, pad_side, bat_hout_, lengths ? dlen : nullptr, mask ? bat_hmask_ : nullptr, st) < 0)
+      return -1;
+    if (cells) ENC_OK(hipMemcpyAsync(out + r0 * width, bat_hout_, cells * 4, hipMemcpyDeviceToHost, st));
+    if (lengths) ENC_OK(hipMemcpyAsync(lengths + r0, dlen, m * 4, hipMemcpyDeviceToHost, st));
+    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + r0 * width, bat_hmask_, cells, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    r0 = r1;
+  }
+  return 0;
+}
+
+// A pack piece writes its slice of the flat stream at the offset of its first row (BatchCall::base),
+// cut at out_len = S * seq_len; only the last piece runs on to out_len, which writes the pad tail.
+int EncodeDevice::pack_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                            uint64_t out_len, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg,
+                            int64_t* row_start) {
+  const size_t R = row_off ? rows : 1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  const size_t piece = piece_ids();
+  hipStream_t st = (hipStream_t)stream_;
+  std::vector<int64_t> local;
+  u64 done = 0;
+  if (row_start) row_start[0] = 0;
+  for (size_t r0 = 0; r0 < R;) {
+    const size_t r1 = row_off ? piece_end(row_off, R, r0, piece, 0) : 1;
+    const size_t m = r1 - r0;
+    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
+    if (!reserve_batch(m) || !grow(&bat_hids_, &bat_hids_cap_, std::max<size_t>(len, 1)) ||
+        !grow(&bat_hrow_, &bat_hrow_cap_, m + 1, 2 * sizeof(int64_t))) {
+      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
+      return -1;
+    }
+    if (len) ENC_OK(hipMemcpyAsync(bat_hids_, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    if (row_off) {
+      local.resize(m + 1);
+      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
+      ENC_OK(hipMemcpyAsync(bat_hrow_, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    const BatchCall c{bat_hids_, len, row_off ? bat_hrow_ : nullptr, m, false, o, done, r0};
+    u64 total = 0, widest = 0;
+    if (batch_lengths(c, true, st, &total, &widest) < 0) return -1;  // (the caller has validated row_off)
+    const u64 end = r1 == R ? out_len : std::min(done + total, out_len);
+    const u64 limit = end > done ? end - done : 0;
+    if (!tiles_fit(limit) || !grow(&bat_hout_, &bat_hout_cap_, std::max<size_t>((size_t)limit, 1), 3 * sizeof(int32_t))) {
+      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu entries)\n", (size_t)limit);
+      return -1;
+    }
+    int32_t* dpos = bat_hout_ + bat_hout_cap_;
+    int32_t* dseg = dpos + bat_hout_cap_;
+    int64_t* dstart = bat_hrow_ + bat_hrow_cap_;
+    if (pack_expand(c, limit, pad_id, bat_hout_, pos ? dpos : nullptr, seg ? dseg : nullptr,
+                    row_start ? dstart : nullptr, st) < 0)
+      return -1;
+    if (limit) {
+      ENC_OK(hipMemcpyAsync(out + done, bat_hout_, limit * 4, hipMemcpyDeviceToHost, st));
+      if (pos) ENC_OK(hipMemcpyAsync(pos + done, dpos, limit * 4, hipMemcpyDeviceToHost, st));
+      if (seg) ENC_OK(hipMemcpyAsync(seg + done, dseg, limit * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (row_start) ENC_OK(hipMemcpyAsync(row_start + r0 + 1, dstart + 1, m * 8, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    done += total;
+    r0 = r1;
+  }
+  return 0;
+}
+
+}  // namespace shred

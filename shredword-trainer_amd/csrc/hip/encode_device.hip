@@ -592,6 +592,7 @@ EncodeDevice::~EncodeDevice() {
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   free_spans();
   free_decode();
+  free_batch();
   for (void* p : {(void*)table_, (void*)byte_map_, (void*)misc_, (void*)pad_, (void*)rank_, (void*)tcnt_,
                   (void*)bcnt_, (void*)dtext_, (void*)dout_, (void*)cslot_, scan_tmp_})
     if (p) (void)hipFree(p);

@@ -298,4 +298,99 @@ int64_t shred_decode_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const
   return r < 0 ? r : (int64_t)need;
 }
 
+namespace {
+// What the four batch calls refuse before any work (0 or -1), and their options.
+int batch_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+               const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side,
+               shred::EncodeDevice::BatchOpts* o) {
+  if (!enc || (n && !ids) || (!row_off && rows) || trunc_side < 0 || trunc_side > 1) return -1;
+  const size_t add = (bos ? 1 : 0) + (eos ? 1 : 0);
+  if (max_len && max_len < add) return -1;
+  *o = shred::EncodeDevice::BatchOpts{bos != nullptr, eos != nullptr, bos ? *bos : 0, eos ? *eos : 0,
+                                      (uint64_t)max_len, trunc_side};
+  return 0;
+}
+
+// The length pass of host rows: 0 with T = sum e_r and the largest e_r, -6 for a bad row_off, -1
+// for an e_r past int32.
+int batch_host_lengths(size_t n, const int64_t* row_off, size_t rows, const shred::EncodeDevice::BatchOpts& o,
+                       uint64_t* total, uint64_t* widest) {
+  const uint64_t add = (o.has_bos ? 1 : 0) + (o.has_eos ? 1 : 0);
+  const uint64_t keep_max = o.max_len ? o.max_len - add : ~0ull;
+  *total = *widest = 0;
+  if (row_off) {
+    if (row_off[0] != 0 || row_off[rows] < 0 || (uint64_t)row_off[rows] != n) return -6;
+    for (size_t r = 0; r < rows; ++r)
+      if (row_off[r] > row_off[r + 1]) return -6;
+  }
+  const size_t R = row_off ? rows : 1;
+  for (size_t r = 0; r < R; ++r) {
+    const uint64_t len = row_off ? (uint64_t)(row_off[r + 1] - row_off[r]) : (uint64_t)n;
+    const uint64_t e = add + std::min(len, keep_max);
+    if (e > (uint64_t)INT32_MAX) return -1;
+    *total += e;
+    *widest = std::max(*widest, e);
+  }
+  return 0;
+}
+}  // namespace
+
+int64_t shred_pad_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t width,
+                         int32_t pad_id, int pad_side, void* out, size_t cap, void* lengths, void* mask,
+                         void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::BatchOpts o;
+  if (batch_args(enc, ids, n, row_off, rows, bos, eos, max_len, trunc_side, &o) || pad_side < 0 || pad_side > 1)
+    return -1;
+  return enc->dev->pad((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, width, pad_id, pad_side,
+                       (int32_t*)out, cap, (int32_t*)lengths, (uint8_t*)mask, stream, kernel_ms);
+}
+
+int64_t shred_pack_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                          const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t seq_len,
+                          int32_t pad_id, int drop_last, void* out, size_t cap, void* pos, void* seg,
+                          void* row_start, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::BatchOpts o;
+  if (batch_args(enc, ids, n, row_off, rows, bos, eos, max_len, trunc_side, &o) || seq_len < 1 ||
+      rows > (size_t)INT32_MAX)
+    return -1;
+  return enc->dev->pack((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, seq_len, pad_id, drop_last != 0,
+                        (int32_t*)out, cap, (int32_t*)pos, (int32_t*)seg, (int64_t*)row_start, stream, kernel_ms);
+}
+
+int64_t shred_pad_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t width,
+                       int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask) {
+  shred::EncodeDevice::BatchOpts o;
+  if (batch_args(enc, ids, n, row_off, rows, bos, eos, max_len, trunc_side, &o) || pad_side < 0 || pad_side > 1)
+    return -1;
+  uint64_t total = 0, widest = 0;
+  if (const int r = batch_host_lengths(n, row_off, rows, o, &total, &widest)) return r;
+  const uint64_t R = row_off ? rows : 1;
+  if (width && R > (uint64_t)INT64_MAX / width) return -1;
+  if (!out || width < widest || cap < R * width) return (int64_t)widest;
+  const int r = enc->dev->pad_host(ids, n, row_off, rows, o, width, pad_id, pad_side, out, lengths, mask);
+  return r < 0 ? r : (int64_t)widest;
+}
+
+int64_t shred_pack_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                        const int32_t* bos, const int32_t* eos, size_t max_len, int trunc_side, size_t seq_len,
+                        int32_t pad_id, int drop_last, int32_t* out, size_t cap, int32_t* pos, int32_t* seg,
+                        int64_t* row_start) {
+  shred::EncodeDevice::BatchOpts o;
+  if (batch_args(enc, ids, n, row_off, rows, bos, eos, max_len, trunc_side, &o) || seq_len < 1 ||
+      rows > (size_t)INT32_MAX)
+    return -1;
+  uint64_t total = 0, widest = 0;
+  if (const int r = batch_host_lengths(n, row_off, rows, o, &total, &widest)) return r;
+  const uint64_t L = seq_len;
+  const uint64_t S = drop_last ? total / L : total / L + (total % L ? 1 : 0);
+  if (S > (uint64_t)INT64_MAX / L) return -1;
+  if (!out || cap < S * L) return (int64_t)S;
+  const int r = enc->dev->pack_host(ids, n, row_off, rows, o, S * L, pad_id, out, pos, seg, row_start);
+  return r < 0 ? r : (int64_t)S;
+}
+
 }  // extern "C"

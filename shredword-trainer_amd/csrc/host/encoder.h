@@ -72,6 +72,29 @@ class EncodeDevice {
                       int64_t* byte_off, int sep, const uint8_t* unk, int unk_len,
                       const std::vector<int32_t>& first, const std::vector<int32_t>& second);
 
+  // ---- rows of ids to padded batches and packed sequences (batch_device.hip; arguments and
+  // results as include/shredword_encode.h defines them for shred_pad_* / shred_pack_*).  The
+  // callers have checked the arguments' ranges.  pad / pack take device buffers and return the
+  // width needed / S, -1 or -6.  pad_host / pack_host take host buffers whose row_off, width, cap
+  // and S * seq_len = out_len the caller has checked on the host; they return 0 or -1.
+  struct BatchOpts {
+    bool has_bos, has_eos;
+    int32_t bos, eos;
+    uint64_t max_len;  // 0: unlimited, else >= has_bos + has_eos
+    int trunc_side;
+  };
+  int64_t pad(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o, size_t width,
+              int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask, void* stream,
+              double* kernel_ms);
+  int64_t pack(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o, size_t seq_len,
+               int32_t pad_id, bool drop_last, int32_t* out, size_t cap, int32_t* pos, int32_t* seg,
+               int64_t* row_start, void* stream, double* kernel_ms);
+  static constexpr size_t kBatchPiece = size_t(1) << 24;  // ids per piece of pad_host / pack_host
+  int pad_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o, size_t width,
+               int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths, uint8_t* mask);
+  int pack_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                uint64_t out_len, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg, int64_t* row_start);
+
  private:
   EncodeDevice() = default;
   bool reserve(size_t n, std::string* why);
@@ -155,6 +178,33 @@ class EncodeDevice {
   int32_t* dec_hids_ = nullptr;
   int64_t* dec_hrow_ = nullptr;      // 2 x dec_hrow_cap_: row offsets, then byte offsets
   uint8_t* dec_hout_ = nullptr;
+
+  // batch passes (batch_device.hip): allocated on the first pad / pack call, never by the encode
+  // or decode calls
+  struct BatchCall;  // one call's (or piece's) rows, as the kernels take them
+  bool reserve_batch(size_t rows);
+  // Row checks (when c.row), E into bat_e_ (when scan) and max e_r over c's rows: 0, -1, -6.
+  int batch_lengths(const BatchCall& c, bool scan, void* stream, uint64_t* total, uint64_t* widest);
+  int pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
+                 uint8_t* mask, void* stream);
+  // Stream positions [c.base, c.base + limit) into out / pos / seg (which point at position
+  // c.base), pad_id from the rows' end on; row_start[r] = c.base + E[r] for the call's rows.
+  int pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out, int32_t* pos,
+                  int32_t* seg, int64_t* row_start, void* stream);
+  void free_batch();  // called by the destructor
+  size_t bat_rows_ = 0;              // bat_e_ holds bat_rows_ + 1 entries
+  uint64_t* bat_e_ = nullptr;        // E[r]: stream offset of emitted row r; E[rows] = T
+  void* bat_tmp_ = nullptr;          // hipCUB scan / reduce scratch
+  size_t bat_tmp_bytes_ = 0;
+  uint64_t* bat_res_ = nullptr;      // device: [0] bad row_off, [1] an e_r past int32, [2] max e_r
+  uint64_t* bat_host_ = nullptr;     // pinned: T, then the three words of bat_res_
+  void* bat_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  // host-path staging: ids, row offsets, a piece's int32 outputs, its mask
+  size_t bat_hids_cap_ = 0, bat_hrow_cap_ = 0, bat_hout_cap_ = 0, bat_hmask_cap_ = 0;
+  int32_t* bat_hids_ = nullptr;
+  int64_t* bat_hrow_ = nullptr;      // 2 x bat_hrow_cap_: row offsets, then row_start
+  int32_t* bat_hout_ = nullptr;      // 3 x bat_hout_cap_: out, then pos / lengths, then seg
+  uint8_t* bat_hmask_ = nullptr;
 };
 
 }  // namespace shred

@@ -170,3 +170,16 @@ lib.shred_decode_device.restype = c_int64
 lib.shred_decode_rows.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                   c_int, c_char_p, c_int]
 lib.shred_decode_rows.restype = c_int64
+# rows of ids to padded batches and packed sequences
+_batch_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_int32), POINTER(c_int32), c_size_t, c_int]
+lib.shred_pad_device.argtypes = _batch_rows + [c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                               c_void_p, POINTER(c_double)]
+lib.shred_pad_device.restype = c_int64
+lib.shred_pad_rows.argtypes = _batch_rows + [c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+lib.shred_pad_rows.restype = c_int64
+lib.shred_pack_device.argtypes = _batch_rows + [c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, POINTER(c_double)]
+lib.shred_pack_device.restype = c_int64
+lib.shred_pack_rows.argtypes = _batch_rows + [c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                              c_void_p]
+lib.shred_pack_rows.restype = c_int64

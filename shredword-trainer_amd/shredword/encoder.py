@@ -22,6 +22,10 @@ MAX_UNK = 8      # SHRED_DECODE_MAX_UNK
 # the strict-mode id check (kChunk)
 DECODE_TILE = 4096
 DECODE_CHUNK = 4096
+# batch_device.hip: output entries per workgroup of the pad and pack kernels (kTile), rows the pack
+# kernel stages in LDS per round (kStage)
+BATCH_TILE = 1024
+BATCH_STAGE = 512
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -259,6 +263,180 @@ class BPEEncoder:
         r = self._check_decode(lib.shred_decode_device(*args, out.data_ptr(), need, boff.data_ptr(), s, u, ul, st,
                                                        ctypes.byref(ms1)))
         return out[:r], boff, ms1.value
+
+    # ---- rows of ids to padded batches and packed sequences (include/shredword_encode.h) ----------
+
+    @staticmethod
+    def _int32(name, v):
+        v = int(v)
+        if not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError(f"{name} must fit an int32")
+        return v
+
+    @classmethod
+    def _batch_args(cls, bos, eos, max_len, truncate, pad_id):
+        """-> (bos pointer, eos pointer, max_len, trunc_side, pad_id) as the C ABI takes them."""
+        if truncate not in ("left", "right"):
+            raise ValueError('truncate must be "left" or "right"')
+        add = (bos is not None) + (eos is not None)
+        ml = 0 if max_len is None else int(max_len)
+        if ml < 0 or (ml and ml < add):
+            raise ValueError(f"max_len must leave room for the {add} added ids")
+        ptr = lambda name, v: None if v is None else ctypes.byref(ctypes.c_int32(cls._int32(name, v)))
+        return ptr("bos", bos), ptr("eos", eos), ml, int(truncate == "left"), cls._int32("pad_id", pad_id)
+
+    @staticmethod
+    def _check_batch(r: int) -> int:
+        if r == -6:
+            raise ValueError("row_offsets must be 0 = row_offsets[0] <= ... <= row_offsets[rows] = len(ids)")
+        if r < 0:
+            raise RuntimeError(f"batch call failed (code {r})")
+        return r
+
+    @staticmethod
+    def _host_rows(ids, row_offsets):
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        row = None if row_offsets is None else np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+        if row is not None and row.size == 0:
+            raise ValueError("row_offsets must hold rows + 1 entries")
+        return a, row, (1 if row is None else row.size - 1)
+
+    def _device_rows(self, ids, row_offsets):
+        import torch
+        for name, t, dt in (("ids", ids, torch.int32), ("row_offsets", row_offsets, torch.int64)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} CUDA tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the encoder on cuda:{self.device}")
+        if row_offsets is not None and row_offsets.numel() == 0:
+            raise ValueError("row_offsets must hold rows + 1 entries")
+        return 1 if row_offsets is None else row_offsets.numel() - 1
+
+    def pad_rows(self, ids, row_offsets=None, *, bos=None, eos=None, max_len=None, truncate="right", pad_id=0,
+                 pad="right", width=None, mask=False):
+        """-> (batch, lengths) or (batch, lengths, mask): the padded batch of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (the line_offsets format of encode_lines; None: one row).
+        Each row becomes [bos] + its ids + [eos], cut to max_len ids in all (None or 0: no limit) by
+        dropping ids on the `truncate` side, and padded with pad_id on the `pad` side to `width`
+        (None: the longest emitted row).  batch: int32 [rows, width]; lengths: int32 [rows], the
+        emitted lengths; mask: uint8 [rows, width], 1 on tokens.  Built on the GPU."""
+        if pad not in ("left", "right"):
+            raise ValueError('pad must be "left" or "right"')
+        b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
+        a, row, R = self._host_rows(ids, row_offsets)
+        args = (self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data,
+                0 if row is None else R, b, e, ml, ts)
+        ps = int(pad == "left")
+        if width is None:
+            width = self._check_batch(lib.shred_pad_rows(*args, 0, pid, ps, None, 0, None, None))
+        W = int(width)
+        if W < 0:
+            raise ValueError("width must not be negative")
+        out = np.empty(max(1, R * W), dtype=np.int32)
+        lengths = np.empty(max(1, R), dtype=np.int32)
+        m = np.empty(max(1, R * W), dtype=np.uint8) if mask else None
+        need = self._check_batch(lib.shred_pad_rows(*args, W, pid, ps, out.ctypes.data, R * W, lengths.ctypes.data,
+                                                    None if m is None else m.ctypes.data))
+        if need > W:
+            raise ValueError(f"width {W} is smaller than the longest row ({need} ids)")
+        res = (out[:R * W].reshape(R, W), lengths[:R])
+        return res + (m[:R * W].reshape(R, W),) if mask else res
+
+    def pack_rows(self, ids, row_offsets=None, *, seq_len, bos=None, eos=None, max_len=None, truncate="right",
+                  pad_id=0, drop_last=False, positions=False, segments=False):
+        """-> (seqs, row_start[, positions][, segments]).  The rows, each emitted as in pad_rows, are
+        concatenated into one stream and cut into sequences of seq_len: seqs is int32 [S, seq_len], the
+        last sequence filled with pad_id, or dropped with drop_last when it is not full.  row_start
+        (int64, rows + 1): the stream offset of every emitted row, row_start[rows] the stream's
+        length.  positions / segments (int32 [S, seq_len]): each token's index inside its emitted
+        row, and its row; padding gets 0 and -1.  Built on the GPU."""
+        if int(seq_len) < 1:
+            raise ValueError("seq_len must be at least 1")
+        L = int(seq_len)
+        b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
+        a, row, R = self._host_rows(ids, row_offsets)
+        args = (self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data,
+                0 if row is None else R, b, e, ml, ts, L, pid, int(bool(drop_last)))
+        S = self._check_batch(lib.shred_pack_rows(*args, None, 0, None, None, None))
+        out = np.empty(max(1, S * L), dtype=np.int32)
+        pos = np.empty(max(1, S * L), dtype=np.int32) if positions else None
+        seg = np.empty(max(1, S * L), dtype=np.int32) if segments else None
+        start = np.empty(R + 1, dtype=np.int64)
+        self._check_batch(lib.shred_pack_rows(*args, out.ctypes.data, S * L, None if pos is None else pos.ctypes.data,
+                                              None if seg is None else seg.ctypes.data, start.ctypes.data))
+        res = (out[:S * L].reshape(S, L), start)
+        res += (pos[:S * L].reshape(S, L),) if positions else ()
+        return res + ((seg[:S * L].reshape(S, L),) if segments else ())
+
+    def pad_device(self, ids, row_offsets=None, *, bos=None, eos=None, max_len=None, truncate="right", pad_id=0,
+                   pad="right", width=None, mask=False, stream=None):
+        """pad_rows on device tensors: ids a 1-D int32 torch tensor on the encoder's GPU, row_offsets None
+        or a 1-D int64 tensor there (the views encode_spans_device returns fit) -> (batch, lengths[,
+        mask], device milliseconds of the batch passes), tensors on the same device."""
+        import torch
+        if pad not in ("left", "right"):
+            raise ValueError('pad must be "left" or "right"')
+        b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
+        R = self._device_rows(ids, row_offsets)
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
+                0 if row_offsets is None else R, b, e, ml, ts)
+        ps = int(pad == "left")
+        ms = ctypes.c_double()
+        if width is None:
+            width = self._check_batch(lib.shred_pad_device(*args, 0, pid, ps, None, 0, None, None, st, None))
+        W = int(width)
+        if W < 0:
+            raise ValueError("width must not be negative")
+        out = torch.empty(max(1, R * W), dtype=torch.int32, device=ids.device)
+        lengths = torch.empty(max(1, R), dtype=torch.int32, device=ids.device)
+        m = torch.empty(max(1, R * W), dtype=torch.uint8, device=ids.device) if mask else None
+        need = self._check_batch(lib.shred_pad_device(*args, W, pid, ps, out.data_ptr(), R * W, lengths.data_ptr(),
+                                                      None if m is None else m.data_ptr(), st, ctypes.byref(ms)))
+        if need > W:
+            raise ValueError(f"width {W} is smaller than the longest row ({need} ids)")
+        res = (out[:R * W].view(R, W), lengths[:R])
+        return res + ((m[:R * W].view(R, W),) if mask else ()) + (ms.value,)
+
+    def pack_device(self, ids, row_offsets=None, *, seq_len, bos=None, eos=None, max_len=None, truncate="right",
+                    pad_id=0, drop_last=False, positions=False, segments=False, stream=None):
+        """pack_rows on device tensors (as pad_device takes them) -> (seqs, row_start[, positions][,
+        segments], device milliseconds of the batch passes)."""
+        import torch
+        if int(seq_len) < 1:
+            raise ValueError("seq_len must be at least 1")
+        L = int(seq_len)
+        b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
+        R = self._device_rows(ids, row_offsets)
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
+                0 if row_offsets is None else R, b, e, ml, ts, L, pid, int(bool(drop_last)))
+        ms = ctypes.c_double()
+        S = self._check_batch(lib.shred_pack_device(*args, None, 0, None, None, None, st, None))
+        new = lambda dt, k: torch.empty(max(1, k), dtype=dt, device=ids.device)
+        out = new(torch.int32, S * L)
+        pos = new(torch.int32, S * L) if positions else None
+        seg = new(torch.int32, S * L) if segments else None
+        start = new(torch.int64, R + 1)
+        self._check_batch(lib.shred_pack_device(*args, out.data_ptr(), S * L, None if pos is None else pos.data_ptr(),
+                                                None if seg is None else seg.data_ptr(), start.data_ptr(), st,
+                                                ctypes.byref(ms)))
+        res = (out[:S * L].view(S, L), start)
+        res += (pos[:S * L].view(S, L),) if positions else ()
+        return res + ((seg[:S * L].view(S, L),) if segments else ()) + (ms.value,)
+
+    def encode_padded(self, text, **kw):
+        """encode_lines, then pad_rows(**kw): one row of the batch per '\\n' line of the text."""
+        ids, line = self.encode_lines(text)
+        return self.pad_rows(ids, line, **kw)
+
+    def encode_packed(self, text, **kw):
+        """encode_lines, then pack_rows(**kw): every '\\n' line of the text is one row of the stream."""
+        ids, line = self.encode_lines(text)
+        return self.pack_rows(ids, line, **kw)
 
     def destroy(self):
         if getattr(self, "enc", None):

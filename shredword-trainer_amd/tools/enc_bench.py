@@ -1,8 +1,13 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch]   (SHREDWORD_LIB picks the build)
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
-GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison."""
+GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
+trailing `batch`, the decode leg and then pad_device (rows cut to 1024 ids, with the mask) and
+pack_device (an eos per row, sequences of 2048, positions and segments) on the corpus's ids and line
+offsets: device ms and effective GB/s by the traffic model of batch_device.hip, and the torch
+composition (torch.full, an index from repeat_interleave of the lengths, a scatter) on the same
+tensors, timed with device events in the same process after a warm-up."""
 import os
 import subprocess
 import sys
@@ -27,7 +32,8 @@ if mode == "prepare":
     t.destroy()
 else:
     args = sys.argv[3:]
-    spans, decode = args[-1] == "spans", args[-1] == "decode"
+    spans, batch = args[-1] == "spans", args[-1] == "batch"
+    decode = batch or args[-1] == "decode"
     if spans or decode:
         args = args[:-1]
     d = args[0]
@@ -68,4 +74,77 @@ else:
         host.sort()
         print("host shred_decode (sizing + copy, wall): ms", host[len(host) // 2], "GB/s",
               len(want) / host[len(host) // 2] / 1e6, "min", host[0], "max", host[-1], flush=True)
+    if batch:
+        reps = max(reps, 5)
+        R, n, W, L = line.numel() - 1, ids.numel(), 1024, 2048
+
+        def timed(fn):
+            """median / min / max device ms of fn() over reps runs, after two warm-up runs"""
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            ms.sort()
+            return ms[len(ms) // 2], ms[0], ms[-1]
+
+        def torch_rows(lens, width):
+            """(row, column, source index) of every kept id: the index built from repeat_interleave"""
+            total = int(lens.sum().item())
+            row = torch.repeat_interleave(torch.arange(R, device="cuda"), lens, output_size=total)
+            col = torch.arange(total, device="cuda") - torch.repeat_interleave(lens.cumsum(0) - lens, lens,
+                                                                              output_size=total)
+            return row, col, torch.repeat_interleave(line[:-1], lens, output_size=total) + col
+
+        def torch_pad():
+            lens = (line[1:] - line[:-1]).clamp(max=W)
+            out = torch.full((R, W), -1, dtype=torch.int32, device="cuda")
+            mask = torch.zeros((R, W), dtype=torch.uint8, device="cuda")
+            row, col, src = torch_rows(lens, W)
+            out[row, col] = ids[src]
+            mask[row, col] = 1
+            return out, lens.to(torch.int32), mask
+
+        def torch_pack():
+            lens = line[1:] - line[:-1]
+            e = lens + 1
+            start = torch.cat([e.new_zeros(1), e.cumsum(0)])
+            T = int(start[-1].item())
+            S = -(-T // L)
+            out = torch.full((S * L,), -1, dtype=torch.int32, device="cuda")
+            pos = torch.zeros(S * L, dtype=torch.int32, device="cuda")
+            seg = torch.full((S * L,), -1, dtype=torch.int32, device="cuda")
+            row, col, src = torch_rows(lens, 0)
+            out[start[:-1][row] + col] = ids[src]
+            out[start[1:] - 1] = 0  # the eos of every row
+            seg[:T] = torch.repeat_interleave(torch.arange(R, device="cuda", dtype=torch.int32), e, output_size=T)
+            pos[:T] = (torch.arange(T, device="cuda") - torch.repeat_interleave(start[:-1], e, output_size=T)).int()
+            return out.view(S, L), start, pos.view(S, L), seg.view(S, L)
+
+        pad_kw = dict(max_len=W, width=W, pad_id=-1, mask=True)
+        pack_kw = dict(seq_len=L, eos=0, pad_id=-1, positions=True, segments=True)
+        ours = enc.pad_device(ids, line, **pad_kw)  # first call: allocates the batch scratch
+        assert all(torch.equal(a, b) for a, b in zip(ours[:3], torch_pad()))
+        ms = sorted(enc.pad_device(ids, line, **pad_kw)[3] for _ in range(reps))
+        fill = ours[1].sum().item() / (R * W)
+        nbytes = R * W * (4 + 4 * fill + 1) + 16 * R
+        t, c = timed(torch_pad), timed(lambda: enc.pad_device(ids, line, **pad_kw))
+        print("pad: rows", R, "width", W, "fill", fill, "ms", ms[len(ms) // 2], "GB/s", nbytes / ms[len(ms) // 2] / 1e6,
+              "of 8 TB/s", nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0], "max", ms[-1],
+              "| whole call (sizing call, allocation, passes) ms", c[0],
+              "| torch ms", t[0], "min", t[1], "max", t[2], flush=True)
+        ours = enc.pack_device(ids, line, **pack_kw)
+        assert all(torch.equal(a, b) for a, b in zip(ours[:4], torch_pack()))
+        ms = sorted(enc.pack_device(ids, line, **pack_kw)[4] for _ in range(reps))
+        nbytes = ours[0].numel() * 16 + 16 * R
+        t, c = timed(torch_pack), timed(lambda: enc.pack_device(ids, line, **pack_kw))
+        print("pack: rows", R, "ids", n, "sequences", ours[0].shape[0], "ms", ms[len(ms) // 2], "GB/s",
+              nbytes / ms[len(ms) // 2] / 1e6, "of 8 TB/s", nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0],
+              "max", ms[-1], "| whole call (sizing call, allocation, passes) ms", c[0],
+              "| torch ms", t[0], "min", t[1], "max", t[2], flush=True)
     enc.destroy()
