@@ -60,7 +60,8 @@ int64_t shred_encode_device(ShredEncoder* enc, const void* text, size_t n, void*
                             void* stream, double* kernel_ms);
 
 /* Concatenates the bytes of n token ids into out (cap bytes).  Returns the byte count needed
- * (nothing is written past cap), or -1 for an id outside [0, 256 + num_merges).  Host only. */
+ * (nothing is written past cap), or -1 for an id outside [0, 256 + num_merges + K), K the number
+ * of registered special tokens (below).  Host only. */
 int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint8_t* out, size_t cap);
 
 /* ---- token byte offsets and per-line id offsets ("offset mapping", dataset rows) ----------
@@ -84,8 +85,9 @@ int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint
  * spans call and freed with the encoder, so shred_encode's footprint is unchanged.
  */
 
-/* 256 + num_merges source-byte lengths (ids < 256: 1; saturating at INT32_MAX).  Returns 0, or -1
- * when cap is smaller than 256 + num_merges.  Host only. */
+/* 256 + num_merges source-byte lengths (ids < 256: 1; saturating at INT32_MAX), then those of the
+ * K registered special tokens (below).  Returns 0, or -1 when cap is smaller than 256 + num_merges
+ * + K.  Host only. */
 int shred_encoder_token_lengths(const ShredEncoder* enc, int32_t* out, size_t cap);
 
 /* shred_encode plus, optionally, starts (NULL or cap int64) and line_off (NULL, or line_cap >=
@@ -102,6 +104,60 @@ int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n,
                                   void* starts, void* line_off, size_t line_cap, size_t* num_lines,
                                   void* stream, double* kernel_ms);
 
+/* ---- special tokens matched in the text ----------------------------------------------------------
+ *
+ * An encoder holds an ordered list of K special tokens (control tokens such as "<|endoftext|>"),
+ * each a byte string b_i.  Special i has id 256 + num_merges + i: the specials follow the merges
+ * in the vocabulary, in the order given.  0 <= K <= SHRED_SPECIAL_MAX, 1 <= len(b_i) <=
+ * SHRED_SPECIAL_MAX_LEN, all b_i distinct, and no b_i holds a delimiter byte ("\t\r\n "), so a
+ * special always lies inside one word, never spans a line, and covers len(b_i) source bytes.
+ *
+ * Only the two shred_encode_special calls match them; every other encode call never does, whether
+ * specials are registered or not (text from an untrusted source cannot inject control tokens
+ * unless the caller asks).  Matching, within each maximal run of non-delimiter bytes, from the
+ * run's first byte p on: if one or more specials equal text[p : p + len] and fit inside the run,
+ * the longest is taken, its id is emitted and the scan continues at p + len; otherwise at p + 1
+ * (leftmost, then longest, no overlap).  What remains of the run on either side of a match is
+ * split into words as if the match were a delimiter, and those words are encoded as shred_encode
+ * encodes them: no merge reaches across a special.  The word limit applies to the run before it
+ * is cut: a run longer than SHRED_ENCODE_MAX_WORD fails the call with -3.
+ *
+ * starts[k] of a special is its match position, and the ids still tile the text's non-delimiter
+ * bytes; lines and line_off are defined as above.  A special is a word of its own: token k begins
+ * a word iff k == 0, or ids[k] or ids[k-1] is a special, or starts[k] != starts[k-1] +
+ * len(ids[k-1]).  shred_encoder_token_lengths then holds 256 + num_merges + K entries.
+ *
+ * The decode calls below turn a special's id back into b_i (strict and unk mode alike); the
+ * specials' bytes count towards SHRED_DECODE_MAX_VOCAB_BYTES.  The batch calls never look ids up.
+ *
+ * The passes run on the GPU around the encode.  Their scratch (5 B per text byte for the copy of
+ * the text with the matches blanked and its word ids, 12 B per 32 text bytes of match counts, 8 B
+ * per id, 12 B per match, the table of the specials) is allocated on the first special call and
+ * freed with the encoder, so the other calls' footprints are unchanged.  A call that finds no
+ * match costs one scan of the text on top of shred_encode_spans.
+ */
+#define SHRED_SPECIAL_MAX 256
+#define SHRED_SPECIAL_MAX_LEN 64
+
+/* Replaces the encoder's specials: special i is bytes[offsets[i] : offsets[i+1]] (K + 1 offsets);
+ * K == 0 clears the set (bytes and offsets may then be NULL).  Returns 0, or -1 when a limit above
+ * is violated; the previous set then stays in place. */
+int shred_encoder_set_specials(ShredEncoder* enc, const uint8_t* bytes, const size_t* offsets, size_t K);
+
+size_t shred_encoder_num_specials(const ShredEncoder* enc);
+
+/* shred_encode_spans with the registered specials matched: the same arguments, NULL rules and
+ * return values, and the same staging in pieces (a special never straddles two pieces).  With
+ * K == 0 it returns exactly what shred_encode_spans returns. */
+int64_t shred_encode_special(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap,
+                             int64_t* starts, int64_t* line_off, size_t line_cap, size_t* num_lines);
+
+/* The same on device buffers, as shred_encode_spans_device; kernel_ms (NULL or 3 doubles): [0] the
+ * encode passes, [1] the span passes, [2] the special passes. */
+int64_t shred_encode_special_device(ShredEncoder* enc, const void* text, size_t n, void* out, size_t cap,
+                                    void* starts, void* line_off, size_t line_cap, size_t* num_lines,
+                                    void* stream, double* kernel_ms);
+
 /* ---- ids back to bytes on the GPU, per row ---------------------------------------------------
  *
  *   ids        n int32.
@@ -111,7 +167,8 @@ int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n,
  *   sep        -1 for none, or a byte 0..255 written after every row, the last and empty rows
  *              included (with row_off == NULL one separator ends the single row).  line_off from
  *              shred_encode_spans with sep = '\n' gives one '\n'-terminated line per row.
- *   unk        unk_len == -1 is strict: an id outside [0, 256 + num_merges) fails the call with
+ *   unk        the vocabulary is [0, 256 + num_merges + K) with K registered special tokens.
+ *              unk_len == -1 is strict: an id outside the vocabulary fails the call with
  *              -1, as shred_decode does.  0 <= unk_len <= SHRED_DECODE_MAX_UNK: each such id
  *              decodes to these unk_len bytes (0 drops it).
  *   byte_off   NULL, or rows + 1 int64 (1 + 1 when row_off is NULL): byte_off[r] is the offset in

@@ -282,6 +282,10 @@ bool EncodeDevice::reserve_decode(size_t n, size_t rows, const std::vector<int32
     std::vector<uint32_t> off;
     std::vector<uint8_t> bytes;
     if (!enc_build_arena(first, second, &off, &bytes)) return false;
+    for (size_t i = 0; i + 1 < sx_off_.size(); ++i) {  // the special tokens: ids 256 + M + i
+      bytes.insert(bytes.end(), sx_bytes_.begin() + sx_off_[i], sx_bytes_.begin() + sx_off_[i + 1]);
+      off.push_back((uint32_t)bytes.size());
+    }
     if (hipMalloc(&dec_arena_, bytes.size()) != hipSuccess) return false;
     if (hipMemcpy(dec_arena_, bytes.data(), bytes.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
     uint32_t* t = nullptr;

@@ -1,4 +1,5 @@
-// What the two encoder units (encode_device.hip, encode_spans.hip) share on the host side.
+// What the encoder units (encode_device.hip, encode_spans.hip, encode_special.hip, ...) share on the
+// host side.
 // Included by .hip files only.
 #pragma once
 

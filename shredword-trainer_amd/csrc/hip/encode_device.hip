@@ -34,19 +34,15 @@
 
 #include "../host/encoder.h"
 #include "encode_common.h"
+#include "encode_words.h"
 
 namespace shred {
 namespace {
 
 typedef uint64_t u64;
 
-constexpr int kThreads = 128;              // threads per workgroup
-constexpr int kSpan = 32;                  // bytes whose word starts one thread owns
-constexpr int kChunk = kThreads * kSpan;   // bytes per workgroup
 constexpr int kStrip = 32;                 // tokens a word keeps in LDS (32 KB per workgroup)
 constexpr int kInf = 0x7fffffff;
-
-__device__ __forceinline__ uint32_t is_delim(uint32_t c) { return c == 9u || c == 13u || c == 10u || c == 32u; }
 
 __device__ __forceinline__ int pair_rank(const u64* __restrict__ tab, u64 mask, int a, int b) {
   if ((uint32_t)a >= (uint32_t)kEncIdLimit || (uint32_t)b >= (uint32_t)kEncIdLimit) return kInf;
@@ -229,33 +225,6 @@ constexpr int kInlineBytes = 16;
 constexpr int kInlineIds = 8;
 constexpr int kSpanWords = kSpan / 2 + 1;  // words starting in one span, at most
 
-// The chunk's text staged in LDS (coalesced 4-byte loads), with a few bytes before it and
-// kOverhang after: word scans, hashes and compares read LDS, and global memory only for bytes
-// outside the staged window.
-constexpr int kOverhang = 256;
-constexpr int kStageBytes = 4 + kChunk + kOverhang;
-
-struct TextView {
-  const uint8_t* __restrict__ g;
-  const uint8_t* l;  // LDS copy of [lo, hi)
-  u64 lo, hi;
-  __device__ __forceinline__ uint32_t operator[](u64 i) const { return (i >= lo && i < hi) ? l[i - lo] : g[i]; }
-};
-
-__device__ __forceinline__ TextView stage_chunk(const uint8_t* __restrict__ text, u64 n, u64 chunk, uint32_t* lds) {
-  const u64 cbase = chunk * kChunk;
-  const u64 lo = cbase >= 4 ? cbase - 4 : 0;
-  u64 hi = lo + kStageBytes;
-  if (hi > n) hi = n;
-  const u64 words = (hi - lo) / 4;
-  for (u64 w = threadIdx.x; w < words; w += kThreads) {
-    const uint8_t* p = text + lo + 4 * w;  // lo is 4-aligned; the text base may not be
-    lds[w] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-  }
-  __syncthreads();
-  return TextView{text, reinterpret_cast<const uint8_t*>(lds), lo, lo + 4 * words};
-}
-
 template <typename T>
 __device__ __forceinline__ u64 word_hash(const T& t, u64 s, uint32_t L) {
   u64 h = 1469598103934665603ull;
@@ -268,32 +237,6 @@ __device__ __forceinline__ u64 word_hash(const T& t, u64 s, uint32_t L) {
   h *= 0xc4ceb9fe1a85ec53ull;
   h ^= h >> 33;
   return h | 1ull;  // 0 marks an empty slot
-}
-
-// Calls f(s, L, j) for every word starting in the span at `base` (L may exceed kEncMaxWord).
-template <typename T, typename F>
-__device__ __forceinline__ void for_each_word(const T& text, u64 n, u64 base, F f) {
-  if (base >= n) return;
-  const u64 lim = n - base < (u64)kSpan ? n - base : (u64)kSpan;
-  uint32_t dm = 0;
-  for (int k = 0; k < kSpan; ++k) dm |= ((u64)k < lim ? is_delim(text[base + k]) : 1u) << k;
-  const uint32_t prevd = base == 0 ? 1u : is_delim(text[base - 1]);
-  uint32_t starts = ~dm & ((dm << 1) | prevd);
-  while (starts) {
-    const int j = __ffs(starts) - 1;
-    starts &= starts - 1;
-    const u64 s = base + j;
-    const uint32_t above = dm >> j;
-    u64 L;
-    if (above) {
-      L = __ffs(above) - 1;
-    } else {
-      u64 e = base + kSpan;
-      while (e < n && e - s <= (u64)kEncMaxWord && !is_delim(text[e])) ++e;
-      L = e - s;
-    }
-    f(s, L, j);
-  }
 }
 
 __device__ __forceinline__ void flag(u64* misc, u64 bit) {
@@ -591,6 +534,7 @@ EncodeDevice::~EncodeDevice() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   free_spans();
+  free_special();
   free_decode();
   free_batch();
   for (void* p : {(void*)table_, (void*)byte_map_, (void*)misc_, (void*)pad_, (void*)rank_, (void*)tcnt_,

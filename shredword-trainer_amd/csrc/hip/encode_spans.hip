@@ -319,8 +319,10 @@ int EncodeDevice::span_passes(const uint8_t* text, size_t n, const int32_t* ids,
 
 int64_t EncodeDevice::encode_spans(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts,
                                    int64_t* line_off, size_t line_cap, size_t* num_lines,
-                                   const std::vector<int32_t>& lens, void* stream, double* kernel_ms) {
+                                   const std::vector<int32_t>& lens, void* stream, double* kernel_ms,
+                                   bool specials) {
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+  if (kernel_ms && specials) kernel_ms[2] = 0;
   if (num_lines) *num_lines = 0;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
@@ -333,7 +335,8 @@ int64_t EncodeDevice::encode_spans(const uint8_t* text, size_t n, int32_t* out, 
     }
     return 0;
   }
-  const int64_t T = encode(text, n, out, cap, stream, kernel_ms);
+  const int64_t T = specials ? encode_special(text, n, out, cap, lens, stream, kernel_ms, kernel_ms ? kernel_ms + 2 : nullptr)
+                             : encode(text, n, out, cap, stream, kernel_ms);
   if (T < 0 || (!starts && !line_off && !num_lines)) return T;
   ENC_OK(hipSetDevice(device_));  // (encode's guard restored the caller's)
   size_t nl = 0;
@@ -383,9 +386,9 @@ size_t count_newlines(const uint8_t* p, size_t n) {
 // the '\n' ordinal carried from the pieces before it, and line_off[L] = T is written at the end.
 int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts,
                                         int64_t* line_off, size_t line_cap, size_t* num_lines,
-                                        const std::vector<int32_t>& lens) {
+                                        const std::vector<int32_t>& lens, bool specials) {
   if (num_lines) *num_lines = 0;
-  if (!starts && !line_off && !num_lines) return encode_host(text, n, out, cap);
+  if (!specials && !starts && !line_off && !num_lines) return encode_host(text, n, out, cap);
   if (n == 0) {
     if (line_off) {
       if (line_cap < 1) return -2;
@@ -413,7 +416,8 @@ int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* 
     const size_t len = host_piece_len(text, n, pos, piece);
     if (len == 0) return -3;
     ENC_OK(hipMemcpyAsync(dtext_, text + pos, len, hipMemcpyHostToDevice, st));
-    const int64_t r = encode(dtext_, len, dout_, cap - done, nullptr, nullptr);
+    const int64_t r = specials ? encode_special(dtext_, len, dout_, cap - done, lens, nullptr, nullptr, nullptr)
+                               : encode(dtext_, len, dout_, cap - done, nullptr, nullptr);
     if (r < 0) return r;
     ENC_OK(hipSetDevice(device_));
     const size_t T = (size_t)r;
@@ -434,8 +438,10 @@ int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* 
     }
     size_t nl = 0;
     uint8_t last = 0;
-    const int s = span_passes(dtext_, len, dout_, T, starts ? sp_hstarts_ : nullptr, line_off ? sp_hline_ : nullptr,
-                              sp_hline_cap_, (u64)pos, (u64)done, false, lens, st, &nl, &last, nullptr);
+    // (nothing but the ids wanted: a special call, which has no other host path)
+    const int s = !starts && !line_off ? 0
+                  : span_passes(dtext_, len, dout_, T, starts ? sp_hstarts_ : nullptr, line_off ? sp_hline_ : nullptr,
+                                sp_hline_cap_, (u64)pos, (u64)done, false, lens, st, &nl, &last, nullptr);
     if (s < 0) return -1;  // (-2 cannot happen: the staging holds the piece's own '\n' count + 1)
     if (T) ENC_OK(hipMemcpyAsync(out + done, dout_, T * 4, hipMemcpyDeviceToHost, st));
     if (starts && T) ENC_OK(hipMemcpyAsync(starts + done, sp_hstarts_, T * 8, hipMemcpyDeviceToHost, st));

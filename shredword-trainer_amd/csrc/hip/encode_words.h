@@ -1,0 +1,76 @@
+// The word walk of the encoder kernels (encode_device.hip) and of the special-token scan
+// (encode_special.hip): one workgroup per 4096-byte chunk, one thread per 32-byte span, a word
+// belongs to the span it starts in.  Device code; included by those two .hip files only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../host/encoder.h"
+
+namespace shred {
+namespace {
+
+constexpr int kThreads = 128;              // threads per workgroup
+constexpr int kSpan = 32;                  // bytes whose word starts one thread owns
+constexpr int kChunk = kThreads * kSpan;   // bytes per workgroup
+
+__device__ __forceinline__ uint32_t is_delim(uint32_t c) { return c == 9u || c == 13u || c == 10u || c == 32u; }
+
+// The chunk's text staged in LDS (coalesced 4-byte loads), with a few bytes before it and
+// kOverhang after: word scans, hashes and compares read LDS, and global memory only for bytes
+// outside the staged window.
+constexpr int kOverhang = 256;
+constexpr int kStageBytes = 4 + kChunk + kOverhang;
+
+struct TextView {
+  const uint8_t* __restrict__ g;
+  const uint8_t* l;  // LDS copy of [lo, hi)
+  uint64_t lo, hi;
+  __device__ __forceinline__ uint32_t operator[](uint64_t i) const { return (i >= lo && i < hi) ? l[i - lo] : g[i]; }
+};
+
+__device__ __forceinline__ TextView stage_chunk(const uint8_t* __restrict__ text, uint64_t n, uint64_t chunk,
+                                                uint32_t* lds) {
+  const uint64_t cbase = chunk * kChunk;
+  const uint64_t lo = cbase >= 4 ? cbase - 4 : 0;
+  uint64_t hi = lo + kStageBytes;
+  if (hi > n) hi = n;
+  const uint64_t words = (hi - lo) / 4;
+  for (uint64_t w = threadIdx.x; w < words; w += kThreads) {
+    const uint8_t* p = text + lo + 4 * w;  // lo is 4-aligned; the text base may not be
+    lds[w] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+  }
+  __syncthreads();
+  return TextView{text, reinterpret_cast<const uint8_t*>(lds), lo, lo + 4 * words};
+}
+
+// Calls f(s, L, j) for every word starting in the span at `base` (L may exceed kEncMaxWord).
+template <typename T, typename F>
+__device__ __forceinline__ void for_each_word(const T& text, uint64_t n, uint64_t base, F f) {
+  if (base >= n) return;
+  const uint64_t lim = n - base < (uint64_t)kSpan ? n - base : (uint64_t)kSpan;
+  uint32_t dm = 0;
+  for (int k = 0; k < kSpan; ++k) dm |= ((uint64_t)k < lim ? is_delim(text[base + k]) : 1u) << k;
+  const uint32_t prevd = base == 0 ? 1u : is_delim(text[base - 1]);
+  uint32_t starts = ~dm & ((dm << 1) | prevd);
+  while (starts) {
+    const int j = __ffs(starts) - 1;
+    starts &= starts - 1;
+    const uint64_t s = base + j;
+    const uint32_t above = dm >> j;
+    uint64_t L;
+    if (above) {
+      L = __ffs(above) - 1;
+    } else {
+      uint64_t e = base + kSpan;
+      while (e < n && e - s <= (uint64_t)kEncMaxWord && !is_delim(text[e])) ++e;
+      L = e - s;
+    }
+    f(s, L, j);
+  }
+}
+
+}  // namespace
+}  // namespace shred

@@ -63,8 +63,9 @@ bool enc_build_arena(const std::vector<int32_t>& first, const std::vector<int32_
 struct ShredEncoder {
   std::vector<int32_t> first, second;
   int32_t byte_map[256];
-  std::vector<std::string> tokens;  // bytes of every id (256 + merges)
-  std::vector<int32_t> lens;        // source bytes of every id, from the merge list alone
+  std::vector<std::string> tokens;  // bytes of every id (256 + merges + specials)
+  std::vector<int32_t> lens;        // source bytes of every id, from the merge list and the specials alone
+  size_t num_specials = 0;
   bool spans_ok = true;             // no byte maps to an id >= 256
   uint64_t vocab_bytes = 0;         // bytes of all tokens (the device decoder's arena)
   std::unique_ptr<shred::EncodeDevice> dev;
@@ -243,6 +244,52 @@ int64_t shred_encode_spans_device(ShredEncoder* enc, const void* text, size_t n,
   if (!enc->spans_ok) return -4;
   return enc->dev->encode_spans((const uint8_t*)text, n, (int32_t*)out, cap, (int64_t*)starts, (int64_t*)line_off,
                                 line_cap, num_lines, enc->lens, stream, kernel_ms);
+}
+
+int shred_encoder_set_specials(ShredEncoder* enc, const uint8_t* bytes, const size_t* offsets, size_t K) {
+  if (!enc || K > SHRED_SPECIAL_MAX || (K && (!bytes || !offsets))) return -1;
+  std::vector<std::string> sp(K);
+  for (size_t i = 0; i < K; ++i) {
+    if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > SHRED_SPECIAL_MAX_LEN) return -1;
+    sp[i].assign((const char*)bytes + offsets[i], offsets[i + 1] - offsets[i]);
+    if (sp[i].find_first_of("\t\r\n ") != std::string::npos) return -1;
+    if (std::find(sp.begin(), sp.begin() + i, sp[i]) != sp.begin() + i) return -1;
+  }
+  const size_t V = 256 + enc->first.size();
+  enc->tokens.resize(V);
+  enc->lens.resize(V);
+  for (const std::string& t : sp) {
+    enc->tokens.push_back(t);
+    enc->lens.push_back((int32_t)t.size());
+  }
+  enc->vocab_bytes = 0;
+  for (const std::string& t : enc->tokens) enc->vocab_bytes += t.size();
+  enc->num_specials = K;
+  // (positions relative to the set's first byte: the device keeps its own copy)
+  std::vector<size_t> off(K + 1, 0);
+  for (size_t i = 0; i < K; ++i) off[i + 1] = off[i] + sp[i].size();
+  enc->dev->set_specials(K ? bytes + offsets[0] : nullptr, off.data(), K, (int32_t)V);
+  return 0;
+}
+
+size_t shred_encoder_num_specials(const ShredEncoder* enc) { return enc ? enc->num_specials : 0; }
+
+int64_t shred_encode_special(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap,
+                             int64_t* starts, int64_t* line_off, size_t line_cap, size_t* num_lines) {
+  if (!enc || (n && (!text || !out))) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_spans_host(text, n, out, cap, starts, line_off, line_cap, num_lines, enc->lens,
+                                     enc->num_specials != 0);
+}
+
+int64_t shred_encode_special_device(ShredEncoder* enc, const void* text, size_t n, void* out, size_t cap,
+                                    void* starts, void* line_off, size_t line_cap, size_t* num_lines, void* stream,
+                                    double* kernel_ms) {
+  if (kernel_ms) kernel_ms[2] = 0;
+  if (!enc || (n && (!text || !out))) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_spans((const uint8_t*)text, n, (int32_t*)out, cap, (int64_t*)starts, (int64_t*)line_off,
+                                line_cap, num_lines, enc->lens, stream, kernel_ms, enc->num_specials != 0);
 }
 
 int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint8_t* out, size_t cap) {

@@ -52,16 +52,31 @@ class EncodeDevice {
   // lens: the 256 + M source-byte lengths of the ids (host; uploaded on the first call).
   // kernel_ms: nullptr or 2 doubles (encode passes, span passes).  Returns as encode(); -2 also
   // when line_cap < lines + 1 (*num_lines is set, line_off untouched).
+  // specials: the ids come from encode_special() instead of encode() (lens then holds the special
+  // tokens' lengths too, and kernel_ms 3 doubles: the third is the special passes).
   int64_t encode_spans(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts, int64_t* line_off,
                        size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens, void* stream,
-                       double* kernel_ms);
+                       double* kernel_ms, bool specials = false);
   // The same on host buffers, in the pieces of encode_host.
   int64_t encode_spans_host(const uint8_t* text, size_t n, int32_t* out, size_t cap, int64_t* starts,
-                            int64_t* line_off, size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens);
+                            int64_t* line_off, size_t line_cap, size_t* num_lines, const std::vector<int32_t>& lens,
+                            bool specials = false);
+
+  // ---- special tokens (encode_special.hip; include/shredword_encode.h defines the matching) ----
+  // Replaces the set: special i is bytes[off[i] .. off[i + 1]) and gets id first_id + i (the
+  // caller has validated the set).  The scan table is rebuilt on the next special call, the span
+  // length table and the decode vocabulary on the next call that uses them.
+  void set_specials(const uint8_t* bytes, const size_t* off, size_t K, int32_t first_id);
+  // encode() with the registered special tokens matched in the text: out receives the word ids
+  // and the special ids in text order.  Returns as encode().  lens: as encode_spans takes it.
+  // enc_ms / special_ms: nullptr or the device time of the encode passes / of the special passes.
+  int64_t encode_special(const uint8_t* text, size_t n, int32_t* out, size_t cap, const std::vector<int32_t>& lens,
+                         void* stream, double* enc_ms, double* special_ms);
 
   // ---- ids to bytes (decode_device.hip; arguments and results as include/shredword_encode.h
   // defines them for shred_decode_device / shred_decode_rows).  first / second: the merge list,
-  // from which the device vocabulary is built and uploaded on the first call.  The callers have
+  // from which the device vocabulary (with the registered special tokens behind the merges) is
+  // built and uploaded on the first call, and again after set_specials().  The callers have
   // checked the arguments' ranges; decode_host's have also checked row_off, the ids (strict mode)
   // and cap on the host, so it returns the bytes written or -1.
   int64_t decode(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, uint8_t* out, size_t cap,
@@ -151,6 +166,31 @@ class EncodeDevice {
   size_t sp_hstarts_cap_ = 0, sp_hline_cap_ = 0;
   int64_t* sp_hstarts_ = nullptr;
   int64_t* sp_hline_ = nullptr;
+
+  // special passes (encode_special.hip): allocated on the first special call, never by the others
+  bool reserve_special(size_t n);
+  void free_special();  // called by the destructor
+  std::vector<uint8_t> sx_bytes_;    // the registered specials' bytes, in id order
+  std::vector<uint32_t> sx_off_;     // K + 1 offsets into sx_bytes_
+  int32_t sx_first_id_ = 0;          // id of special 0
+  bool sx_dirty_ = false;            // the device table is older than the set
+  uint32_t* sx_tab_ = nullptr;       // scan table: first-byte set, groups, entries, bytes
+  uint32_t sx_tab_words_ = 0, sx_tab_ent_ = 0, sx_tab_bytes_ = 0;  // its size, entry and byte word offsets
+  size_t sx_cap_ = 0;                // text bytes the scratch below holds
+  uint8_t* sx_text_ = nullptr;       // the text with the accepted matches blanked
+  int32_t* sx_wids_ = nullptr;       // ids of the blanked text's words
+  uint32_t* sx_cnt_ = nullptr;       // matches of the runs that start in each 32-byte span
+  uint64_t* sx_inc_ = nullptr;       // their inclusive sum
+  void* sx_tmp_ = nullptr;           // hipCUB scan scratch
+  size_t sx_tmp_bytes_ = 0;
+  size_t sx_ids_ = 0;                // entries sx_wstarts_ holds
+  int64_t* sx_wstarts_ = nullptr;    // byte offsets of the word ids
+  size_t sx_matches_ = 0;            // entries sx_mpos_ / sx_midx_ hold
+  uint64_t* sx_mpos_ = nullptr;      // match positions, ascending
+  uint32_t* sx_midx_ = nullptr;      // their specials
+  uint64_t* sx_flag_ = nullptr;      // device: a run past kEncMaxWord
+  uint64_t* sx_host_ = nullptr;      // pinned: match total, the flag
+  void* sx_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
 
   // decode passes (decode_device.hip): allocated on the first decode call, never by the encode calls
   struct DecodeCall;  // one call's arguments, as the kernels take them

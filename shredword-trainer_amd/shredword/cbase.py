@@ -163,6 +163,14 @@ lib.shred_encode_spans.restype = c_int64
 lib.shred_encode_spans_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                           c_size_t, POINTER(c_size_t), c_void_p, POINTER(c_double)]
 lib.shred_encode_spans_device.restype = c_int64
+# special tokens matched in the text
+lib.shred_encoder_set_specials.argtypes = [Encoder, c_void_p, POINTER(c_size_t), c_size_t]
+lib.shred_encoder_set_specials.restype = c_int
+lib.shred_encoder_num_specials.argtypes, lib.shred_encoder_num_specials.restype = [Encoder], c_size_t
+lib.shred_encode_special.argtypes = lib.shred_encode_spans.argtypes
+lib.shred_encode_special.restype = c_int64
+lib.shred_encode_special_device.argtypes = lib.shred_encode_spans_device.argtypes
+lib.shred_encode_special_device.restype = c_int64
 # ids back to bytes, per row
 lib.shred_decode_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                     c_int, c_char_p, c_int, c_void_p, POINTER(c_double)]

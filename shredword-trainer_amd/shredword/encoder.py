@@ -18,6 +18,8 @@ from .cbase import lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_UNK = 8      # SHRED_DECODE_MAX_UNK
+MAX_SPECIALS = 256     # SHRED_SPECIAL_MAX
+MAX_SPECIAL_LEN = 64   # SHRED_SPECIAL_MAX_LEN
 # decode_device.hip: output bytes per workgroup of the expansion kernel (kTile), ids per workgroup of
 # the strict-mode id check (kChunk)
 DECODE_TILE = 4096
@@ -39,7 +41,9 @@ def _destroy_live():
 
 
 class BPEEncoder:
-    def __init__(self, model_path: str, vocab_path: str = None, unk_id: int = 0, device: int = 0):
+    def __init__(self, model_path: str, vocab_path: str = None, unk_id: int = 0, device: int = 0,
+                 special_tokens=None):
+        """special_tokens: None or a list of bytes / str, see set_special_tokens."""
         self.enc = lib.shred_encoder_load(model_path.encode("utf-8"),
                                           vocab_path.encode("utf-8") if vocab_path else None,
                                           int(unk_id), int(device))
@@ -47,9 +51,12 @@ class BPEEncoder:
         if not self.enc:
             raise RuntimeError(f"Failed to create the encoder for {model_path} (see stderr; a GPU is required)")
         _LIVE.add(self)
+        self._specials = []
+        if special_tokens:
+            self.set_special_tokens(special_tokens)
 
     @classmethod
-    def from_merges(cls, merges, byte_map=None, device: int = 0):
+    def from_merges(cls, merges, byte_map=None, device: int = 0, special_tokens=None):
         """merges: (M, 3) int32 array of (first, second, 256 + m) as in a .model file."""
         m = np.ascontiguousarray(np.asarray(merges, dtype=np.int32).reshape(-1, 3))
         bm = None if byte_map is None else np.ascontiguousarray(np.asarray(byte_map, dtype=np.int32))
@@ -63,7 +70,30 @@ class BPEEncoder:
         if not self.enc:
             raise RuntimeError("Failed to create the encoder (invalid merges or no GPU; see stderr)")
         _LIVE.add(self)
+        self._specials = []
+        if special_tokens:
+            self.set_special_tokens(special_tokens)
         return self
+
+    def set_special_tokens(self, tokens):
+        """Replaces the encoder's special tokens (an empty list clears them).  tokens: bytes / str, at most
+        256 distinct ones of 1 to 64 bytes without a delimiter byte (tab, CR, LF, space); token i gets id
+        256 + num_merges + i.  They are matched only by the calls given specials=True (leftmost, then
+        longest, without overlap; no merge reaches across a match), and every decode call turns their
+        ids back into their bytes.  A rejected list raises ValueError and leaves the set as it was."""
+        toks = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in tokens]
+        data = np.frombuffer(b"".join(toks) or b"\0", dtype=np.uint8)
+        off = (ctypes.c_size_t * (len(toks) + 1))(*np.cumsum([0] + [len(t) for t in toks]).tolist())
+        if lib.shred_encoder_set_specials(self.enc, data.ctypes.data, off, len(toks)):
+            raise ValueError(f"special tokens must be at most {MAX_SPECIALS} distinct byte strings of 1 to "
+                             f"{MAX_SPECIAL_LEN} bytes without a delimiter byte")
+        self._specials = toks
+
+    @property
+    def special_tokens(self) -> dict:
+        """The registered special tokens: bytes -> id."""
+        base = 256 + self.num_merges
+        return {t: base + i for i, t in enumerate(self._specials)}
 
     @property
     def num_merges(self) -> int:
@@ -79,8 +109,9 @@ class BPEEncoder:
 
     @property
     def token_lengths(self) -> np.ndarray:
-        """Source bytes each id covers: int32, 256 + num_merges entries (ids below 256: 1)."""
-        out = np.empty(256 + self.num_merges, dtype=np.int32)
+        """Source bytes each id covers: int32, 256 + num_merges entries (ids below 256: 1), then one per
+        special token."""
+        out = np.empty(256 + self.num_merges + len(self._specials), dtype=np.int32)
         if lib.shred_encoder_token_lengths(self.enc, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), out.size):
             raise RuntimeError("token_lengths failed")
         return out
@@ -102,8 +133,11 @@ class BPEEncoder:
         return np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) \
             else np.ascontiguousarray(text, dtype=np.uint8)
 
-    def encode(self, text) -> np.ndarray:
-        """bytes / str / uint8 array -> int32 ids of every word, in text order."""
+    def encode(self, text, specials: bool = False) -> np.ndarray:
+        """bytes / str / uint8 array -> int32 ids of every word, in text order.  specials: match the
+        registered special tokens in the text (set_special_tokens)."""
+        if specials:
+            return self._spans_host(text, False, False, True)[0]
         buf = self._host_text(text)
         out = np.empty(max(1, buf.size), dtype=np.int32)
         r = self._check(lib.shred_encode(self.enc, buf.ctypes.data, buf.size, out.ctypes.data, out.size))
@@ -128,36 +162,41 @@ class BPEEncoder:
                                                 ctypes.c_void_p(st), ctypes.byref(ms)))
         return out[:r], ms.value
 
-    def _spans_host(self, text, want_starts, want_lines):
+    def _spans_host(self, text, want_starts, want_lines, specials=False):
         buf = self._host_text(text)
         out = np.empty(max(1, buf.size), dtype=np.int32)
         starts = np.empty(out.size, dtype=np.int64) if want_starts else None
         line = np.empty(np.count_nonzero(buf == 10) + 2, dtype=np.int64) if want_lines else None
         nl = ctypes.c_size_t()
-        r = self._check(lib.shred_encode_spans(self.enc, buf.ctypes.data, buf.size, out.ctypes.data, out.size,
-                                               None if starts is None else starts.ctypes.data,
-                                               None if line is None else line.ctypes.data,
-                                               0 if line is None else line.size, ctypes.byref(nl)))
+        call = lib.shred_encode_special if specials else lib.shred_encode_spans
+        r = self._check(call(self.enc, buf.ctypes.data, buf.size, out.ctypes.data, out.size,
+                             None if starts is None else starts.ctypes.data,
+                             None if line is None else line.ctypes.data,
+                             0 if line is None else line.size, ctypes.byref(nl)))
         return (out[:r].copy(), None if starts is None else starts[:r].copy(),
                 None if line is None else line[:nl.value + 1].copy())
 
-    def encode_lines(self, text):
+    def encode_lines(self, text, specials: bool = False):
         """-> (ids, line_offsets): line i (split on '\\n' only) holds ids[line_offsets[i]:line_offsets[i + 1]];
-        int64, lines + 1 entries, where a text not ending in '\\n' has a last line of its own."""
-        ids, _, line = self._spans_host(text, False, True)
+        int64, lines + 1 entries, where a text not ending in '\\n' has a last line of its own.
+        specials: as encode."""
+        ids, _, line = self._spans_host(text, False, True, specials)
         return ids, line
 
-    def encode_spans(self, text, lines: bool = False):
+    def encode_spans(self, text, lines: bool = False, specials: bool = False):
         """-> (ids, starts) or (ids, starts, line_offsets).  starts[k] (int64) is the byte offset in
         the text of token k's first byte; the token ends at starts[k] + token_lengths[max(ids[k], 0)]
         (an id below 256 covers 1 byte), and begins a word iff k == 0 or it does not start where
-        token k - 1 ended."""
-        ids, starts, line = self._spans_host(text, True, lines)
+        token k - 1 ended.  specials: as encode; a special token starts at its match, covers its own
+        bytes and is a word of its own."""
+        ids, starts, line = self._spans_host(text, True, lines, specials)
         return (ids, starts, line) if lines else (ids, starts)
 
-    def encode_spans_device(self, text, starts: bool = True, lines: bool = True, stream=None):
+    def encode_spans_device(self, text, starts: bool = True, lines: bool = True, stream=None,
+                            specials: bool = False):
         """text: 1-D uint8 torch tensor on the encoder's GPU -> (ids, starts or None, line_offsets or
-        None, (encode_ms, spans_ms)): int32 / int64 / int64 tensor views on the text's device."""
+        None, (encode_ms, spans_ms)): int32 / int64 / int64 tensor views on the text's device.
+        specials: as encode; the times are then (encode_ms, spans_ms, specials_ms)."""
         import torch
         if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_cuda or not text.is_contiguous():
             raise ValueError("text must be a contiguous 1-D uint8 CUDA tensor")
@@ -168,15 +207,16 @@ class BPEEncoder:
         st_t = torch.empty(max(1, n), dtype=torch.int64, device=text.device) if starts else None
         ln_t = torch.empty(int((text == 10).sum().item()) + 1 + 1, dtype=torch.int64, device=text.device) \
             if lines else None
-        ms = (ctypes.c_double * 2)()
+        ms = (ctypes.c_double * 3)()
         nl = ctypes.c_size_t()
         st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
-        r = self._check(lib.shred_encode_spans_device(
+        call = lib.shred_encode_special_device if specials else lib.shred_encode_spans_device
+        r = self._check(call(
             self.enc, text.data_ptr(), n, out.data_ptr(), out.numel(),
             None if st_t is None else st_t.data_ptr(), None if ln_t is None else ln_t.data_ptr(),
             0 if ln_t is None else ln_t.numel(), ctypes.byref(nl), ctypes.c_void_p(st), ms))
         return (out[:r], None if st_t is None else st_t[:r], None if ln_t is None else ln_t[:nl.value + 1],
-                (ms[0], ms[1]))
+                (ms[0], ms[1], ms[2]) if specials else (ms[0], ms[1]))
 
     def decode(self, ids) -> bytes:
         """Concatenated bytes of the ids (whitespace between words is not restored)."""
@@ -428,14 +468,14 @@ class BPEEncoder:
         res += (pos[:S * L].view(S, L),) if positions else ()
         return res + ((seg[:S * L].view(S, L),) if segments else ()) + (ms.value,)
 
-    def encode_padded(self, text, **kw):
+    def encode_padded(self, text, *, specials: bool = False, **kw):
         """encode_lines, then pad_rows(**kw): one row of the batch per '\\n' line of the text."""
-        ids, line = self.encode_lines(text)
+        ids, line = self.encode_lines(text, specials)
         return self.pad_rows(ids, line, **kw)
 
-    def encode_packed(self, text, **kw):
+    def encode_packed(self, text, *, specials: bool = False, **kw):
         """encode_lines, then pack_rows(**kw): every '\\n' line of the text is one row of the stream."""
-        ids, line = self.encode_lines(text)
+        ids, line = self.encode_lines(text, specials)
         return self.pack_rows(ids, line, **kw)
 
     def destroy(self):

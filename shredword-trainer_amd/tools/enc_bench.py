@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | special]   (SHREDWORD_LIB picks the build)
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
 GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
@@ -7,7 +7,10 @@ trailing `batch`, the decode leg and then pad_device (rows cut to 1024 ids, with
 pack_device (an eos per row, sequences of 2048, positions and segments) on the corpus's ids and line
 offsets: device ms and effective GB/s by the traffic model of batch_device.hip, and the torch
 composition (torch.full, an index from repeat_interleave of the lengths, a scatter) on the same
-tensors, timed with device events in the same process after a warm-up."""
+tensors, timed with device events in the same process after a warm-up; with a trailing `special`,
+"<|endoftext|>" is put in front of the first '\\n' after every 2048th byte of the corpus, and that
+text is timed through encode_spans_device without and with specials=True (the encode, span and
+special passes of one call each)."""
 import os
 import subprocess
 import sys
@@ -34,7 +37,8 @@ else:
     args = sys.argv[3:]
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
-    if spans or decode:
+    special = args[-1] == "special"
+    if spans or decode or special:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -54,6 +58,24 @@ else:
         encode_ms, spans_ms = sorted(t[0] for t in runs)[reps // 2], runs[reps // 2][1]
         print("spans: encode_ms", encode_ms, "spans_ms", spans_ms, "ratio", spans_ms / encode_ms,
               "spans min", runs[0][1], "max", runs[-1][1], flush=True)
+    if special:
+        del out
+        tok = np.frombuffer(b"<|endoftext|>", dtype=np.uint8)
+        host = text.cpu().numpy()
+        nl = np.flatnonzero(host == 10)
+        at = np.unique(nl[np.searchsorted(nl, np.arange(2048, host.size, 2048))[:-1]])
+        text = torch.from_numpy(np.insert(host, np.repeat(at, tok.size), np.tile(tok, at.size))).cuda()
+        enc.set_special_tokens([tok.tobytes()])
+        med = lambda runs, i: sorted(t[i] for t in runs)[len(runs) // 2]
+        enc.encode_spans_device(text)  # first calls: allocate the scratch
+        plain = [enc.encode_spans_device(text)[3] for _ in range(reps)]
+        ids = enc.encode_spans_device(text, specials=True)[0]
+        found = int((ids == 256 + enc.num_merges).sum().item())
+        assert found == at.size, (found, at.size)
+        runs = [enc.encode_spans_device(text, specials=True)[3] for _ in range(reps)]
+        print("special: bytes", text.numel(), "matches", found, "plain encode_ms", med(plain, 0), "spans_ms",
+              med(plain, 1), "| specials=True encode_ms", med(runs, 0), "spans_ms", med(runs, 1), "special_ms",
+              med(runs, 2), "min", min(t[2] for t in runs), "max", max(t[2] for t in runs), flush=True)
     if decode:
         del out
         ids, _, line, _ = enc.encode_spans_device(text, starts=False)
