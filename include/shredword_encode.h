@@ -158,6 +158,67 @@ int64_t shred_encode_special_device(ShredEncoder* enc, const void* text, size_t 
                                     void* starts, void* line_off, size_t line_cap, size_t* num_lines,
                                     void* stream, double* kernel_ms);
 
+/* ---- batches of documents: rows cut at given byte offsets ------------------------------------------
+ *
+ * The calls above take one text and know rows only as '\n' lines.  These take many documents in
+ * one call, and their rows are the documents, which may hold '\n' themselves.
+ *
+ *   text       n bytes: the documents concatenated with nothing between them.
+ *   doc_off    docs + 1 int64 with 0 = doc_off[0] <= ... <= doc_off[docs] = n; any other doc_off
+ *              returns -6 with nothing written.  Document d is text[doc_off[d] : doc_off[d+1]] and
+ *              may be empty.  NULL with docs == 0: one document holding all of text (the outputs
+ *              then have 1 row and row_off 1 + 1 entries, the row_off == NULL rule of the decode
+ *              and batch calls).  rows below is docs, or 1 for doc_off == NULL.
+ *
+ * Each document is encoded as if alone: a document boundary is a zero-width delimiter, and no
+ * word, no merge and no special-token match reaches across it.  '\n' inside a document is an
+ * ordinary delimiter, as in shred_encode.
+ *
+ *   ids        shred_encode(doc_0) ++ shred_encode(doc_1) ++ ...; with specials != 0 each part is
+ *              shred_encode_special(doc_d) instead (exactly shred_encode's when K == 0).
+ *   row_off    rows + 1 int64 in the line_off format: row_off[0] = 0, row_off[rows] = T, row d is
+ *              ids[row_off[d] : row_off[d+1]].  An empty or all-delimiter document is an empty row.
+ *              It feeds shred_pad_*, shred_pack_* and shred_decode_* unchanged.  Must not be NULL.
+ *   starts     NULL, or cap int64: byte offsets in the concatenated text, not relative to the
+ *              document.  The ids still tile the non-delimiter bytes of text in order.  Token k
+ *              begins a word iff k == 0, or k is the first token of its row, or ids[k] or ids[k-1]
+ *              is a special, or starts[k] != starts[k-1] + len(ids[k-1]).
+ *
+ * The word limit applies to the words after the cut: a run of 2000 non-delimiter bytes that a
+ * boundary cuts into 1000 + 1000 passes, a document holding a run of SHRED_ENCODE_MAX_WORD + 1
+ * returns -3.  Returns the id count T; -1 / -2 / -3 / -4 as shred_encode_spans (-4 because the rows
+ * are found from the tokens' byte lengths), -6 as above.  On any error row_off and starts are not
+ * written.  (A HIP error after the first piece of shred_encode_docs leaves the earlier pieces'
+ * entries in place.)
+ *
+ * The passes run on the GPU around the encode: a copy of the text in which every document is
+ * followed by one '\n' and holds none itself (its own become ' ', a delimiter too), the encode and
+ * the span passes on that copy (whose lines are the documents), and a pass that takes the inserted
+ * bytes out of starts.  Their scratch (1 B per text byte + 1 B per document for the copy, a flag
+ * word, events) is allocated on the first docs call and freed with the encoder, so the other
+ * calls' footprints are unchanged; the encode and span scratch is that of shred_encode_spans on
+ * n + docs bytes, with specials that of shred_encode_special.
+ */
+
+/* Host buffers, staged through cached device buffers in pieces that hold whole documents: a piece
+ * takes documents while their bytes plus one per document stay within the piece budget of
+ * shred_encode.  A single document longer than a piece is staged whole (the rule shred_pad_rows
+ * has for a long row): the longest document bounds the device memory.  Staging: 13 B per piece
+ * byte (text, ids, starts) + 16 B per document of the piece.  doc_off is validated, and the word
+ * limit checked, on the host before anything is staged; when cap is smaller than the text's
+ * non-delimiter bytes, a first round of the pieces only counts the ids, so -2 too comes before
+ * anything is written. */
+int64_t shred_encode_docs(ShredEncoder* enc, const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs,
+                          int specials, int32_t* out, size_t cap, int64_t* starts, int64_t* row_off);
+
+/* All buffers on the encoder's device; doc_off is validated there (a flag word the host reads
+ * before any other pass runs).  Queued on `stream` (NULL = the encoder's own) and synchronised
+ * before return.  kernel_ms (NULL or 4 doubles): [0] the encode passes, [1] the span passes, [2]
+ * the special passes, [3] the document passes. */
+int64_t shred_encode_docs_device(ShredEncoder* enc, const void* text, size_t n, const void* doc_off, size_t docs,
+                                 int specials, void* out, size_t cap, void* starts, void* row_off, void* stream,
+                                 double* kernel_ms);
+
 /* ---- ids back to bytes on the GPU, per row ---------------------------------------------------
  *
  *   ids        n int32.

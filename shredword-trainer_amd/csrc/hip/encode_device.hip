@@ -535,6 +535,7 @@ EncodeDevice::~EncodeDevice() {
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   free_spans();
   free_special();
+  free_docs();
   free_decode();
   free_batch();
   for (void* p : {(void*)table_, (void*)byte_map_, (void*)misc_, (void*)pad_, (void*)rank_, (void*)tcnt_,

@@ -292,6 +292,25 @@ int64_t shred_encode_special_device(ShredEncoder* enc, const void* text, size_t 
                                 line_cap, num_lines, enc->lens, stream, kernel_ms, enc->num_specials != 0);
 }
 
+int64_t shred_encode_docs(ShredEncoder* enc, const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs,
+                          int specials, int32_t* out, size_t cap, int64_t* starts, int64_t* row_off) {
+  if (!enc || !row_off || (n && (!text || !out)) || (!doc_off && docs)) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_docs_host(text, n, doc_off, docs, specials != 0 && enc->num_specials != 0, out, cap, starts,
+                                    row_off, enc->lens);
+}
+
+int64_t shred_encode_docs_device(ShredEncoder* enc, const void* text, size_t n, const void* doc_off, size_t docs,
+                                 int specials, void* out, size_t cap, void* starts, void* row_off, void* stream,
+                                 double* kernel_ms) {
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0;
+  if (!enc || !row_off || (n && (!text || !out)) || (!doc_off && docs)) return -1;
+  if (!enc->spans_ok) return -4;
+  return enc->dev->encode_docs((const uint8_t*)text, n, (const int64_t*)doc_off, docs,
+                               specials != 0 && enc->num_specials != 0, (int32_t*)out, cap, (int64_t*)starts,
+                               (int64_t*)row_off, 0, enc->lens, stream, kernel_ms);
+}
+
 int64_t shred_decode(const ShredEncoder* enc, const int32_t* ids, size_t n, uint8_t* out, size_t cap) {
   if (!enc || (n && !ids)) return -1;
   size_t need = 0;

@@ -73,6 +73,20 @@ class EncodeDevice {
   int64_t encode_special(const uint8_t* text, size_t n, int32_t* out, size_t cap, const std::vector<int32_t>& lens,
                          void* stream, double* enc_ms, double* special_ms);
 
+  // ---- batches of documents (encode_docs.hip; include/shredword_encode.h defines the rows) ----
+  // text (n bytes), doc_off (nullptr with docs == 0: one document; else docs + 1 entries, validated
+  // on the device) and the outputs on the device: out (cap ids), starts (nullptr or cap int64; each
+  // gets start_base added), row_off (rows + 1 int64).  specials: the ids come from encode_special().
+  // kernel_ms: nullptr or 4 doubles (encode, span, special, document passes).  Returns as
+  // encode_spans(), -6 for a bad doc_off.
+  int64_t encode_docs(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials, int32_t* out,
+                      size_t cap, int64_t* starts, int64_t* row_off, uint64_t start_base,
+                      const std::vector<int32_t>& lens, void* stream, double* kernel_ms);
+  // The same on host buffers, in pieces of whole documents (doc_off is validated on the host).
+  int64_t encode_docs_host(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials,
+                           int32_t* out, size_t cap, int64_t* starts, int64_t* row_off,
+                           const std::vector<int32_t>& lens);
+
   // ---- ids to bytes (decode_device.hip; arguments and results as include/shredword_encode.h
   // defines them for shred_decode_device / shred_decode_rows).  first / second: the merge list,
   // from which the device vocabulary (with the registered special tokens behind the merges) is
@@ -191,6 +205,20 @@ class EncodeDevice {
   uint64_t* sx_flag_ = nullptr;      // device: a run past kEncMaxWord
   uint64_t* sx_host_ = nullptr;      // pinned: match total, the flag
   void* sx_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+
+  // document passes (encode_docs.hip): allocated on the first docs call, never by the others
+  bool reserve_docs(size_t total);
+  void free_docs();  // called by the destructor
+  size_t dx_cap_ = 0;                // bytes dx_text_ holds
+  uint8_t* dx_text_ = nullptr;       // the copy: every document followed by a '\n', none inside
+  uint64_t* dx_flag_ = nullptr;      // device: bad doc_off
+  uint64_t* dx_host_ = nullptr;      // pinned: the flag
+  void* dx_ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around the check, the copy, the starts pass
+  // host-path staging: a piece's document offsets, row offsets, starts (text and ids: dtext_ / dout_)
+  size_t dx_hoff_cap_ = 0, dx_hrow_cap_ = 0, dx_hstarts_cap_ = 0;
+  int64_t* dx_hoff_ = nullptr;
+  int64_t* dx_hrow_ = nullptr;
+  int64_t* dx_hstarts_ = nullptr;
 
   // decode passes (decode_device.hip): allocated on the first decode call, never by the encode calls
   struct DecodeCall;  // one call's arguments, as the kernels take them

@@ -171,6 +171,12 @@ lib.shred_encode_special.argtypes = lib.shred_encode_spans.argtypes
 lib.shred_encode_special.restype = c_int64
 lib.shred_encode_special_device.argtypes = lib.shred_encode_spans_device.argtypes
 lib.shred_encode_special_device.restype = c_int64
+# batches of documents: rows cut at given byte offsets
+lib.shred_encode_docs.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t,
+                                  c_void_p, c_void_p]
+lib.shred_encode_docs.restype = c_int64
+lib.shred_encode_docs_device.argtypes = lib.shred_encode_docs.argtypes + [c_void_p, POINTER(c_double)]
+lib.shred_encode_docs_device.restype = c_int64
 # ids back to bytes, per row
 lib.shred_decode_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                     c_int, c_char_p, c_int, c_void_p, POINTER(c_double)]

@@ -40,6 +40,16 @@ def _destroy_live():
         e.destroy()
 
 
+def join_docs(texts):
+    """A sequence of bytes / str documents (str as UTF-8) -> (uint8 array of the documents joined with
+    nothing between them, int64 offsets with len(texts) + 1 entries): document d is
+    array[offsets[d]:offsets[d + 1]], the form encode_docs takes."""
+    docs = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in texts]
+    off = np.zeros(len(docs) + 1, dtype=np.int64)
+    np.cumsum([len(d) for d in docs], dtype=np.int64, out=off[1:])
+    return np.frombuffer(b"".join(docs), dtype=np.uint8), off
+
+
 class BPEEncoder:
     def __init__(self, model_path: str, vocab_path: str = None, unk_id: int = 0, device: int = 0,
                  special_tokens=None):
@@ -217,6 +227,69 @@ class BPEEncoder:
             0 if ln_t is None else ln_t.numel(), ctypes.byref(nl), ctypes.c_void_p(st), ms))
         return (out[:r], None if st_t is None else st_t[:r], None if ln_t is None else ln_t[:nl.value + 1],
                 (ms[0], ms[1], ms[2]) if specials else (ms[0], ms[1]))
+
+    # ---- batches of documents: rows cut at given byte offsets (include/shredword_encode.h) --------
+
+    @classmethod
+    def _check_docs(cls, r: int) -> int:
+        if r == -6:
+            raise ValueError("doc_offsets must be 0 = doc_offsets[0] <= ... <= doc_offsets[docs] = len(text)")
+        return cls._check(r)
+
+    def encode_docs(self, text, doc_offsets=None, *, starts: bool = False, specials: bool = False):
+        """-> (ids, row_offsets) or (ids, row_offsets, starts).  text holds the documents concatenated with
+        nothing between them; document d is text[doc_offsets[d]:doc_offsets[d + 1]] (docs + 1 offsets from
+        0 to len(text), non-decreasing; None: one document).  Each document is encoded as if alone: no
+        word, merge or special token reaches across a boundary, and a '\\n' inside a document is an
+        ordinary delimiter.  Row d of the result is ids[row_offsets[d]:row_offsets[d + 1]] (int64, docs
+        + 1 entries, the line_offsets format: pad_rows, pack_rows and decode_rows take it).  starts: the
+        byte offset of every token in `text`.  specials: as encode."""
+        buf = self._host_text(text)
+        off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        if off is not None and off.size == 0:
+            raise ValueError("doc_offsets must hold docs + 1 entries")
+        docs = 0 if off is None else off.size - 1
+        out = np.empty(max(1, buf.size), dtype=np.int32)
+        st = np.empty(out.size, dtype=np.int64) if starts else None
+        row = np.empty((docs if off is not None else 1) + 1, dtype=np.int64)
+        r = self._check_docs(lib.shred_encode_docs(
+            self.enc, buf.ctypes.data, buf.size, None if off is None else off.ctypes.data, docs, int(bool(specials)),
+            out.ctypes.data, out.size, None if st is None else st.ctypes.data, row.ctypes.data))
+        return (out[:r].copy(), row, st[:r].copy()) if starts else (out[:r].copy(), row)
+
+    def encode_batch(self, texts, *, starts: bool = False, specials: bool = False):
+        """A sequence of bytes / str documents -> encode_docs of them joined (join_docs): one row per
+        document, whatever '\\n' bytes the documents hold.  An empty sequence gives no id and row_offsets [0]."""
+        buf, off = join_docs(texts)
+        return self.encode_docs(buf, off, starts=starts, specials=specials)
+
+    def encode_docs_device(self, text, doc_offsets=None, *, starts: bool = False, specials: bool = False, stream=None):
+        """encode_docs on device tensors: text a 1-D uint8 torch tensor on the encoder's GPU, doc_offsets None
+        or a 1-D int64 tensor there (validated on the device) -> (ids, row_offsets, starts or None,
+        (encode_ms, spans_ms, specials_ms, docs_ms)): int32 / int64 / int64 tensor views on the text's device."""
+        import torch
+        for name, t, dt in (("text", text, torch.uint8), ("doc_offsets", doc_offsets, torch.int64)):
+            if t is None and name != "text":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} CUDA tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the encoder on cuda:{self.device}")
+        if doc_offsets is not None and doc_offsets.numel() == 0:
+            raise ValueError("doc_offsets must hold docs + 1 entries")
+        n = text.numel()
+        docs = 0 if doc_offsets is None else doc_offsets.numel() - 1
+        out = torch.empty(max(1, n), dtype=torch.int32, device=text.device)
+        st_t = torch.empty(max(1, n), dtype=torch.int64, device=text.device) if starts else None
+        row = torch.empty((docs if doc_offsets is not None else 1) + 1, dtype=torch.int64, device=text.device)
+        ms = (ctypes.c_double * 4)()
+        st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
+        r = self._check_docs(lib.shred_encode_docs_device(
+            self.enc, text.data_ptr(), n, None if doc_offsets is None else doc_offsets.data_ptr(), docs,
+            int(bool(specials)), out.data_ptr(), out.numel(), None if st_t is None else st_t.data_ptr(),
+            row.data_ptr(), ctypes.c_void_p(st), ms))
+        return out[:r], row, None if st_t is None else st_t[:r], (ms[0], ms[1], ms[2], ms[3])
 
     def decode(self, ids) -> bytes:
         """Concatenated bytes of the ids (whitespace between words is not restored)."""
@@ -468,15 +541,27 @@ class BPEEncoder:
         res += (pos[:S * L].view(S, L),) if positions else ()
         return res + ((seg[:S * L].view(S, L),) if segments else ()) + (ms.value,)
 
-    def encode_padded(self, text, *, specials: bool = False, **kw):
-        """encode_lines, then pad_rows(**kw): one row of the batch per '\\n' line of the text."""
-        ids, line = self.encode_lines(text, specials)
-        return self.pad_rows(ids, line, **kw)
+    def _encode_rows(self, text, specials, doc_offsets):
+        """(ids, row_offsets): documents when text is a list / tuple or doc_offsets is given, else lines."""
+        if isinstance(text, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            return self.encode_batch(text, specials=specials)
+        if doc_offsets is not None:
+            return self.encode_docs(text, doc_offsets, specials=specials)
+        return self.encode_lines(text, specials)
 
-    def encode_packed(self, text, *, specials: bool = False, **kw):
-        """encode_lines, then pack_rows(**kw): every '\\n' line of the text is one row of the stream."""
-        ids, line = self.encode_lines(text, specials)
-        return self.pack_rows(ids, line, **kw)
+    def encode_padded(self, text, *, specials: bool = False, doc_offsets=None, **kw):
+        """encode_lines, then pad_rows(**kw): one row of the batch per '\\n' line of the text.  With a
+        list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): one row per document."""
+        ids, row = self._encode_rows(text, specials, doc_offsets)
+        return self.pad_rows(ids, row, **kw)
+
+    def encode_packed(self, text, *, specials: bool = False, doc_offsets=None, **kw):
+        """encode_lines, then pack_rows(**kw): every '\\n' line of the text is one row of the stream.  With
+        a list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): every document is."""
+        ids, row = self._encode_rows(text, specials, doc_offsets)
+        return self.pack_rows(ids, row, **kw)
 
     def destroy(self):
         if getattr(self, "enc", None):

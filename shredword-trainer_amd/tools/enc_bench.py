@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | special]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | special | docs]   (SHREDWORD_LIB picks the build)
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
 GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
@@ -10,7 +10,12 @@ composition (torch.full, an index from repeat_interleave of the lengths, a scatt
 tensors, timed with device events in the same process after a warm-up; with a trailing `special`,
 "<|endoftext|>" is put in front of the first '\\n' after every 2048th byte of the corpus, and that
 text is timed through encode_spans_device without and with specials=True (the encode, span and
-special passes of one call each)."""
+special passes of one call each); with a trailing `docs`, the corpus is one document per line (doc_offsets
+after every '\\n') and goes through encode_docs_device with starts, then, after a warm-up,
+encode_spans_device(lines=True) on the same text, each also as a whole call between device events, and a
+device-to-device copy of the text's bytes is timed beside the copy kernel of the document passes, whose
+time the library prints under SHREDWORD_ENCODE_DEBUG (set here for the last calls: the corpus one document
+per line, as one document and as 16 documents), and beside a copy of 1 GiB, which the cache does not hold."""
 import os
 import subprocess
 import sys
@@ -37,8 +42,8 @@ else:
     args = sys.argv[3:]
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
-    special = args[-1] == "special"
-    if spans or decode or special:
+    special, docs = args[-1] == "special", args[-1] == "docs"
+    if spans or decode or special or docs:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -76,6 +81,61 @@ else:
         print("special: bytes", text.numel(), "matches", found, "plain encode_ms", med(plain, 0), "spans_ms",
               med(plain, 1), "| specials=True encode_ms", med(runs, 0), "spans_ms", med(runs, 1), "special_ms",
               med(runs, 2), "min", min(t[2] for t in runs), "max", max(t[2] for t in runs), flush=True)
+    if docs:
+        del out
+        reps = max(reps, 5)
+        n = text.numel()
+        nl = torch.nonzero(text == 10).flatten() + 1
+        if nl.numel() == 0 or int(nl[-1].item()) != n:
+            nl = torch.cat([nl, nl.new_tensor([n])])
+        off = torch.cat([nl.new_zeros(1), nl]).contiguous()
+        med = lambda v: sorted(v)[len(v) // 2]
+
+        def whole(fn):
+            """median device ms of the whole call fn() over reps runs"""
+            ms = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            return med(ms)
+
+        run_docs = lambda: enc.encode_docs_device(text, off, starts=True)
+        run_spans = lambda: enc.encode_spans_device(text, starts=True, lines=True)
+        got = run_docs()  # first calls: allocate the scratch
+        ref = run_spans()
+        assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[2]) and torch.equal(got[2], ref[1])
+        run_docs()
+        run_spans()
+        dt = [run_docs()[3] for _ in range(reps)]
+        st = [run_spans()[3] for _ in range(reps)]
+        call_docs, call_spans = whole(run_docs), whole(run_spans)
+        dst = torch.empty_like(text)
+        copy_ms = whole(lambda: dst.copy_(text))
+        big = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")  # past the last-level cache
+        big_dst = torch.empty_like(big)
+        big_ms = whole(lambda: big_dst.copy_(big))
+        del big, big_dst
+        docs_ms = med([t[3] for t in dt])
+        print("docs: bytes", n, "documents", off.numel() - 1, "ids", got[0].numel(), "| encode_docs_device encode_ms",
+              med([t[0] for t in dt]), "spans_ms", med([t[1] for t in dt]), "docs_ms", docs_ms, "min",
+              min(t[3] for t in dt), "max", max(t[3] for t in dt), "| encode_spans_device encode_ms",
+              med([t[0] for t in st]), "spans_ms", med([t[1] for t in st]), "| whole call ms docs", call_docs, "spans",
+              call_spans, "ratio", call_docs / call_spans, "| d2d copy of the text ms", copy_ms, "GB/s (read + write)",
+              2 * n / copy_ms / 1e6, "| d2d copy of 1 GiB ms", big_ms, "GB/s", 2 * (1 << 30) / big_ms / 1e6, flush=True)
+        # the library prints the split of the document passes; the same text as one document (no
+        # boundary: no search, no byte walk) and as 16 documents (searches of 4 steps, next to no walk)
+        # shows what the copy kernel pays for the documents
+        os.environ["SHREDWORD_ENCODE_DEBUG"] = "1"
+        few = off[torch.arange(17, device="cuda") * (off.numel() - 1) // 16].contiguous()
+        for name, o in (("one per line", off), ("one document", None), ("16 documents", few)):
+            print("document passes,", name, file=sys.stderr, flush=True)
+            for _ in range(4):
+                enc.encode_docs_device(text, o, starts=True)
+        del os.environ["SHREDWORD_ENCODE_DEBUG"]
     if decode:
         del out
         ids, _, line, _ = enc.encode_spans_device(text, starts=False)
