@@ -597,7 +597,22 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
   const char* env = std::getenv("SHREDWORD_ENCODE_CACHE");
   bool cached = !(env && env[0] == '0');
   ENC_OK(hipEventRecord(ev[0], st));
-  size_t cc = ccap_min_;
+  size_t cc = ccap_min_, cmax = ccap_;
+  // tests: "<start>[:<max>]" slots for this call (powers of two in [kThreads, ccap_]: the encode
+  // grid is cc / kThreads and the probe mask cc - 1), so a few thousand words reach the growth
+  // branch and the overflow after it
+  if (const char* e = std::getenv("SHREDWORD_ENCODE_CACHE_SLOTS")) {
+    auto slots = [&](const char* s) {
+      const unsigned long long want = std::strtoull(s, nullptr, 10);
+      size_t v = kThreads;
+      while (v < ccap_ && v < want) v <<= 1;
+      return v;
+    };
+    cc = slots(e);
+    const char* colon = std::strchr(e, ':');
+    cmax = colon ? std::max(cc, slots(colon + 1)) : ccap_;
+  }
+  const bool debug = std::getenv("SHREDWORD_ENCODE_DEBUG") != nullptr;
   for (;;) {
     ENC_OK(hipMemsetAsync(misc_, 0, 32, st));
     if (cached) {
@@ -632,14 +647,17 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
     if (fl & 1) return -3;
     if (fl & 16) return -2;  // the output capacity (the cached path writes it directly)
     if (!(fl & 14)) break;
-    if (fl == 2 && cc < ccap_) {  // only a probe window overflowed: a bigger table
-      cc = std::min(ccap_, cc * 4);
+    if (fl == 2 && cc < cmax) {  // only a probe window overflowed: a bigger table
+      cc = std::min(cmax, cc * 4);
+      if (debug) std::fprintf(stderr, "[DEBUG]\t encoder: word cache grows to %zu slots\n", cc);
       continue;
     }
     cached = false;  // cache / arena overflow or a 64-bit word-hash collision: redo on the direct path
-    if (std::getenv("SHREDWORD_ENCODE_DEBUG"))
+    // a slot the full arena left unencoded still holds its text offset where k_cache_words expects
+    // a payload, so its occurrences raise the collision flag too: name the arena first
+    if (debug)
       std::fprintf(stderr, "[DEBUG]\t encoder: word cache %s (%zu slots); direct path\n",
-                   fl & 4 ? "hash collision" : fl & 8 ? "arena overflow" : "overflow", cc);
+                   fl & 8 ? "arena overflow" : fl & 4 ? "hash collision" : "overflow", cc);
     ++fallbacks_;
   }
   ENC_OK(hipEventRecord(ev[1], st));
