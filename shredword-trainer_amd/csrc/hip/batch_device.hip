@@ -49,19 +49,19 @@
 #include "encode_common.h"
 
 namespace shred {
+namespace {
 
-struct EncodeDevice::BatchCall {
+// One call's (or piece's) rows, as the kernels take them.
+struct BatchCall {
   const int32_t* ids;
   uint64_t n;
   const int64_t* row;  // nullptr: one row of all ids (rows == 1); else rows + 1 entries
   uint64_t rows;
   bool ends;           // check row[0] == 0 and row[rows] == n (a piece's local offsets: no)
-  BatchOpts o;
+  EncodeDevice::BatchOpts o;
   uint64_t base;       // pack: stream offset of the call's first row (ids of the pieces before)
   uint64_t row_base;   // pack: index of the call's first row
 };
-
-namespace {
 
 typedef uint64_t u64;
 
@@ -310,17 +310,6 @@ __global__ __launch_bounds__(kThreads) void k_bat_pack(const int32_t* __restrict
   }
 }
 
-template <class T>
-bool grow(T** p, size_t* have, size_t want, size_t elem = sizeof(T)) {
-  if (want <= *have) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, want * elem) != hipSuccess) return false;
-  *have = want;
-  return true;
-}
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Grids are one workgroup per tile / 256 rows.
@@ -328,10 +317,7 @@ bool rows_fit(u64 rows) { return rows / kThreads < 0x7FFFFFFFull; }
 bool tiles_fit(u64 entries) { return entries / kTile < 0x7FFFFFFFull; }
 
 size_t piece_ids() {
-  size_t piece = EncodeDevice::kBatchPiece;
-  if (const char* e = std::getenv("SHREDWORD_BATCH_PIECE"))  // tests: small pieces
-    piece = std::min<size_t>(std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), 1), size_t(1) << 40);
-  return piece;
+  return std::min(piece_from_env("SHREDWORD_BATCH_PIECE", EncodeDevice::kBatchPiece, 1), size_t(1) << 40);
 }
 
 // The rows [r0, r1) of a piece: whole rows while it holds at most `piece` ids, `piece` rows and
@@ -344,86 +330,9 @@ size_t piece_end(const int64_t* row, size_t rows, size_t r0, size_t piece, size_
   return r1;
 }
 
-}  // namespace
-
-void EncodeDevice::free_batch() {
-  for (void* p : {(void*)bat_e_, bat_tmp_, (void*)bat_res_, (void*)bat_hids_, (void*)bat_hrow_, (void*)bat_hout_,
-                  (void*)bat_hmask_})
-    if (p) (void)hipFree(p);
-  if (bat_host_) (void)hipHostFree(bat_host_);
-  for (void* e : bat_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
-}
-
-// Scratch grown to the most rows seen: 8 B per row (E) and what the scan and the reduction ask for.
-bool EncodeDevice::reserve_batch(size_t rows) {
-  if (!bat_res_ && hipMalloc(&bat_res_, 32) != hipSuccess) return false;
-  if (!bat_host_ && hipHostMalloc(&bat_host_, 32, hipHostMallocDefault) != hipSuccess) return false;
-  for (void*& e : bat_ev_) {
-    if (e) continue;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e = ev;
-  }
-  if (bat_e_ == nullptr || rows > bat_rows_) {
-    size_t have = bat_e_ ? bat_rows_ + 1 : 0;
-    if (!grow(&bat_e_, &have, rows + 1)) {
-      bat_rows_ = 0;
-      return false;
-    }
-    bat_rows_ = rows;
-  }
-  const Rows rw{nullptr, 0, kNoLimit, 0, 0, 0, 0, 0};
-  size_t scan = 0, red = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}), bat_e_,
-                                       (u64)rows + 1) != hipSuccess)
-    return false;
-  if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}), bat_res_ + 2,
-                                (u64)std::max<size_t>(rows, 1)) != hipSuccess)
-    return false;
-  const size_t need = std::max<size_t>(std::max(scan, red), 16);
-  if (need > bat_tmp_bytes_) {
-    if (bat_tmp_) (void)hipFree(bat_tmp_);
-    bat_tmp_ = nullptr;
-    bat_tmp_bytes_ = 0;
-    if (hipMalloc(&bat_tmp_, need) != hipSuccess) return false;
-    bat_tmp_bytes_ = need;
-  }
-  return true;
-}
-
-int EncodeDevice::batch_lengths(const BatchCall& c, bool scan, void* stream, uint64_t* total, uint64_t* widest) {
-  hipStream_t st = (hipStream_t)stream;
-  const Rows rw = rows_of(c.o, c.row, c.n);
-  ENC_OK(hipMemsetAsync(bat_res_, 0, 32, st));
-  if (c.row) {
-    k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(rw, c.rows,
-                                                                                            c.ends ? 1 : 0, bat_res_);
-    ENC_OK(hipGetLastError());
-  } else if (rw.emit(0) > (u64)INT32_MAX) {
-    return -1;
-  }
-  size_t tmp = bat_tmp_bytes_;
-  if (scan) {
-    ENC_OK(hipcub::DeviceScan::InclusiveSum(bat_tmp_, tmp, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
-                                            bat_e_, c.rows + 1, st));
-    ENC_OK(hipMemcpyAsync(bat_host_, bat_e_ + c.rows, 8, hipMemcpyDeviceToHost, st));
-  } else if (c.rows) {
-    ENC_OK(hipcub::DeviceReduce::Max(bat_tmp_, tmp, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
-                                     bat_res_ + 2, c.rows, st));
-  }
-  ENC_OK(hipMemcpyAsync(bat_host_ + 1, bat_res_, 24, hipMemcpyDeviceToHost, st));
-  ENC_OK(hipStreamSynchronize(st));
-  if (bat_host_[1]) return -6;
-  if (bat_host_[2]) return -1;
-  *total = scan ? bat_host_[0] : 0;
-  *widest = bat_host_[3];
-  return 0;
-}
-
-int EncodeDevice::pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out,
-                             int32_t* lengths, uint8_t* mask, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// Pad needs no state: entry (r, c) depends on row r alone.
+int pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
+               uint8_t* mask, hipStream_t st) {
   const u64 total = c.rows * width;
   if (!total) {  // width == 0: every e_r is 0 and no lane owns a column
     if (lengths && c.rows) ENC_OK(hipMemsetAsync(lengths, 0, c.rows * 4, st));
@@ -438,24 +347,85 @@ int EncodeDevice::pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id,
   return 0;
 }
 
-int EncodeDevice::pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out,
-                              int32_t* pos, int32_t* seg, int64_t* row_start, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (row_start) {
-    k_bat_row_start<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(bat_e_, c.rows,
-                                                                                                 c.base, row_start);
-    ENC_OK(hipGetLastError());
+// The batch passes' state, allocated on the first pad / pack call.  Scratch grown to the most rows
+// seen: 8 B per row (E) and what the scan and the reduction ask for.
+struct BatchState : PassState {
+  DeviceBuf<u64> e;            // E[r]: stream offset of emitted row r; E[rows] = T
+  DeviceBuf<uint8_t> tmp;      // hipCUB scan / reduce scratch
+  DeviceWords res;             // [0] bad row_off, [1] an e_r past int32, [2] max e_r
+  PinnedWords host;            // T, then the three words of res
+  EventSet<4> ev;
+  // host-path staging: ids; row offsets then row_start (2 x hrow.cap()); a piece's int32 outputs:
+  // out, then pos / lengths, then seg (3 x hout.cap()); its mask
+  DeviceBuf<int32_t> hids;
+  DeviceBuf<int64_t> hrow;
+  DeviceBuf<int32_t> hout;
+  DeviceBuf<uint8_t> hmask;
+
+  bool reserve(size_t rows) {
+    if (!res.ensure(4) || !host.ensure(4) || !ev.ensure() || !e.grow(rows + 1)) return false;
+    const Rows rw{nullptr, 0, kNoLimit, 0, 0, 0, 0, 0};
+    size_t scan = 0, red = 0;
+    if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
+                                         e.get(), (u64)rows + 1) != hipSuccess)
+      return false;
+    if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
+                                  res.get() + 2, (u64)std::max<size_t>(rows, 1)) != hipSuccess)
+      return false;
+    return tmp.grow(std::max<size_t>(std::max(scan, red), 16));
   }
-  if (limit) {
+
+  // Row checks (when c.row), E into e (when scan) and max e_r over c's rows: 0, -1, -6.
+  int lengths(const BatchCall& c, bool scan, hipStream_t st, uint64_t* total, uint64_t* widest) {
     const Rows rw = rows_of(c.o, c.row, c.n);
-    const u64 tiles = (limit + kTile - 1) / kTile;
-    const uint32_t al = (aligned16(out) ? 1u : 0u) | (aligned16(pos) ? 2u : 0u) | (aligned16(seg) ? 4u : 0u);
-    k_bat_pack<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(c.ids, rw, c.rows, bat_e_, limit, pad_id, c.row_base,
-                                                                 out, pos, seg, al);
-    ENC_OK(hipGetLastError());
+    ENC_OK(hipMemsetAsync(res.get(), 0, 32, st));
+    if (c.row) {
+      k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(rw, c.rows,
+                                                                                              c.ends ? 1 : 0, res.get());
+      ENC_OK(hipGetLastError());
+    } else if (rw.emit(0) > (u64)INT32_MAX) {
+      return -1;
+    }
+    size_t bytes = tmp.cap();
+    if (scan) {
+      ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
+                                              e.get(), c.rows + 1, st));
+      ENC_OK(hipMemcpyAsync(host.get(), e.get() + c.rows, 8, hipMemcpyDeviceToHost, st));
+    } else if (c.rows) {
+      ENC_OK(hipcub::DeviceReduce::Max(tmp.get(), bytes, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
+                                       res.get() + 2, c.rows, st));
+    }
+    ENC_OK(hipMemcpyAsync(host.get() + 1, res.get(), 24, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    if (host[1]) return -6;
+    if (host[2]) return -1;
+    *total = scan ? host[0] : 0;
+    *widest = host[3];
+    return 0;
   }
-  return 0;
-}
+
+  // Stream positions [c.base, c.base + limit) into out / pos / seg (which point at position
+  // c.base), pad_id from the rows' end on; row_start[r] = c.base + E[r] for the call's rows.
+  int pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg,
+                  int64_t* row_start, hipStream_t st) {
+    if (row_start) {
+      k_bat_row_start<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(e.get(), c.rows,
+                                                                                                   c.base, row_start);
+      ENC_OK(hipGetLastError());
+    }
+    if (limit) {
+      const Rows rw = rows_of(c.o, c.row, c.n);
+      const u64 tiles = (limit + kTile - 1) / kTile;
+      const uint32_t al = (aligned16(out) ? 1u : 0u) | (aligned16(pos) ? 2u : 0u) | (aligned16(seg) ? 4u : 0u);
+      k_bat_pack<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(c.ids, rw, c.rows, e.get(), limit, pad_id,
+                                                                   c.row_base, out, pos, seg, al);
+      ENC_OK(hipGetLastError());
+    }
+    return 0;
+  }
+};
+
+}  // namespace
 
 int64_t EncodeDevice::pad(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                           size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths,
@@ -465,33 +435,28 @@ int64_t EncodeDevice::pad(const int32_t* ids, size_t n, const int64_t* row_off, 
   if (!rows_fit(R) || (width && R > (u64)INT64_MAX / width)) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  if (!reserve_batch(R)) {
+  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
+  if (!bs.reserve(R)) {
     std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
     return -1;
   }
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(bat_ev_);
+  const EventSet<4>& ev = bs.ev;
   const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
   u64 total = 0, widest = 0;
   ENC_OK(hipEventRecord(ev[0], st));
-  const int r = batch_lengths(c, false, st, &total, &widest);
+  const int r = bs.lengths(c, false, st, &total, &widest);
   if (r < 0) return r;
   ENC_OK(hipEventRecord(ev[1], st));
-  float a = 0, b = 0;
-  if (out && width >= widest && cap >= R * width) {
+  const bool expand = out && width >= widest && cap >= R * width;
+  if (expand) {
     if (!tiles_fit(R * width)) return -1;
     ENC_OK(hipEventRecord(ev[2], st));
     if (pad_expand(c, width, pad_id, pad_side, out, lengths, mask, st) < 0) return -1;
     ENC_OK(hipEventRecord(ev[3], st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (kernel_ms) ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-  } else {
-    ENC_OK(hipStreamSynchronize(st));
   }
-  if (kernel_ms) {
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    *kernel_ms = (double)a + (double)b;
-  }
+  ENC_OK(hipStreamSynchronize(st));
+  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
   return (int64_t)widest;
 }
 
@@ -503,36 +468,31 @@ int64_t EncodeDevice::pack(const int32_t* ids, size_t n, const int64_t* row_off,
   if (!rows_fit(R)) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  if (!reserve_batch(R)) {
+  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
+  if (!bs.reserve(R)) {
     std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
     return -1;
   }
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(bat_ev_);
+  const EventSet<4>& ev = bs.ev;
   const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
   u64 total = 0, widest = 0;
   ENC_OK(hipEventRecord(ev[0], st));
-  const int r = batch_lengths(c, true, st, &total, &widest);
+  const int r = bs.lengths(c, true, st, &total, &widest);
   if (r < 0) return r;
   ENC_OK(hipEventRecord(ev[1], st));
   const u64 L = seq_len;
   const u64 S = drop_last ? total / L : total / L + (total % L ? 1 : 0);
   if (S > (u64)INT64_MAX / L) return -1;
-  float a = 0, b = 0;
-  if (out && cap >= S * L) {
+  const bool expand = out && cap >= S * L;
+  if (expand) {
     if (!tiles_fit(S * L)) return -1;
     ENC_OK(hipEventRecord(ev[2], st));
-    if (pack_expand(c, S * L, pad_id, out, pos, seg, row_start, st) < 0) return -1;
+    if (bs.pack_expand(c, S * L, pad_id, out, pos, seg, row_start, st) < 0) return -1;
     ENC_OK(hipEventRecord(ev[3], st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (kernel_ms) ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-  } else {
-    ENC_OK(hipStreamSynchronize(st));
   }
-  if (kernel_ms) {
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    *kernel_ms = (double)a + (double)b;
-  }
+  ENC_OK(hipStreamSynchronize(st));
+  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
   return (int64_t)S;
 }
 
@@ -545,6 +505,7 @@ int EncodeDevice::pad_host(const int32_t* ids, size_t n, const int64_t* row_off,
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
   const size_t piece = piece_ids();
+  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
   hipStream_t st = (hipStream_t)stream_;
   std::vector<int64_t> local;
   for (size_t r0 = 0; r0 < R;) {
@@ -552,26 +513,24 @@ int EncodeDevice::pad_host(const int32_t* ids, size_t n, const int64_t* row_off,
     const size_t m = r1 - r0;
     const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
     const size_t cells = m * width;
-    if (!tiles_fit(cells) || !grow(&bat_hids_, &bat_hids_cap_, std::max<size_t>(len, 1)) ||
-        !grow(&bat_hrow_, &bat_hrow_cap_, m + 1, 2 * sizeof(int64_t)) ||
-        !grow(&bat_hout_, &bat_hout_cap_, std::max(cells, m), 3 * sizeof(int32_t)) ||
-        (mask && !grow(&bat_hmask_, &bat_hmask_cap_, std::max<size_t>(cells, 1)))) {
+    if (!tiles_fit(cells) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2) ||
+        !bs.hout.grow(std::max(cells, m), 3) || (mask && !bs.hmask.grow(std::max<size_t>(cells, 1)))) {
       std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
       return -1;
     }
-    if (len) ENC_OK(hipMemcpyAsync(bat_hids_, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    int32_t *const dids = bs.hids.get(), *const dout = bs.hout.get(), *const dlen = dout + bs.hout.cap();
+    if (len) ENC_OK(hipMemcpyAsync(dids, ids + a, len * 4, hipMemcpyHostToDevice, st));
     if (row_off) {
       local.resize(m + 1);
       for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(bat_hrow_, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
     }
-    int32_t* dlen = bat_hout_ + bat_hout_cap_;
-    const BatchCall c{bat_hids_, len, row_off ? bat_hrow_ : nullptr, m, false, o, 0, r0};
-    if (pad_expand(c, width, pad_id, pad_side, bat_hout_, lengths ? dlen : nullptr, mask ? bat_hmask_ : nullptr, st) < 0)
+    const BatchCall c{dids, len, row_off ? bs.hrow.get() : nullptr, m, false, o, 0, r0};
+    if (pad_expand(c, width, pad_id, pad_side, dout, lengths ? dlen : nullptr, mask ? bs.hmask.get() : nullptr, st) < 0)
       return -1;
-    if (cells) ENC_OK(hipMemcpyAsync(out + r0 * width, bat_hout_, cells * 4, hipMemcpyDeviceToHost, st));
+    if (cells) ENC_OK(hipMemcpyAsync(out + r0 * width, dout, cells * 4, hipMemcpyDeviceToHost, st));
     if (lengths) ENC_OK(hipMemcpyAsync(lengths + r0, dlen, m * 4, hipMemcpyDeviceToHost, st));
-    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + r0 * width, bat_hmask_, cells, hipMemcpyDeviceToHost, st));
+    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + r0 * width, bs.hmask.get(), cells, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
     r0 = r1;
   }
@@ -587,6 +546,7 @@ int EncodeDevice::pack_host(const int32_t* ids, size_t n, const int64_t* row_off
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
   const size_t piece = piece_ids();
+  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
   hipStream_t st = (hipStream_t)stream_;
   std::vector<int64_t> local;
   u64 done = 0;
@@ -595,34 +555,32 @@ int EncodeDevice::pack_host(const int32_t* ids, size_t n, const int64_t* row_off
     const size_t r1 = row_off ? piece_end(row_off, R, r0, piece, 0) : 1;
     const size_t m = r1 - r0;
     const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
-    if (!reserve_batch(m) || !grow(&bat_hids_, &bat_hids_cap_, std::max<size_t>(len, 1)) ||
-        !grow(&bat_hrow_, &bat_hrow_cap_, m + 1, 2 * sizeof(int64_t))) {
+    if (!bs.reserve(m) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2)) {
       std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
       return -1;
     }
-    if (len) ENC_OK(hipMemcpyAsync(bat_hids_, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    if (len) ENC_OK(hipMemcpyAsync(bs.hids.get(), ids + a, len * 4, hipMemcpyHostToDevice, st));
     if (row_off) {
       local.resize(m + 1);
       for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(bat_hrow_, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
     }
-    const BatchCall c{bat_hids_, len, row_off ? bat_hrow_ : nullptr, m, false, o, done, r0};
+    const BatchCall c{bs.hids.get(), len, row_off ? bs.hrow.get() : nullptr, m, false, o, done, r0};
     u64 total = 0, widest = 0;
-    if (batch_lengths(c, true, st, &total, &widest) < 0) return -1;  // (the caller has validated row_off)
+    if (bs.lengths(c, true, st, &total, &widest) < 0) return -1;  // (the caller has validated row_off)
     const u64 end = r1 == R ? out_len : std::min(done + total, out_len);
     const u64 limit = end > done ? end - done : 0;
-    if (!tiles_fit(limit) || !grow(&bat_hout_, &bat_hout_cap_, std::max<size_t>((size_t)limit, 1), 3 * sizeof(int32_t))) {
+    if (!tiles_fit(limit) || !bs.hout.grow(std::max<size_t>((size_t)limit, 1), 3)) {
       std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu entries)\n", (size_t)limit);
       return -1;
     }
-    int32_t* dpos = bat_hout_ + bat_hout_cap_;
-    int32_t* dseg = dpos + bat_hout_cap_;
-    int64_t* dstart = bat_hrow_ + bat_hrow_cap_;
-    if (pack_expand(c, limit, pad_id, bat_hout_, pos ? dpos : nullptr, seg ? dseg : nullptr,
-                    row_start ? dstart : nullptr, st) < 0)
+    int32_t *const dout = bs.hout.get(), *const dpos = dout + bs.hout.cap(), *const dseg = dpos + bs.hout.cap();
+    int64_t* dstart = bs.hrow.get() + bs.hrow.cap();
+    if (bs.pack_expand(c, limit, pad_id, dout, pos ? dpos : nullptr, seg ? dseg : nullptr,
+                       row_start ? dstart : nullptr, st) < 0)
       return -1;
     if (limit) {
-      ENC_OK(hipMemcpyAsync(out + done, bat_hout_, limit * 4, hipMemcpyDeviceToHost, st));
+      ENC_OK(hipMemcpyAsync(out + done, dout, limit * 4, hipMemcpyDeviceToHost, st));
       if (pos) ENC_OK(hipMemcpyAsync(pos + done, dpos, limit * 4, hipMemcpyDeviceToHost, st));
       if (seg) ENC_OK(hipMemcpyAsync(seg + done, dseg, limit * 4, hipMemcpyDeviceToHost, st));
     }

@@ -46,8 +46,10 @@
 #include "encode_common.h"
 
 namespace shred {
+namespace {
 
-struct EncodeDevice::DecodeCall {
+// One call's (or piece's) arguments, as the kernels take them.
+struct DecodeCall {
   const int32_t* ids;
   uint64_t n;
   const int64_t* row;  // nullptr, or rows + 1 entries
@@ -59,8 +61,6 @@ struct EncodeDevice::DecodeCall {
   uint64_t unk;        // the replacement's bytes, first in the low byte
   uint64_t base;       // added to every byte offset (bytes of the pieces before)
 };
-
-namespace {
 
 typedef uint64_t u64;
 
@@ -252,142 +252,111 @@ __global__ __launch_bounds__(kThreads) void k_dec_expand(const int32_t* __restri
   }
 }
 
-template <class T>
-bool grow(T** p, size_t* have, size_t want, size_t elem = sizeof(T)) {
-  if (want <= *have) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, want * elem) != hipSuccess) return false;
-  *have = want;
-  return true;
-}
+// The decode passes' state, allocated on the first decode call: the vocabulary, and scratch grown
+// to the largest call seen: 8 B per id (Q), 4 B per id once a call has rows and a separator
+// (mark), the scan's scratch.
+struct DecodeState : PassState {
+  uint32_t vocab = 0;             // 256 + M + the registered specials
+  DeviceBuf<uint32_t> tok_off;    // vocab + 1 offsets into arena
+  DeviceBuf<uint8_t> arena;       // the bytes of every token
+  DeviceBuf<u64> q;               // Q[k]: output offset of token k; Q[n] = the total
+  DeviceBuf<uint32_t> mark;       // rows that end just before id k (separators in front of it)
+  DeviceBuf<uint8_t> tmp;         // hipCUB scan scratch
+  DeviceWords err;                // [0] an id outside the vocabulary, [1] bad row_off
+  PinnedWords host;               // total, the two error words
+  EventSet<4> ev;
+  // host-path staging: ids, row offsets then byte offsets (2 x hrow.cap()), output bytes of a piece
+  DeviceBuf<int32_t> hids;
+  DeviceBuf<int64_t> hrow;
+  DeviceBuf<uint8_t> hout;
 
-}  // namespace
+  void specials_changed() override {  // the vocabulary holds the specials: rebuilt by the next call
+    tok_off.reset();
+    arena.reset();
+    vocab = 0;
+  }
 
-void EncodeDevice::free_decode() {
-  for (void* p : {(void*)dec_tok_off_, (void*)dec_arena_, (void*)dec_q_, (void*)dec_mark_, dec_tmp_, (void*)dec_err_,
-                  (void*)dec_hids_, (void*)dec_hrow_, (void*)dec_hout_})
-    if (p) (void)hipFree(p);
-  if (dec_host_) (void)hipHostFree(dec_host_);
-  for (void* e : dec_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
-}
-
-// The vocabulary on the first call; scratch grown to the largest call seen: 8 B per id (Q), 4 B
-// per id once a call has rows and a separator (mark), the scan's scratch.
-bool EncodeDevice::reserve_decode(size_t n, size_t rows, const std::vector<int32_t>& first,
-                                  const std::vector<int32_t>& second) {
-  if (!dec_tok_off_) {
-    std::vector<uint32_t> off;
-    std::vector<uint8_t> bytes;
-    if (!enc_build_arena(first, second, &off, &bytes)) return false;
-    for (size_t i = 0; i + 1 < sx_off_.size(); ++i) {  // the special tokens: ids 256 + M + i
-      bytes.insert(bytes.end(), sx_bytes_.begin() + sx_off_[i], sx_bytes_.begin() + sx_off_[i + 1]);
-      off.push_back((uint32_t)bytes.size());
+  // n ids, with marks when rows; the vocabulary is the merge list's, then the specials sx_bytes[sx_off[i] ..].
+  bool reserve(size_t n, size_t rows, const std::vector<int32_t>& first, const std::vector<int32_t>& second,
+               const std::vector<uint8_t>& sx_bytes, const std::vector<uint32_t>& sx_off) {
+    if (!tok_off.get()) {
+      std::vector<uint32_t> off;
+      std::vector<uint8_t> bytes;
+      if (!enc_build_arena(first, second, &off, &bytes)) return false;
+      for (size_t i = 0; i + 1 < sx_off.size(); ++i) {  // the special tokens: ids 256 + M + i
+        bytes.insert(bytes.end(), sx_bytes.begin() + sx_off[i], sx_bytes.begin() + sx_off[i + 1]);
+        off.push_back((uint32_t)bytes.size());
+      }
+      arena.reset();
+      if (!arena.grow(bytes.size()) || !tok_off.grow(off.size()) ||
+          hipMemcpy(arena.get(), bytes.data(), bytes.size(), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(tok_off.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        tok_off.reset();
+        return false;
+      }
+      vocab = (uint32_t)(off.size() - 1);
     }
-    if (hipMalloc(&dec_arena_, bytes.size()) != hipSuccess) return false;
-    if (hipMemcpy(dec_arena_, bytes.data(), bytes.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
-    uint32_t* t = nullptr;
-    if (hipMalloc(&t, off.size() * 4) != hipSuccess) return false;
-    if (hipMemcpy(t, off.data(), off.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(t);
+    if (!err.ensure(2) || !host.ensure(4) || !ev.ensure() || !q.grow(n + 1) || (rows && !mark.grow(n + 1))) return false;
+    size_t need = 0;
+    QInput in{nullptr, tok_off.get(), nullptr, (u64)n, vocab, 0, 0};
+    if (hipcub::DeviceScan::InclusiveSum(nullptr, need, QIter(hipcub::CountingInputIterator<u64>(0), in), q.get(),
+                                         (u64)n + 1) != hipSuccess)
       return false;
-    }
-    dec_tok_off_ = t;
-    dec_vocab_ = (uint32_t)(off.size() - 1);
+    return tmp.grow(std::max<size_t>(need, 16));
   }
-  if (!dec_err_ && hipMalloc(&dec_err_, 16) != hipSuccess) return false;
-  if (!dec_host_ && hipHostMalloc(&dec_host_, 32, hipHostMallocDefault) != hipSuccess) return false;
-  for (void*& e : dec_ev_) {
-    if (e) continue;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e = ev;
-  }
-  if (dec_q_ == nullptr || n > dec_ids_) {
-    size_t have = dec_q_ ? dec_ids_ + 1 : 0;
-    if (!grow(&dec_q_, &have, n + 1)) {
-      dec_ids_ = 0;
-      return false;
-    }
-    dec_ids_ = n;
-  }
-  if (rows && (dec_mark_ == nullptr || n > dec_marks_)) {
-    size_t have = dec_mark_ ? dec_marks_ + 1 : 0;
-    if (!grow(&dec_mark_, &have, n + 1)) {
-      dec_marks_ = 0;
-      return false;
-    }
-    dec_marks_ = n;
-  }
-  size_t need = 0;
-  QInput in{nullptr, dec_tok_off_, nullptr, (u64)n, dec_vocab_, 0, 0};
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, need, QIter(hipcub::CountingInputIterator<u64>(0), in), dec_q_,
-                                       (u64)n + 1) != hipSuccess)
-    return false;
-  need = std::max<size_t>(need, 16);
-  if (need > dec_tmp_bytes_) {
-    if (dec_tmp_) (void)hipFree(dec_tmp_);
-    dec_tmp_ = nullptr;
-    dec_tmp_bytes_ = 0;
-    if (hipMalloc(&dec_tmp_, need) != hipSuccess) return false;
-    dec_tmp_bytes_ = need;
-  }
-  return true;
-}
 
-int EncodeDevice::decode_lengths(const DecodeCall& c, void* stream, uint64_t* total) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool marks = c.sep >= 0 && c.row && c.rows;
-  ENC_OK(hipMemsetAsync(dec_err_, 0, 16, st));
-  if (c.unk_len < 0 && c.n) {
-    k_dec_check<<<dim3((unsigned)((c.n + kChunk - 1) / kChunk)), dim3(kThreads), 0, st>>>(c.ids, c.n, dec_vocab_,
-                                                                                          dec_err_);
-    ENC_OK(hipGetLastError());
+  // Length passes over c's device ids and row offsets (whose end points are checked when c.ends):
+  // Q into q, *total = the bytes needed.  0, -1, -6.
+  int lengths(const DecodeCall& c, hipStream_t st, uint64_t* total) {
+    const bool marks = c.sep >= 0 && c.row && c.rows;
+    ENC_OK(hipMemsetAsync(err.get(), 0, 16, st));
+    if (c.unk_len < 0 && c.n) {
+      k_dec_check<<<dim3((unsigned)((c.n + kChunk - 1) / kChunk)), dim3(kThreads), 0, st>>>(c.ids, c.n, vocab,
+                                                                                            err.get());
+      ENC_OK(hipGetLastError());
+    }
+    if (marks) ENC_OK(hipMemsetAsync(mark.get(), 0, (c.n + 1) * 4, st));
+    if (c.row) {
+      k_dec_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(
+          c.row, c.rows, c.n, c.ends ? 1 : 0, marks ? mark.get() : nullptr, err.get());
+      ENC_OK(hipGetLastError());
+    }
+    QInput in{c.ids, tok_off.get(), marks ? mark.get() : nullptr, c.n, vocab,
+              c.unk_len > 0 ? (uint32_t)c.unk_len : 0u, c.tail};
+    size_t bytes = tmp.cap();
+    ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, QIter(hipcub::CountingInputIterator<u64>(0), in),
+                                            q.get(), c.n + 1, st));
+    ENC_OK(hipMemcpyAsync(host.get(), q.get() + c.n, 8, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipMemcpyAsync(host.get() + 1, err.get(), 16, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    if (host[2]) return -6;
+    if (host[1]) return -1;
+    *total = host[0];
+    return 0;
   }
-  if (marks) ENC_OK(hipMemsetAsync(dec_mark_, 0, (c.n + 1) * 4, st));
-  if (c.row) {
-    k_dec_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(
-        c.row, c.rows, c.n, c.ends ? 1 : 0, marks ? dec_mark_ : nullptr, dec_err_);
-    ENC_OK(hipGetLastError());
-  }
-  QInput in{c.ids, dec_tok_off_, marks ? dec_mark_ : nullptr, c.n, dec_vocab_,
-            c.unk_len > 0 ? (uint32_t)c.unk_len : 0u, c.tail};
-  size_t tmp = dec_tmp_bytes_;
-  ENC_OK(hipcub::DeviceScan::InclusiveSum(dec_tmp_, tmp, QIter(hipcub::CountingInputIterator<u64>(0), in), dec_q_,
-                                          c.n + 1, st));
-  ENC_OK(hipMemcpyAsync(dec_host_, dec_q_ + c.n, 8, hipMemcpyDeviceToHost, st));
-  ENC_OK(hipMemcpyAsync(dec_host_ + 1, dec_err_, 16, hipMemcpyDeviceToHost, st));
-  ENC_OK(hipStreamSynchronize(st));
-  if (dec_host_[2]) return -6;
-  if (dec_host_[1]) return -1;
-  *total = dec_host_[0];
-  return 0;
-}
 
-int EncodeDevice::decode_expand(const DecodeCall& c, uint64_t total, uint8_t* out, int64_t* byte_off, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (byte_off) {
-    if (c.row)
-      k_dec_byte_off<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(
-          c.row, c.rows, dec_q_, c.sep >= 0 ? 1 : 0, c.base, byte_off);
-    else
-      k_dec_ends<<<dim3(1), dim3(64), 0, st>>>(byte_off, c.base, total);
-    ENC_OK(hipGetLastError());
+  // byte_off (nullptr, or as the header defines it, plus c.base) and the total bytes into out.
+  int expand(const DecodeCall& c, uint64_t total, uint8_t* out, int64_t* byte_off, hipStream_t st) {
+    if (byte_off) {
+      if (c.row)
+        k_dec_byte_off<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(
+            c.row, c.rows, q.get(), c.sep >= 0 ? 1 : 0, c.base, byte_off);
+      else
+        k_dec_ends<<<dim3(1), dim3(64), 0, st>>>(byte_off, c.base, total);
+      ENC_OK(hipGetLastError());
+    }
+    if (total) {
+      const u64 tiles = (total + kTile - 1) / kTile;
+      const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+      (aligned ? k_dec_expand<true> : k_dec_expand<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
+          c.ids, c.n, q.get(), tok_off.get(), arena.get(), vocab, c.unk_len > 0 ? (uint32_t)c.unk_len : 0u, c.unk,
+          c.sep >= 0 ? (uint32_t)c.sep : 0u, out, total);
+      ENC_OK(hipGetLastError());
+    }
+    return 0;
   }
-  if (total) {
-    const u64 tiles = (total + kTile - 1) / kTile;
-    const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    (aligned ? k_dec_expand<true> : k_dec_expand<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
-        c.ids, c.n, dec_q_, dec_tok_off_, dec_arena_, dec_vocab_, c.unk_len > 0 ? (uint32_t)c.unk_len : 0u, c.unk,
-        c.sep >= 0 ? (uint32_t)c.sep : 0u, out, total);
-    ENC_OK(hipGetLastError());
-  }
-  return 0;
-}
+};
 
-namespace {
 u64 pack_unk(const uint8_t* unk, int unk_len) {
   u64 v = 0;
   for (int i = 0; i < unk_len; ++i) v |= (u64)unk[i] << (8 * i);
@@ -405,34 +374,29 @@ int64_t EncodeDevice::decode(const int32_t* ids, size_t n, const int64_t* row_of
   if (!grids_fit(n, rows)) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  if (!reserve_decode(n, row_off && sep >= 0 ? rows : 0, first, second)) {
+  DecodeState& ds = pass_state<DecodeState>(pass_[kDecode]);
+  if (!ds.reserve(n, row_off && sep >= 0 ? rows : 0, first, second, sx_bytes_, sx_off_)) {
     std::fprintf(stderr, "[ERROR]\t encoder: decode allocation failed (%zu ids)\n", n);
     return -1;
   }
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(dec_ev_);
+  const EventSet<4>& ev = ds.ev;
   const DecodeCall c{ids, n, row_off, rows, true, (!row_off && sep >= 0) ? 1u : 0u, sep, unk_len,
                      pack_unk(unk, unk_len), 0};
   u64 total = 0;
   ENC_OK(hipEventRecord(ev[0], st));
-  const int r = decode_lengths(c, st, &total);
+  const int r = ds.lengths(c, st, &total);
   if (r < 0) return r;
   ENC_OK(hipEventRecord(ev[1], st));
-  float a = 0, b = 0;
-  if (out && total <= cap) {
+  const bool expand = out && total <= cap;
+  if (expand) {
     if (total / kTile >= 0x7FFFFFFFull) return -1;
     ENC_OK(hipEventRecord(ev[2], st));
-    if (decode_expand(c, total, out, byte_off, st) < 0) return -1;
+    if (ds.expand(c, total, out, byte_off, st) < 0) return -1;
     ENC_OK(hipEventRecord(ev[3], st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (kernel_ms) ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-  } else {
-    ENC_OK(hipStreamSynchronize(st));
   }
-  if (kernel_ms) {
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    *kernel_ms = (double)a + (double)b;
-  }
+  ENC_OK(hipStreamSynchronize(st));
+  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
   return (int64_t)total;
 }
 
@@ -446,10 +410,8 @@ int64_t EncodeDevice::decode_host(const int32_t* ids, size_t n, const int64_t* r
   if (!grids_fit(n, rows)) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  size_t piece = kDecodePiece;
-  if (const char* e = std::getenv("SHREDWORD_DECODE_PIECE"))  // tests: small pieces
-    piece = std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), 1);
-  piece = std::min(piece, std::max<size_t>(n, 1));
+  const size_t piece = std::min(piece_from_env("SHREDWORD_DECODE_PIECE", kDecodePiece, 1), std::max<size_t>(n, 1));
+  DecodeState& ds = pass_state<DecodeState>(pass_[kDecode]);
   hipStream_t st = (hipStream_t)stream_;
   const u64 unk_bytes = pack_unk(unk, unk_len);
   std::vector<int64_t> local;
@@ -463,26 +425,26 @@ int64_t EncodeDevice::decode_host(const int32_t* ids, size_t n, const int64_t* r
     if (row_off)
       for (; r_end <= rows && (size_t)row_off[r_end] <= b; ++r_end) local.push_back(row_off[r_end] - (int64_t)a);
     const size_t m = r_end - r_next;
-    if (!reserve_decode(len, sep >= 0 ? m : 0, first, second) || !grow(&dec_hids_, &dec_hids_cap_, std::max(len, piece)) ||
-        !grow(&dec_hrow_, &dec_hrow_cap_, m + 1, 2 * sizeof(int64_t))) {
+    if (!ds.reserve(len, sep >= 0 ? m : 0, first, second, sx_bytes_, sx_off_) || !ds.hids.grow(std::max(len, piece)) ||
+        !ds.hrow.grow(m + 1, 2)) {
       std::fprintf(stderr, "[ERROR]\t encoder: decode allocation failed (%zu ids)\n", len);
       return -1;
     }
-    int64_t* drow = dec_hrow_;
-    int64_t* dboff = dec_hrow_ + dec_hrow_cap_;
-    if (len) ENC_OK(hipMemcpyAsync(dec_hids_, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    int64_t* drow = ds.hrow.get();
+    int64_t* dboff = drow + ds.hrow.cap();
+    if (len) ENC_OK(hipMemcpyAsync(ds.hids.get(), ids + a, len * 4, hipMemcpyHostToDevice, st));
     if (m) ENC_OK(hipMemcpyAsync(drow, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    const DecodeCall c{dec_hids_, len, m ? drow : nullptr, m, false, (!row_off && sep >= 0 && b == n) ? 1u : 0u,
+    const DecodeCall c{ds.hids.get(), len, m ? drow : nullptr, m, false, (!row_off && sep >= 0 && b == n) ? 1u : 0u,
                        sep, unk_len, unk_bytes, done};
     u64 total = 0;
-    if (decode_lengths(c, st, &total) < 0) return -1;  // (the caller has validated ids and row_off)
-    if (!grow(&dec_hout_, &dec_hout_cap_, (size_t)total)) {
+    if (ds.lengths(c, st, &total) < 0) return -1;  // (the caller has validated ids and row_off)
+    if (!ds.hout.grow((size_t)total)) {
       std::fprintf(stderr, "[ERROR]\t encoder: decode staging allocation failed (%zu bytes)\n", (size_t)total);
       return -1;
     }
     if (total / kTile >= 0x7FFFFFFFull) return -1;
-    if (decode_expand(c, total, dec_hout_, byte_off && m ? dboff : nullptr, st) < 0) return -1;
-    if (total) ENC_OK(hipMemcpyAsync(out + done, dec_hout_, total, hipMemcpyDeviceToHost, st));
+    if (ds.expand(c, total, ds.hout.get(), byte_off && m ? dboff : nullptr, st) < 0) return -1;
+    if (total) ENC_OK(hipMemcpyAsync(out + done, ds.hout.get(), total, hipMemcpyDeviceToHost, st));
     if (byte_off && m) ENC_OK(hipMemcpyAsync(byte_off + r_next, dboff + 1, m * 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
     done += total;

@@ -115,6 +115,38 @@ struct GlobalRef {
   __device__ __forceinline__ int& operator()(int j) const { return base[j]; }
 };
 
+// The ids of the word text[s .. s + L), L <= kEncMaxWord, to dst = out + at; returns how many.  A
+// word of at most kStrip bytes merges on the thread's LDS strip (s_strip is the workgroup's).  A
+// longer one merges in global scratch, tokens at gtok and ranks at grank, and is then copied to dst
+// in ascending order: gtok is dst itself (no copy) or lies at or behind it.  (out and at apart:
+// the direct path's kernel keeps two registers fewer than with the pointer formed by the caller.)
+template <bool kPacked>
+__device__ __forceinline__ int encode_word(const uint8_t* __restrict__ text, u64 s, int L, const int* s_map,
+                                           int* s_strip, int tid, const u64* __restrict__ tab, u64 mask,
+                                           int32_t* gtok, int32_t* grank, int32_t* out, u64 at) {
+  int m;
+  if (L <= kStrip) {
+    if (kPacked) {
+      uint32_t* e = reinterpret_cast<uint32_t*>(s_strip) + tid;
+      for (int k = 0; k < L; ++k) e[k * kThreads] = (uint32_t)s_map[text[s + k]] << 16;
+      m = merge_word_packed(e, L, tab, mask);
+      for (int k = 0; k < m; ++k) out[at + k] = (int)(e[k * kThreads] >> 16);
+    } else {
+      LdsRef tok{s_strip + tid}, rk{s_strip + kStrip * kThreads + tid};
+      for (int k = 0; k < L; ++k) tok(k) = s_map[text[s + k]];
+      m = merge_word(tok, rk, L, tab, mask);
+      for (int k = 0; k < m; ++k) out[at + k] = tok(k);
+    }
+  } else {
+    GlobalRef gt{gtok}, gr{grank};
+    for (int k = 0; k < L; ++k) gt(k) = s_map[text[s + k]];
+    m = merge_word(gt, gr, L, tab, mask);
+    if (gtok != out + at)
+      for (int k = 0; k < m; ++k) out[at + k] = gt(k);
+  }
+  return m;
+}
+
 template <bool kAligned, bool kPacked>
 __global__ __launch_bounds__(kThreads) void k_encode_words(const uint8_t* __restrict__ text, u64 n,
                                                            const int32_t* __restrict__ byte_map,
@@ -148,7 +180,6 @@ __global__ __launch_bounds__(kThreads) void k_encode_words(const uint8_t* __rest
     uint32_t starts = ~dm & ((dm << 1) | prevd);
     if (starts) j0 = __ffs(starts) - 1;
     u64 wpos = base + j0;
-    LdsRef tok{s_strip + tid}, rk{s_strip + kStrip * kThreads + tid};
     while (starts) {
       const int j = __ffs(starts) - 1;
       starts &= starts - 1;
@@ -166,24 +197,8 @@ __global__ __launch_bounds__(kThreads) void k_encode_words(const uint8_t* __rest
         atomicOr(reinterpret_cast<unsigned long long*>(misc + 1), 1ull);
         continue;
       }
-      int m;
-      if (L <= (u64)kStrip) {
-        if (kPacked) {
-          uint32_t* e = reinterpret_cast<uint32_t*>(s_strip) + tid;
-          for (int k = 0; k < (int)L; ++k) e[k * kThreads] = (uint32_t)s_map[text[s + k]] << 16;
-          m = merge_word_packed(e, (int)L, tab, mask);
-          for (int k = 0; k < m; ++k) pad[wpos + k] = (int)(e[k * kThreads] >> 16);
-        } else {
-          for (int k = 0; k < (int)L; ++k) tok(k) = s_map[text[s + k]];
-          m = merge_word(tok, rk, (int)L, tab, mask);
-          for (int k = 0; k < m; ++k) pad[wpos + k] = tok(k);
-        }
-      } else {
-        GlobalRef gt{pad + s}, gr{rank + s};
-        for (int k = 0; k < (int)L; ++k) gt(k) = s_map[text[s + k]];
-        m = merge_word(gt, gr, (int)L, tab, mask);
-        for (int k = 0; k < m; ++k) pad[wpos + k] = gt(k);  // wpos <= s: ascending copy is safe
-      }
+      // a long word's tokens at pad + s: wpos <= s, so the ascending copy to pad + wpos is safe
+      const int m = encode_word<kPacked>(text, s, (int)L, s_map, s_strip, tid, tab, mask, pad + s, rank + s, pad, wpos);
       wpos += m;
       cnt += m;
     }
@@ -299,24 +314,8 @@ __global__ __launch_bounds__(kThreads) void k_cache_encode(const uint8_t* __rest
     return;
   }
   int32_t* ids = arena + off + 1;
-  int m;
-  if (L <= kStrip) {
-    if (kPacked) {
-      uint32_t* q = reinterpret_cast<uint32_t*>(s_strip) + tid;
-      for (int k = 0; k < L; ++k) q[k * kThreads] = (uint32_t)s_map[text[s + k]] << 16;
-      m = merge_word_packed(q, L, tab, mask);
-      for (int k = 0; k < m; ++k) ids[k] = (int)(q[k * kThreads] >> 16);
-    } else {
-      LdsRef tok{s_strip + tid}, rk{s_strip + kStrip * kThreads + tid};
-      for (int k = 0; k < L; ++k) tok(k) = s_map[text[s + k]];
-      m = merge_word(tok, rk, L, tab, mask);
-      for (int k = 0; k < m; ++k) ids[k] = tok(k);
-    }
-  } else {  // tokens in the arena entry, ranks in scratch at the word's own text offset
-    GlobalRef gt{ids}, gr{rank + s};
-    for (int k = 0; k < L; ++k) gt(k) = s_map[text[s + k]];
-    m = merge_word(gt, gr, L, tab, mask);
-  }
+  // a long word's tokens in the arena entry itself, its ranks in scratch at the word's own text offset
+  const int m = encode_word<kPacked>(text, s, L, s_map, s_strip, tid, tab, mask, ids, rank + s, ids, 0);
   uint32_t* bytes = reinterpret_cast<uint32_t*>(ids + m);
   for (int k = 0; k < L; k += 4) {
     uint32_t w = 0;
@@ -397,15 +396,8 @@ __global__ __launch_bounds__(kThreads) void k_cache_words(const uint8_t* __restr
     ++nw;
     cnt += m;
   });
-  // block-inclusive scan of the per-thread id counts
-  s_inc[tid] = cnt;
-  __syncthreads();
-  for (int d = 1; d < kThreads; d <<= 1) {
-    const uint32_t v = tid >= d ? s_inc[tid - d] : 0;
-    __syncthreads();
-    s_inc[tid] += v;
-    __syncthreads();
-  }
+  s_inc[tid] = cnt;  // the per-thread id counts
+  block_inclusive_scan(s_inc, tid);
   if (tid == 0) {
     const u64 agg = s_inc[kThreads - 1];
     u64 prefix = 0;
@@ -459,27 +451,62 @@ __global__ __launch_bounds__(kThreads) void k_encode_emit(const int32_t* __restr
   const uint32_t t = tcnt[(u64)blockIdx.x * kThreads + tid];
   const uint32_t cnt = t >> 5;
   s_inc[tid] = cnt;
-  __syncthreads();
-  for (int d = 1; d < kThreads; d <<= 1) {
-    const uint32_t v = tid >= d ? s_inc[tid - d] : 0;
-    __syncthreads();
-    s_inc[tid] += v;
-    __syncthreads();
-  }
+  block_inclusive_scan(s_inc, tid);
   s_src[tid] = tid * kSpan + (int)(t & 31u) - (int)(s_inc[tid] - cnt);
   __syncthreads();
   const uint32_t total = s_inc[kThreads - 1];
   const u64 base = (u64)blockIdx.x * kChunk;
   int32_t* dst = out + (bcnt[blockIdx.x] - total);  // bcnt: inclusive block sums
   for (uint32_t i = tid; i < total; i += kThreads) {
-    int lo = 0, hi = kThreads - 1;  // first thread whose inclusive count exceeds i
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (s_inc[mid] > i) hi = mid; else lo = mid + 1;
-    }
-    dst[i] = pad[(int64_t)base + s_src[lo] + (int64_t)i];
+    dst[i] = pad[(int64_t)base + s_src[first_above(s_inc, i, ~0u)] + (int64_t)i];
   }
 }
+
+// The core encoder's state: what create() uploads, and scratch sized for the largest text seen.
+struct CoreState : PassState {
+  DeviceBuf<u64> table;        // the merge-rank table (host/encoder.h)
+  DeviceBuf<int32_t> byte_map;
+  DeviceWords misc;            // [0] total ids, [1] flags: 1 long word, 2 probe window full, 4 collision,
+                               // 8 arena full, 16 output capacity; [2] word-cache arena top
+  PinnedWords host_misc;       // misc's first two words
+  EventSet<4> ev;
+  size_t cap_bytes = 0;        // text bytes the scratch below is sized for
+  DeviceBuf<int32_t> pad;      // ids per word span
+  DeviceBuf<int32_t> rank;     // rank cache of long words; the word cache's arena
+  DeviceBuf<uint32_t> tcnt;    // per-thread counts
+  DeviceBuf<u64> bcnt;         // [0, nb) block counts, [nb, 2 nb) inclusive sums, [2 nb, 3 nb] the
+                               // look-back states and the ticket of k_cache_words
+  DeviceBuf<uint8_t> scan_tmp;  // hipCUB scan scratch
+  size_t scan_tmp_bytes = 0;
+  // word cache: one 64-byte slot per distinct word (the layout: kSlotU64 above); the arena is rank
+  size_t ccap = 0, ccap_min = 0;  // allocated slots; slots a call starts with
+  DeviceBuf<u64> cslot;
+
+  bool reserve(size_t n, std::string* why) {
+    if (n <= cap_bytes) return true;
+    cap_bytes = 0;
+    const size_t nb = (n + kChunk - 1) / kChunk, cap = nb * kChunk;  // every later n <= cap fits
+    // word-cache slots: the table is allocated for one slot per 256 text bytes; a call starts with
+    // one per 4096 (a small table keeps the probed lines cache-resident) and grows it 4x while a
+    // probe window overflows, then takes the direct path
+    ccap = 1 << 20;
+    while (ccap < cap / 256) ccap <<= 1;
+    ccap_min = 1 << 20;
+    while (ccap_min < cap / 4096) ccap_min <<= 1;
+    if (!cslot.grow(ccap * kSlotU64)) {
+      *why = "word-cache allocation failed";
+      return false;
+    }
+    if (!pad.grow(cap) || !rank.grow(cap) || !tcnt.grow(nb * kThreads) || !bcnt.grow(3 * nb + 1) ||
+        hipcub::DeviceScan::InclusiveSum(nullptr, scan_tmp_bytes, bcnt.get(), bcnt.get() + nb, (int)nb) != hipSuccess ||
+        !scan_tmp.grow(scan_tmp_bytes ? scan_tmp_bytes : 16)) {
+      *why = "scratch allocation failed";
+      return false;
+    }
+    cap_bytes = cap;
+    return true;
+  }
+};
 
 }  // namespace
 
@@ -511,17 +538,11 @@ EncodeDevice* EncodeDevice::create(int device, const std::vector<uint64_t>& tabl
   hipStream_t st = nullptr;
   bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
   d->stream_ = st;
-  ok = ok && hipMalloc(&d->table_, table.size() * 8) == hipSuccess;
-  ok = ok && hipMalloc(&d->byte_map_, 256 * 4) == hipSuccess;
-  ok = ok && hipMalloc(&d->misc_, 32) == hipSuccess;
-  ok = ok && hipHostMalloc(&d->host_misc_, 16, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMemcpy(d->table_, table.data(), table.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipMemcpy(d->byte_map_, byte_map, 256 * 4, hipMemcpyHostToDevice) == hipSuccess;
-  for (int i = 0; i < 4 && ok; ++i) {
-    hipEvent_t e;
-    ok = hipEventCreate(&e) == hipSuccess;
-    d->ev_[i] = e;
-  }
+  CoreState& c = pass_state<CoreState>(d->pass_[kCore]);
+  ok = ok && c.table.grow(table.size()) && c.byte_map.grow(256) && c.misc.ensure(4) && c.host_misc.ensure(2);
+  ok = ok && hipMemcpy(c.table.get(), table.data(), table.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipMemcpy(c.byte_map.get(), byte_map, 256 * 4, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && c.ev.ensure();
   if (!ok) {
     *why = "device allocation failed";
     delete d;
@@ -533,51 +554,8 @@ EncodeDevice* EncodeDevice::create(int device, const std::vector<uint64_t>& tabl
 EncodeDevice::~EncodeDevice() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
-  free_spans();
-  free_special();
-  free_docs();
-  free_decode();
-  free_batch();
-  for (void* p : {(void*)table_, (void*)byte_map_, (void*)misc_, (void*)pad_, (void*)rank_, (void*)tcnt_,
-                  (void*)bcnt_, (void*)dtext_, (void*)dout_, (void*)cslot_, scan_tmp_})
-    if (p) (void)hipFree(p);
-  if (host_misc_) (void)hipHostFree(host_misc_);
-  for (void* e : ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
+  for (auto& p : pass_) p.reset();
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
-}
-
-bool EncodeDevice::reserve(size_t n, std::string* why) {
-  if (n <= cap_bytes_) return true;
-  for (void* p : {(void*)pad_, (void*)rank_, (void*)tcnt_, (void*)bcnt_, (void*)cslot_, scan_tmp_})
-    if (p) (void)hipFree(p);
-  scan_tmp_ = nullptr;
-  pad_ = rank_ = nullptr;
-  cslot_ = nullptr;
-  tcnt_ = nullptr;
-  bcnt_ = nullptr;
-  cap_bytes_ = 0;
-  const size_t nb = (n + kChunk - 1) / kChunk, cap = nb * kChunk;  // every later n <= cap fits
-  // word-cache slots: the table is allocated for one slot per 256 text bytes; a call starts with
-  // one per 4096 (a small table keeps the probed lines cache-resident) and grows it 4x while a
-  // probe window overflows, then takes the direct path
-  ccap_ = 1 << 20;
-  while (ccap_ < cap / 256) ccap_ <<= 1;
-  ccap_min_ = 1 << 20;
-  while (ccap_min_ < cap / 4096) ccap_min_ <<= 1;
-  if (hipMalloc(&cslot_, ccap_ * kSlotU64 * 8) != hipSuccess) {
-    *why = "word-cache allocation failed";
-    return false;
-  }
-  if (hipMalloc(&pad_, cap * 4) != hipSuccess || hipMalloc(&rank_, cap * 4) != hipSuccess ||
-      hipMalloc(&tcnt_, nb * kThreads * 4) != hipSuccess || hipMalloc(&bcnt_, (3 * nb + 1) * 8) != hipSuccess ||
-      hipcub::DeviceScan::InclusiveSum(nullptr, scan_tmp_bytes_, bcnt_, bcnt_ + nb, (int)nb) != hipSuccess ||
-      hipMalloc(&scan_tmp_, scan_tmp_bytes_ ? scan_tmp_bytes_ : 16) != hipSuccess) {
-    *why = "scratch allocation failed";
-    return false;
-  }
-  cap_bytes_ = cap;
-  return true;
 }
 
 int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms) {
@@ -587,63 +565,65 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
   std::string why;
-  if (!reserve(n, &why)) {
+  CoreState& c = pass_state<CoreState>(pass_[kCore]);
+  if (!c.reserve(n, &why)) {
     std::fprintf(stderr, "[ERROR]\t encoder: %s (%zu bytes)\n", why.c_str(), n);
     return -1;
   }
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
   const u64 nb = (n + kChunk - 1) / kChunk;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(ev_);
   const char* env = std::getenv("SHREDWORD_ENCODE_CACHE");
   bool cached = !(env && env[0] == '0');
-  ENC_OK(hipEventRecord(ev[0], st));
-  size_t cc = ccap_min_, cmax = ccap_;
-  // tests: "<start>[:<max>]" slots for this call (powers of two in [kThreads, ccap_]: the encode
+  ENC_OK(hipEventRecord(c.ev[0], st));
+  size_t cc = c.ccap_min, cmax = c.ccap;
+  // tests: "<start>[:<max>]" slots for this call (powers of two in [kThreads, ccap]: the encode
   // grid is cc / kThreads and the probe mask cc - 1), so a few thousand words reach the growth
   // branch and the overflow after it
   if (const char* e = std::getenv("SHREDWORD_ENCODE_CACHE_SLOTS")) {
     auto slots = [&](const char* s) {
       const unsigned long long want = std::strtoull(s, nullptr, 10);
       size_t v = kThreads;
-      while (v < ccap_ && v < want) v <<= 1;
+      while (v < c.ccap && v < want) v <<= 1;
       return v;
     };
     cc = slots(e);
     const char* colon = std::strchr(e, ':');
-    cmax = colon ? std::max(cc, slots(colon + 1)) : ccap_;
+    cmax = colon ? std::max(cc, slots(colon + 1)) : c.ccap;
   }
   const bool debug = std::getenv("SHREDWORD_ENCODE_DEBUG") != nullptr;
+  u64 *const misc = c.misc.get(), *const cslot = c.cslot.get(), *const bcnt = c.bcnt.get();
+  int32_t *const pad = c.pad.get(), *const rank = c.rank.get();
   for (;;) {
-    ENC_OK(hipMemsetAsync(misc_, 0, 32, st));
+    ENC_OK(hipMemsetAsync(misc, 0, 32, st));
     if (cached) {
-      ENC_OK(hipMemsetAsync(cslot_, 0, cc * kSlotU64 * 8, st));
-      k_cache_insert<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot_, cc - 1, misc_);
+      ENC_OK(hipMemsetAsync(cslot, 0, cc * kSlotU64 * 8, st));
+      k_cache_insert<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, misc);
       ENC_OK(hipGetLastError());
       auto enck = packed_ ? k_cache_encode<true> : k_cache_encode<false>;
       // arena offsets must stay below 2^31: bit 31 of a payload tags "ids inline in the slot", so
       // a larger arena flags "arena full" and the call reruns on the direct path
-      const u64 arena_cap = std::min<u64>(cap_bytes_, (u64)1 << 31);
-      enck<<<dim3((unsigned)(cc / kThreads)), dim3(kThreads), 0, st>>>(text, n, byte_map_, table_, mask_, cslot_, cc,
-                                                                       rank_, arena_cap, pad_, misc_);
+      const u64 arena_cap = std::min<u64>(c.cap_bytes, (u64)1 << 31);
+      enck<<<dim3((unsigned)(cc / kThreads)), dim3(kThreads), 0, st>>>(text, n, c.byte_map.get(), c.table.get(), mask_,
+                                                                       cslot, cc, rank, arena_cap, pad, misc);
       ENC_OK(hipGetLastError());
-      // look-back states and the ticket (bcnt_[2 nb, 3 nb], zero = "not published")
-      ENC_OK(hipMemsetAsync(bcnt_ + 2 * nb, 0, (nb + 1) * 8, st));
-      k_cache_words<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot_, cc - 1, rank_, out, (u64)cap, bcnt_,
-                                                                   bcnt_ + 2 * nb, nb, misc_);
+      // look-back states and the ticket (bcnt[2 nb, 3 nb], zero = "not published")
+      ENC_OK(hipMemsetAsync(bcnt + 2 * nb, 0, (nb + 1) * 8, st));
+      k_cache_words<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, rank, out, (u64)cap, bcnt,
+                                                                   bcnt + 2 * nb, nb, misc);
     } else {
       const bool aligned = (reinterpret_cast<uintptr_t>(text) & 15) == 0;
       auto kern = aligned ? (packed_ ? k_encode_words<true, true> : k_encode_words<true, false>)
                           : (packed_ ? k_encode_words<false, true> : k_encode_words<false, false>);
-      kern<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, byte_map_, table_, mask_, pad_, rank_, tcnt_,
-                                                          bcnt_, misc_);
+      kern<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, c.byte_map.get(), c.table.get(), mask_, pad, rank,
+                                                          c.tcnt.get(), bcnt, misc);
     }
     ENC_OK(hipGetLastError());
-    // inclusive block sums into bcnt_[nb, 2 nb); the last one is the total
-    ENC_OK(hipcub::DeviceScan::InclusiveSum(scan_tmp_, scan_tmp_bytes_, bcnt_, bcnt_ + nb, (int)nb, st));
-    ENC_OK(hipMemcpyAsync(misc_, bcnt_ + 2 * nb - 1, 8, hipMemcpyDeviceToDevice, st));
-    ENC_OK(hipMemcpyAsync(host_misc_, misc_, 16, hipMemcpyDeviceToHost, st));
+    // inclusive block sums into bcnt[nb, 2 nb); the last one is the total
+    ENC_OK(hipcub::DeviceScan::InclusiveSum(c.scan_tmp.get(), c.scan_tmp_bytes, bcnt, bcnt + nb, (int)nb, st));
+    ENC_OK(hipMemcpyAsync(misc, bcnt + 2 * nb - 1, 8, hipMemcpyDeviceToDevice, st));
+    ENC_OK(hipMemcpyAsync(c.host_misc.get(), misc, 16, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
-    const uint64_t fl = host_misc_[1];
+    const uint64_t fl = c.host_misc[1];
     if (fl & 1) return -3;
     if (fl & 16) return -2;  // the output capacity (the cached path writes it directly)
     if (!(fl & 14)) break;
@@ -660,34 +640,17 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
                    fl & 8 ? "arena overflow" : fl & 4 ? "hash collision" : "overflow", cc);
     ++fallbacks_;
   }
-  ENC_OK(hipEventRecord(ev[1], st));
-  const u64 total = host_misc_[0];
+  ENC_OK(hipEventRecord(c.ev[1], st));
+  const u64 total = c.host_misc[0];
   if (total > cap) return -2;
-  ENC_OK(hipEventRecord(ev[2], st));
+  ENC_OK(hipEventRecord(c.ev[2], st));
   if (total && !cached)  // the cached path wrote the ids in place (k_cache_words)
-    k_encode_emit<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(pad_, tcnt_, bcnt_ + nb, out);
+    k_encode_emit<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(pad, c.tcnt.get(), bcnt + nb, out);
   ENC_OK(hipGetLastError());
-  ENC_OK(hipEventRecord(ev[3], st));
+  ENC_OK(hipEventRecord(c.ev[3], st));
   ENC_OK(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float a = 0, b = 0;
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-    *kernel_ms = (double)a + (double)b;
-  }
+  if (kernel_ms) ENC_OK(c.ev.sum_ms(2, kernel_ms));
   return (int64_t)total;
-}
-
-bool EncodeDevice::reserve_host(size_t n) {
-  if (n <= host_cap_) return true;
-  if (dtext_) (void)hipFree(dtext_);
-  if (dout_) (void)hipFree(dout_);
-  dtext_ = nullptr;
-  dout_ = nullptr;
-  host_cap_ = 0;
-  if (hipMalloc(&dtext_, n) != hipSuccess || hipMalloc(&dout_, n * 4) != hipSuccess) return false;
-  host_cap_ = n;
-  return true;
 }
 
 // Host text in pieces of at most kHostPiece bytes, each cut just after a delimiter (words never
@@ -698,34 +661,22 @@ int64_t EncodeDevice::encode_host(const uint8_t* text, size_t n, int32_t* out, s
   if (!text || !out) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  size_t piece = kHostPiece;
-  if (const char* e = std::getenv("SHREDWORD_ENCODE_PIECE"))  // tests: small pieces
-    piece = std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), (size_t)kEncMaxWord + 2);
-  piece = std::min(n, piece);
-  if (!reserve_host(piece)) {
+  const size_t piece = std::min(n, piece_from_env("SHREDWORD_ENCODE_PIECE", kHostPiece, (size_t)kEncMaxWord + 2));
+  HostStage& hs = pass_state<HostStage>(pass_[kStage]);
+  if (!hs.reserve(piece)) {
     std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu bytes)\n", piece);
     return -1;
   }
   hipStream_t st = (hipStream_t)stream_;
   size_t pos = 0, done = 0;
   while (pos < n) {
-    size_t len = std::min(piece, n - pos);
-    if (pos + len < n) {  // end the piece after its last delimiter
-      size_t k = len;
-      const size_t lo = len > (size_t)kEncMaxWord + 1 ? len - (size_t)kEncMaxWord - 1 : 0;
-      while (k > lo) {
-        const uint8_t c = text[pos + k - 1];
-        if (c == 9 || c == 10 || c == 13 || c == 32) break;
-        --k;
-      }
-      if (k == lo) return -3;  // no delimiter in the last kEncMaxWord + 1 bytes: a word past the limit
-      len = k;
-    }
-    ENC_OK(hipMemcpyAsync(dtext_, text + pos, len, hipMemcpyHostToDevice, st));
-    const int64_t r = encode(dtext_, len, dout_, cap - done, nullptr, nullptr);
+    const size_t len = host_piece_len(text, n, pos, piece);
+    if (len == 0) return -3;
+    ENC_OK(hipMemcpyAsync(hs.text.get(), text + pos, len, hipMemcpyHostToDevice, st));
+    const int64_t r = encode(hs.text.get(), len, hs.out.get(), cap - done, nullptr, nullptr);
     if (r < 0) return r;
     if (r > 0) {
-      ENC_OK(hipMemcpyAsync(out + done, dout_, (size_t)r * 4, hipMemcpyDeviceToHost, st));
+      ENC_OK(hipMemcpyAsync(out + done, hs.out.get(), (size_t)r * 4, hipMemcpyDeviceToHost, st));
       ENC_OK(hipStreamSynchronize(st));
     }
     done += (size_t)r;

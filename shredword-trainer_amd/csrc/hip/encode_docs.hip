@@ -145,41 +145,22 @@ __global__ __launch_bounds__(kThreads) void k_docs_starts(int64_t* __restrict__ 
     starts[k] -= (int64_t)(r0 == r1 ? r0 : last_not_above(r0, r1, k, R));
 }
 
-template <class T>
-bool regrow(T** p, size_t* have, size_t want) {
-  if (want <= *have) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, want * sizeof(T)) != hipSuccess) return false;
-  *have = want;
-  return true;
-}
+// The document passes' state, allocated on the first docs call.  Scratch grown to the largest call
+// seen: 1 B per byte of the copy (text bytes + documents).
+struct DocsState : PassState {
+  DeviceBuf<uint8_t> text;   // the copy: every document followed by a '\n', none inside
+  DeviceWords flag;          // bad doc_off
+  PinnedWords host;          // the flag
+  EventSet<6> ev;            // around the check, the copy, the starts pass
+  // host-path staging: a piece's document offsets, row offsets, starts (text and ids: HostStage)
+  DeviceBuf<int64_t> hoff, hrow, hstarts;
 
-bool is_delim(uint8_t c) { return c == 9 || c == 10 || c == 13 || c == 32; }
+  bool reserve(size_t total) {
+    return flag.ensure(1) && host.ensure(1) && ev.ensure() && text.grow((total + kTile - 1) / kTile * kTile);
+  }
+};
 
 }  // namespace
-
-void EncodeDevice::free_docs() {
-  for (void* p : {(void*)dx_text_, (void*)dx_flag_, (void*)dx_hoff_, (void*)dx_hrow_, (void*)dx_hstarts_})
-    if (p) (void)hipFree(p);
-  if (dx_host_) (void)hipHostFree(dx_host_);
-  for (void* e : dx_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
-}
-
-// Scratch grown to the largest call seen: 1 B per byte of the copy (text bytes + documents).
-bool EncodeDevice::reserve_docs(size_t total) {
-  if (!dx_flag_ && hipMalloc(&dx_flag_, 8) != hipSuccess) return false;
-  if (!dx_host_ && hipHostMalloc(&dx_host_, 8, hipHostMallocDefault) != hipSuccess) return false;
-  for (void*& e : dx_ev_) {
-    if (e) continue;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e = ev;
-  }
-  return regrow(&dx_text_, &dx_cap_, (total + kTile - 1) / kTile * kTile);
-}
 
 int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials,
                                   int32_t* out, size_t cap, int64_t* starts, int64_t* row_off, uint64_t start_base,
@@ -191,26 +172,28 @@ int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* 
   const size_t total = n + rows;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  if (!reserve_docs(total)) {
+  DocsState& dx = pass_state<DocsState>(pass_[kDocs]);
+  if (!dx.reserve(total)) {
     std::fprintf(stderr, "[ERROR]\t encoder: document scratch allocation failed (%zu bytes)\n", total);
     return -1;
   }
+  uint8_t* const copy = dx.text.get();
   if (!out) {  // n == 0: no id, but the encoder wants a pointer
-    out = reinterpret_cast<int32_t*>(dx_text_);
+    out = reinterpret_cast<int32_t*>(copy);
     cap = 0;
   }
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(dx_ev_);
+  const EventSet<6>& ev = dx.ev;
   ENC_OK(hipEventRecord(ev[0], st));
   if (doc_off) {
-    ENC_OK(hipMemsetAsync(dx_flag_, 0, 8, st));
+    ENC_OK(hipMemsetAsync(dx.flag.get(), 0, 8, st));
     k_docs_check<<<dim3((unsigned)(((u64)docs + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(doc_off, (u64)docs,
-                                                                                               (u64)n, dx_flag_);
+                                                                                               (u64)n, dx.flag.get());
     ENC_OK(hipGetLastError());
-    ENC_OK(hipMemcpyAsync(dx_host_, dx_flag_, 8, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipMemcpyAsync(dx.host.get(), dx.flag.get(), 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipEventRecord(ev[1], st));
     ENC_OK(hipStreamSynchronize(st));
-    if (dx_host_[0]) return -6;
+    if (dx.host[0]) return -6;
   } else {
     ENC_OK(hipEventRecord(ev[1], st));
   }
@@ -221,18 +204,18 @@ int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* 
   }
   ENC_OK(hipEventRecord(ev[2], st));
   k_docs_expand<<<dim3((unsigned)(((u64)total + kTile - 1) / kTile)), dim3(kThreads), 0, st>>>(text, (u64)n, doc_off,
-                                                                                             (u64)rows, dx_text_);
+                                                                                             (u64)rows, copy);
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[3], st));
   double enc_ms = 0, special_ms = 0, span_ms = 0;
-  const int64_t T = specials ? encode_special(dx_text_, total, out, cap, lens, stream, &enc_ms, &special_ms)
-                             : encode(dx_text_, total, out, cap, stream, &enc_ms);
+  const int64_t T = specials ? encode_special(copy, total, out, cap, lens, stream, &enc_ms, &special_ms)
+                             : encode(copy, total, out, cap, stream, &enc_ms);
   if (T < 0) return T;
   ENC_OK(hipSetDevice(device_));  // (encode's guard restored the caller's)
   size_t nl = 0;
   uint8_t last = 0;
   // every document ends in one of the copy's '\n' bytes: row_off[1 .. rows] are its line entries
-  if (span_passes(dx_text_, total, out, (size_t)T, starts, row_off, rows + 1, start_base, 0, false, lens, st, &nl,
+  if (span_passes(copy, total, out, (size_t)T, starts, row_off, rows + 1, start_base, 0, false, lens, st, &nl,
                   &last, &span_ms) < 0)
     return -1;
   ENC_OK(hipMemsetAsync(row_off, 0, 8, st));
@@ -246,9 +229,9 @@ int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* 
   ENC_OK(hipStreamSynchronize(st));
   if (kernel_ms) {
     float a = 0, b = 0, c = 0;  // the check, the copy, the starts pass
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-    ENC_OK(hipEventElapsedTime(&c, ev[4], ev[5]));
+    ENC_OK(ev.pair_ms(0, &a));
+    ENC_OK(ev.pair_ms(1, &b));
+    ENC_OK(ev.pair_ms(2, &c));
     kernel_ms[0] = enc_ms;
     kernel_ms[1] = span_ms;
     kernel_ms[2] = special_ms;
@@ -284,16 +267,16 @@ int64_t EncodeDevice::encode_docs_host(const uint8_t* text, size_t n, const int6
   for (size_t d = 0; d < rows; ++d) {
     size_t run = 0;
     for (size_t p = doc_begin(d), e = doc_begin(d + 1); p < e; ++p) {
-      run = is_delim(text[p]) ? 0 : run + 1;
+      run = host_is_delim(text[p]) ? 0 : run + 1;
       non_delim += run != 0;
       if (run > (size_t)kEncMaxWord) return -3;
     }
   }
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  size_t piece = kHostPiece;
-  if (const char* e = std::getenv("SHREDWORD_ENCODE_PIECE"))  // tests: small pieces
-    piece = std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), (size_t)kEncMaxWord + 2);
+  const size_t piece = piece_from_env("SHREDWORD_ENCODE_PIECE", kHostPiece, (size_t)kEncMaxWord + 2);
+  HostStage& hs = pass_state<HostStage>(pass_[kStage]);
+  DocsState& dx = pass_state<DocsState>(pass_[kDocs]);
   hipStream_t st = (hipStream_t)stream_;
   std::vector<int64_t> hoff, hrow;
   // pass 0 (only when cap may be too small): the id count alone; pass 1: the outputs
@@ -303,30 +286,30 @@ int64_t EncodeDevice::encode_docs_host(const uint8_t* text, size_t n, const int6
       size_t e = d + 1;
       while (e < rows && (doc_begin(e + 1) - doc_begin(d)) + (e + 1 - d) <= piece) ++e;
       const size_t pos = doc_begin(d), len = doc_begin(e) - pos, nd = e - d;
-      if (!reserve_host(std::max<size_t>(len, 1)) || !regrow(&dx_hoff_, &dx_hoff_cap_, nd + 1) ||
-          !regrow(&dx_hrow_, &dx_hrow_cap_, nd + 1) || (starts && !regrow(&dx_hstarts_, &dx_hstarts_cap_, len))) {
+      if (!hs.reserve(std::max<size_t>(len, 1)) || !dx.hoff.grow(nd + 1) || !dx.hrow.grow(nd + 1) ||
+          (starts && !dx.hstarts.grow(len))) {
         std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu bytes, %zu documents)\n", len, nd);
         return -1;
       }
-      if (len) ENC_OK(hipMemcpyAsync(dtext_, text + pos, len, hipMemcpyHostToDevice, st));
+      if (len) ENC_OK(hipMemcpyAsync(hs.text.get(), text + pos, len, hipMemcpyHostToDevice, st));
       if (doc_off) {
         hoff.resize(nd + 1);
         for (size_t j = 0; j <= nd; ++j) hoff[j] = doc_off[d + j] - (int64_t)pos;
-        ENC_OK(hipMemcpyAsync(dx_hoff_, hoff.data(), (nd + 1) * 8, hipMemcpyHostToDevice, st));
+        ENC_OK(hipMemcpyAsync(dx.hoff.get(), hoff.data(), (nd + 1) * 8, hipMemcpyHostToDevice, st));
         ENC_OK(hipStreamSynchronize(st));  // (hoff is pageable and reused)
       }
-      const size_t room = pass ? std::min(cap - done, host_cap_) : host_cap_;
-      const int64_t r = encode_docs(dtext_, len, doc_off ? dx_hoff_ : nullptr, doc_off ? nd : 0, specials, dout_,
-                                    room, pass && starts ? dx_hstarts_ : nullptr, dx_hrow_, (uint64_t)pos, lens,
-                                    nullptr, nullptr);
+      const size_t room = pass ? std::min(cap - done, hs.out.cap()) : hs.out.cap();
+      const int64_t r = encode_docs(hs.text.get(), len, doc_off ? dx.hoff.get() : nullptr, doc_off ? nd : 0, specials,
+                                    hs.out.get(), room, pass && starts ? dx.hstarts.get() : nullptr, dx.hrow.get(),
+                                    (uint64_t)pos, lens, nullptr, nullptr);
       if (r < 0) return r;
       ENC_OK(hipSetDevice(device_));
       const size_t T = (size_t)r;
       if (pass) {
         hrow.resize(nd + 1);
-        if (T) ENC_OK(hipMemcpyAsync(out + done, dout_, T * 4, hipMemcpyDeviceToHost, st));
-        if (starts && T) ENC_OK(hipMemcpyAsync(starts + done, dx_hstarts_, T * 8, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipMemcpyAsync(hrow.data(), dx_hrow_, (nd + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (T) ENC_OK(hipMemcpyAsync(out + done, hs.out.get(), T * 4, hipMemcpyDeviceToHost, st));
+        if (starts && T) ENC_OK(hipMemcpyAsync(starts + done, dx.hstarts.get(), T * 8, hipMemcpyDeviceToHost, st));
+        ENC_OK(hipMemcpyAsync(hrow.data(), dx.hrow.get(), (nd + 1) * 8, hipMemcpyDeviceToHost, st));
         ENC_OK(hipStreamSynchronize(st));
         for (size_t j = 0; j <= nd; ++j) row_off[d + j] = (int64_t)done + hrow[j];
       }

@@ -36,15 +36,13 @@
 
 #include "../host/encoder.h"
 #include "encode_common.h"
+#include "encode_words.h"  // the encoder's geometry: one thread per 32-byte span, one workgroup per chunk
 
 namespace shred {
 namespace {
 
 typedef uint64_t u64;
 
-constexpr int kThreads = 128;             // as the encoder: one thread per 32-byte span,
-constexpr int kSpan = 32;                 // one workgroup per 4096-byte chunk
-constexpr int kChunk = kThreads * kSpan;
 constexpr int kWords = kChunk / 4;        // 4-byte text words per chunk
 
 // Bits 0-3: bytes of the word outside "\t\r\n "; bits 4-7: bytes equal to '\n'.
@@ -53,8 +51,7 @@ __device__ __forceinline__ uint32_t word_nibbles(uint32_t v) {
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     const uint32_t c = (v >> (8 * b)) & 255u;
-    const uint32_t delim = c == 9u || c == 13u || c == 10u || c == 32u;
-    r |= (delim ^ 1u) << b | (uint32_t)(c == 10u) << (4 + b);
+    r |= (is_delim(c) ^ 1u) << b | (uint32_t)(c == 10u) << (4 + b);
   }
   return r;
 }
@@ -156,13 +153,7 @@ __global__ __launch_bounds__(kThreads) void k_span_resolve(const uint8_t* __rest
   const uint32_t mine = __popc(nd) | __popc(nl) << 16;
   s_mask[tid] = nd;
   s_inc[tid] = mine;
-  __syncthreads();
-  for (int d = 1; d < kThreads; d <<= 1) {
-    const uint32_t v = tid >= d ? s_inc[tid - d] : 0;
-    __syncthreads();
-    s_inc[tid] += v;  // each half <= 4096: no carry between them
-    __syncthreads();
-  }
+  block_inclusive_scan(s_inc, tid);  // each half <= 4096: no carry between them
   const uint32_t total = s_inc[kThreads - 1];
   const uint32_t nd_total = total & 0xFFFFu, nl_total = total >> 16;
   const u64 r1 = nd_inc[blockIdx.x], r0 = r1 - nd_total;  // the chunk's non-delimiter ranks [r0, r1)
@@ -174,11 +165,7 @@ __global__ __launch_bounds__(kThreads) void k_span_resolve(const uint8_t* __rest
   if (starts) {
     for (u64 k = k0 + tid; k < k1; k += kThreads) {
       const uint32_t r = (uint32_t)(P[k] - r0);  // < nd_total
-      int lo = 0, hi = kThreads - 1;             // first span whose inclusive count exceeds r
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((s_inc[mid] & 0xFFFFu) > r) hi = mid; else lo = mid + 1;
-      }
+      const int lo = first_above(s_inc, r, 0xFFFFu);  // the span of the non-delimiter byte of rank r
       const uint32_t m = s_mask[lo];
       const uint32_t before = (s_inc[lo] & 0xFFFFu) - __popc(m);
       const uint32_t i = r - before;
@@ -208,59 +195,37 @@ __global__ void k_span_ends(int64_t* __restrict__ line, u64 L, u64 T) {
 
 typedef hipcub::TransformInputIterator<u64, IdLength, const int32_t*> LengthIter;
 
+// The span passes' state, allocated on the first spans call and grown to the largest call seen:
+// 32 B per chunk, 8 B per id, the scans' scratch.
+struct SpanState : PassState {
+  DeviceBuf<int32_t> lens;      // 256 + M token lengths, then the registered specials'
+  DeviceBuf<u64> cnt;           // 4 x chunks: non-delimiter / '\n' counts, their inclusive sums
+  DeviceBuf<u64> prefix;        // P[k]: source bytes of the ids before k
+  DeviceBuf<uint8_t> tmp;       // hipCUB scan scratch
+  PinnedWords host;             // '\n' total, last text byte
+  EventSet<4> ev;
+  DeviceBuf<int64_t> hstarts, hline;  // host-path staging of the span outputs
+
+  void specials_changed() override { lens.reset(); }
+
+  bool reserve(size_t n, size_t T, const std::vector<int32_t>& host_lens) {
+    if (!lens.get() && (!lens.grow(host_lens.size()) || hipMemcpy(lens.get(), host_lens.data(), host_lens.size() * 4,
+                                                                   hipMemcpyHostToDevice) != hipSuccess)) {
+      lens.reset();
+      return false;
+    }
+    const size_t nb = (n + kChunk - 1) / kChunk;
+    if (!host.ensure(4) || !ev.ensure() || !cnt.grow(nb, 4) || !prefix.grow(T)) return false;
+    size_t a = 0, b = 0;
+    if (hipcub::DeviceScan::InclusiveSum(nullptr, a, cnt.get(), cnt.get(), (u64)nb) != hipSuccess) return false;
+    if (T && hipcub::DeviceScan::ExclusiveSum(nullptr, b, LengthIter((const int32_t*)nullptr, IdLength{lens.get(), 0}),
+                                              prefix.get(), (u64)T) != hipSuccess)
+      return false;
+    return tmp.grow(std::max<size_t>(std::max(a, b), 16));
+  }
+};
+
 }  // namespace
-
-void EncodeDevice::free_spans() {
-  for (void* p : {(void*)sp_lens_, (void*)sp_cnt_, (void*)sp_prefix_, sp_tmp_, (void*)sp_hstarts_, (void*)sp_hline_})
-    if (p) (void)hipFree(p);
-  if (sp_host_) (void)hipHostFree(sp_host_);
-  for (void* e : sp_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
-}
-
-// Span scratch, grown to the largest call seen: 32 B per chunk, 8 B per id, the scans' scratch.
-bool EncodeDevice::reserve_spans(size_t n, size_t T, const std::vector<int32_t>& lens) {
-  if (!sp_lens_) {
-    if (hipMalloc(&sp_lens_, lens.size() * 4) != hipSuccess) return false;
-    if (hipMemcpy(sp_lens_, lens.data(), lens.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-  }
-  if (!sp_host_ && hipHostMalloc(&sp_host_, 32, hipHostMallocDefault) != hipSuccess) return false;
-  for (void*& e : sp_ev_) {
-    if (e) continue;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e = ev;
-  }
-  const size_t nb = (n + kChunk - 1) / kChunk;
-  if (nb > sp_chunks_) {
-    if (sp_cnt_) (void)hipFree(sp_cnt_);
-    sp_cnt_ = nullptr;
-    sp_chunks_ = 0;
-    if (hipMalloc(&sp_cnt_, 4 * nb * 8) != hipSuccess) return false;
-    sp_chunks_ = nb;
-  }
-  if (T > sp_ids_) {
-    if (sp_prefix_) (void)hipFree(sp_prefix_);
-    sp_prefix_ = nullptr;
-    sp_ids_ = 0;
-    if (hipMalloc(&sp_prefix_, T * 8) != hipSuccess) return false;
-    sp_ids_ = T;
-  }
-  size_t a = 0, b = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, a, sp_cnt_, sp_cnt_, (u64)nb) != hipSuccess) return false;
-  if (T && hipcub::DeviceScan::ExclusiveSum(nullptr, b, LengthIter((const int32_t*)nullptr, IdLength{sp_lens_, 0}),
-                                            sp_prefix_, (u64)T) != hipSuccess)
-    return false;
-  const size_t need = std::max<size_t>(std::max(a, b), 16);
-  if (need > sp_tmp_bytes_) {
-    if (sp_tmp_) (void)hipFree(sp_tmp_);
-    sp_tmp_ = nullptr;
-    sp_tmp_bytes_ = 0;
-    if (hipMalloc(&sp_tmp_, need) != hipSuccess) return false;
-    sp_tmp_bytes_ = need;
-  }
-  return true;
-}
 
 int EncodeDevice::span_passes(const uint8_t* text, size_t n, const int32_t* ids, size_t T, int64_t* starts,
                               int64_t* line, size_t line_cap, uint64_t start_base, uint64_t id_base,
@@ -268,52 +233,49 @@ int EncodeDevice::span_passes(const uint8_t* text, size_t n, const int32_t* ids,
                               uint8_t* last_byte, double* ms) {
   if (ms) *ms = 0;
   if (n == 0) return -1;
-  if (!reserve_spans(n, T, lens)) {
+  SpanState& sp = pass_state<SpanState>(pass_[kSpans]);
+  if (!sp.reserve(n, T, lens)) {
     std::fprintf(stderr, "[ERROR]\t encoder: span scratch allocation failed (%zu bytes, %zu ids)\n", n, T);
     return -1;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(sp_ev_);
+  const EventSet<4>& ev = sp.ev;
   const u64 nb = (n + kChunk - 1) / kChunk;
   const bool aligned = (reinterpret_cast<uintptr_t>(text) & 3) == 0;
-  u64 *nd_cnt = sp_cnt_, *nl_cnt = sp_cnt_ + nb, *nd_inc = sp_cnt_ + 2 * nb, *nl_inc = sp_cnt_ + 3 * nb;
+  u64 *nd_cnt = sp.cnt.get(), *nl_cnt = nd_cnt + nb, *nd_inc = nd_cnt + 2 * nb, *nl_inc = nd_cnt + 3 * nb;
   ENC_OK(hipEventRecord(ev[0], st));
   (aligned ? k_span_count<true> : k_span_count<false>)<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, nd_cnt,
                                                                                                      nl_cnt);
   ENC_OK(hipGetLastError());
-  size_t tmp = sp_tmp_bytes_;
-  ENC_OK(hipcub::DeviceScan::InclusiveSum(sp_tmp_, tmp, nd_cnt, nd_inc, nb, st));
-  tmp = sp_tmp_bytes_;
-  ENC_OK(hipcub::DeviceScan::InclusiveSum(sp_tmp_, tmp, nl_cnt, nl_inc, nb, st));
-  sp_host_[1] = 0;
-  ENC_OK(hipMemcpyAsync(sp_host_, nl_inc + nb - 1, 8, hipMemcpyDeviceToHost, st));
-  ENC_OK(hipMemcpyAsync(sp_host_ + 1, text + n - 1, 1, hipMemcpyDeviceToHost, st));
+  size_t tmp = sp.tmp.cap();
+  ENC_OK(hipcub::DeviceScan::InclusiveSum(sp.tmp.get(), tmp, nd_cnt, nd_inc, nb, st));
+  tmp = sp.tmp.cap();
+  ENC_OK(hipcub::DeviceScan::InclusiveSum(sp.tmp.get(), tmp, nl_cnt, nl_inc, nb, st));
+  sp.host[1] = 0;
+  ENC_OK(hipMemcpyAsync(sp.host.get(), nl_inc + nb - 1, 8, hipMemcpyDeviceToHost, st));
+  ENC_OK(hipMemcpyAsync(sp.host.get() + 1, text + n - 1, 1, hipMemcpyDeviceToHost, st));
   ENC_OK(hipEventRecord(ev[1], st));
   ENC_OK(hipStreamSynchronize(st));
-  const size_t nl = (size_t)sp_host_[0];
+  const size_t nl = (size_t)sp.host[0];
   *newlines = nl;
-  *last_byte = (uint8_t)(sp_host_[1] & 255u);
+  *last_byte = (uint8_t)(sp.host[1] & 255u);
   // the whole text: line[L] follows (k_span_ends); a piece: entries up to line[nl] only
   if (line && line_cap < nl + 1 + (whole && *last_byte != 10)) return -2;
   ENC_OK(hipEventRecord(ev[2], st));
   if (starts || line) {
     if (T) {
-      tmp = sp_tmp_bytes_;
-      ENC_OK(hipcub::DeviceScan::ExclusiveSum(sp_tmp_, tmp, LengthIter(ids, IdLength{sp_lens_, (uint32_t)lens.size()}),
-                                              sp_prefix_, (u64)T, st));
+      tmp = sp.tmp.cap();
+      ENC_OK(hipcub::DeviceScan::ExclusiveSum(sp.tmp.get(), tmp,
+                                              LengthIter(ids, IdLength{sp.lens.get(), (uint32_t)lens.size()}),
+                                              sp.prefix.get(), (u64)T, st));
     }
     (aligned ? k_span_resolve<true> : k_span_resolve<false>)<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(
-        text, n, nd_inc, nl_inc, sp_prefix_, (u64)T, starts, line, start_base, id_base);
+        text, n, nd_inc, nl_inc, sp.prefix.get(), (u64)T, starts, line, start_base, id_base);
     ENC_OK(hipGetLastError());
   }
   ENC_OK(hipEventRecord(ev[3], st));
   ENC_OK(hipStreamSynchronize(st));
-  if (ms) {
-    float a = 0, b = 0;
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-    *ms = (double)a + (double)b;
-  }
+  if (ms) ENC_OK(ev.sum_ms(2, ms));
   return 0;
 }
 
@@ -356,31 +318,6 @@ int64_t EncodeDevice::encode_spans(const uint8_t* text, size_t n, int32_t* out, 
   return T;
 }
 
-namespace {
-// The cut rule of encode_host: a piece ends just after its last delimiter; 0 = a word past the limit.
-size_t host_piece_len(const uint8_t* text, size_t n, size_t pos, size_t piece) {
-  size_t len = std::min(piece, n - pos);
-  if (pos + len < n) {
-    size_t k = len;
-    const size_t lo = len > (size_t)kEncMaxWord + 1 ? len - (size_t)kEncMaxWord - 1 : 0;
-    while (k > lo) {
-      const uint8_t c = text[pos + k - 1];
-      if (c == 9 || c == 10 || c == 13 || c == 32) break;
-      --k;
-    }
-    if (k == lo) return 0;
-    len = k;
-  }
-  return len;
-}
-
-size_t count_newlines(const uint8_t* p, size_t n) {
-  size_t c = 0;
-  for (size_t i = 0; i < n; ++i) c += p[i] == 10;
-  return c;
-}
-}  // namespace
-
 // Host text in the pieces of encode_host.  A piece ends after any delimiter, so a line may run
 // over several pieces: each piece's starts get its byte base, its line entries the id count and
 // the '\n' ordinal carried from the pieces before it, and line_off[L] = T is written at the end.
@@ -402,50 +339,43 @@ int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* 
   if (line_off && line_cap < L + 1) return -2;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  size_t piece = kHostPiece;
-  if (const char* e = std::getenv("SHREDWORD_ENCODE_PIECE"))  // tests: small pieces
-    piece = std::max<size_t>((size_t)std::strtoull(e, nullptr, 10), (size_t)kEncMaxWord + 2);
-  piece = std::min(n, piece);
-  if (!reserve_host(piece)) {
+  const size_t piece = std::min(n, piece_from_env("SHREDWORD_ENCODE_PIECE", kHostPiece, (size_t)kEncMaxWord + 2));
+  HostStage& hs = pass_state<HostStage>(pass_[kStage]);
+  if (!hs.reserve(piece)) {
     std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu bytes)\n", piece);
     return -1;
   }
+  SpanState& sp = pass_state<SpanState>(pass_[kSpans]);
+  uint8_t* const dtext = hs.text.get();
+  int32_t* const dout = hs.out.get();
   hipStream_t st = (hipStream_t)stream_;
   size_t pos = 0, done = 0, lines_done = 0;
   while (pos < n) {
     const size_t len = host_piece_len(text, n, pos, piece);
     if (len == 0) return -3;
-    ENC_OK(hipMemcpyAsync(dtext_, text + pos, len, hipMemcpyHostToDevice, st));
-    const int64_t r = specials ? encode_special(dtext_, len, dout_, cap - done, lens, nullptr, nullptr, nullptr)
-                               : encode(dtext_, len, dout_, cap - done, nullptr, nullptr);
+    ENC_OK(hipMemcpyAsync(dtext, text + pos, len, hipMemcpyHostToDevice, st));
+    const int64_t r = specials ? encode_special(dtext, len, dout, cap - done, lens, nullptr, nullptr, nullptr)
+                               : encode(dtext, len, dout, cap - done, nullptr, nullptr);
     if (r < 0) return r;
     ENC_OK(hipSetDevice(device_));
     const size_t T = (size_t)r;
     const size_t pnl = line_off ? count_newlines(text + pos, len) : 0;
-    if (starts && T > sp_hstarts_cap_) {
-      if (sp_hstarts_) (void)hipFree(sp_hstarts_);
-      sp_hstarts_ = nullptr;
-      sp_hstarts_cap_ = 0;
-      ENC_OK(hipMalloc(&sp_hstarts_, T * 8));
-      sp_hstarts_cap_ = T;
-    }
-    if (line_off && pnl + 1 > sp_hline_cap_) {
-      if (sp_hline_) (void)hipFree(sp_hline_);
-      sp_hline_ = nullptr;
-      sp_hline_cap_ = 0;
-      ENC_OK(hipMalloc(&sp_hline_, (pnl + 1) * 8));
-      sp_hline_cap_ = pnl + 1;
+    if ((starts && !sp.hstarts.grow(T)) || (line_off && !sp.hline.grow(pnl + 1))) {
+      std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu ids, %zu lines)\n", T, pnl + 1);
+      return -1;
     }
     size_t nl = 0;
     uint8_t last = 0;
     // (nothing but the ids wanted: a special call, which has no other host path)
     const int s = !starts && !line_off ? 0
-                  : span_passes(dtext_, len, dout_, T, starts ? sp_hstarts_ : nullptr, line_off ? sp_hline_ : nullptr,
-                                sp_hline_cap_, (u64)pos, (u64)done, false, lens, st, &nl, &last, nullptr);
+                  : span_passes(dtext, len, dout, T, starts ? sp.hstarts.get() : nullptr,
+                                line_off ? sp.hline.get() : nullptr, sp.hline.cap(), (u64)pos, (u64)done, false, lens,
+                                st, &nl, &last, nullptr);
     if (s < 0) return -1;  // (-2 cannot happen: the staging holds the piece's own '\n' count + 1)
-    if (T) ENC_OK(hipMemcpyAsync(out + done, dout_, T * 4, hipMemcpyDeviceToHost, st));
-    if (starts && T) ENC_OK(hipMemcpyAsync(starts + done, sp_hstarts_, T * 8, hipMemcpyDeviceToHost, st));
-    if (line_off && nl) ENC_OK(hipMemcpyAsync(line_off + lines_done + 1, sp_hline_ + 1, nl * 8, hipMemcpyDeviceToHost, st));
+    if (T) ENC_OK(hipMemcpyAsync(out + done, dout, T * 4, hipMemcpyDeviceToHost, st));
+    if (starts && T) ENC_OK(hipMemcpyAsync(starts + done, sp.hstarts.get(), T * 8, hipMemcpyDeviceToHost, st));
+    if (line_off && nl)
+      ENC_OK(hipMemcpyAsync(line_off + lines_done + 1, sp.hline.get() + 1, nl * 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
     done += T;
     lines_done += nl;

@@ -173,16 +173,69 @@ __global__ __launch_bounds__(kMergeThreads) void k_special_merge_specials(const 
   out[j + lower_bound(wstarts, 0, Tw, m_pos[j])] = first_id + (int32_t)m_idx[j];
 }
 
-template <class T>
-bool regrow(T** p, size_t* have, size_t want) {
-  if (want <= *have) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc(p, want * sizeof(T)) != hipSuccess) return false;
-  *have = want;
-  return true;
-}
+// The special passes' state, allocated on the first special call.  Scratch grown to the largest
+// call seen: 5 B per text byte (the blanked copy, its word ids) + 12 B per 32-byte span (counts,
+// their sums), the scan's scratch.
+struct SpecialState : PassState {
+  DeviceBuf<uint32_t> tab;          // scan table: first-byte set, groups, entries, bytes
+  uint32_t tab_ent = 0, tab_bytes = 0;  // its entry and byte word offsets (its size: tab.cap())
+  DeviceBuf<uint8_t> text;          // the text with the accepted matches blanked
+  DeviceBuf<int32_t> wids;          // ids of the blanked text's words (as many as text holds bytes)
+  DeviceBuf<uint32_t> cnt;          // matches of the runs that start in each 32-byte span
+  DeviceBuf<u64> inc;               // their inclusive sum
+  DeviceBuf<uint8_t> tmp;           // hipCUB scan scratch
+  DeviceBuf<int64_t> wstarts;       // byte offsets of the word ids
+  DeviceBuf<u64> mpos;              // match positions, ascending
+  DeviceBuf<uint32_t> midx;         // their specials
+  DeviceWords flag;                 // a run past kEncMaxWord
+  PinnedWords host;                 // match total, the flag
+  EventSet<4> ev;
+
+  // The scan table of special i = bytes[off[i] .. off[i + 1]).
+  bool upload_table(const std::vector<uint8_t>& bytes, const std::vector<uint32_t>& off) {
+    const size_t K = off.size() - 1;
+    std::vector<uint32_t> order(K);
+    std::iota(order.begin(), order.end(), 0u);
+    auto len = [&](uint32_t i) { return off[i + 1] - off[i]; };
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+      const uint8_t ca = bytes[off[a]], cb = bytes[off[b]];
+      return ca != cb ? ca < cb : len(a) != len(b) ? len(a) > len(b) : a < b;
+    });
+    std::vector<uint32_t> set(kSetWords, 0);
+    std::vector<uint16_t> grp;
+    for (size_t e = 0; e < K; ++e) {
+      const uint8_t c = bytes[off[order[e]]];
+      if (!(set[c >> 5] >> (c & 31) & 1u)) grp.push_back((uint16_t)e);
+      set[c >> 5] |= 1u << (c & 31);
+    }
+    grp.push_back((uint16_t)K);
+    if (grp.size() & 1) grp.push_back(0);
+    const uint32_t ent = kSetWords + (uint32_t)grp.size() / 2, first = ent + (uint32_t)K;
+    std::vector<uint32_t> t(first + (bytes.size() + 3) / 4, 0);
+    std::copy(set.begin(), set.end(), t.begin());
+    for (size_t g = 0; g < grp.size(); ++g) t[kSetWords + g / 2] |= (uint32_t)grp[g] << (16 * (g & 1));
+    for (size_t e = 0; e < K; ++e)  // (offsets < 2^14, lengths <= 64, indices < 256)
+      t[ent + e] = off[order[e]] | len(order[e]) << 16 | order[e] << 24;
+    for (size_t i = 0; i < bytes.size(); ++i) t[first + i / 4] |= (uint32_t)bytes[i] << (8 * (i & 3));
+    tab.reset();  // (sized exactly: the kernels stage tab.cap() words in LDS)
+    if (!tab.grow(t.size()) || hipMemcpy(tab.get(), t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return false;
+    tab_ent = ent;
+    tab_bytes = first;
+    return true;
+  }
+
+  bool reserve(size_t n) {
+    if (!flag.ensure(1) || !host.ensure(2) || !ev.ensure()) return false;
+    const size_t nb = (n + kChunk - 1) / kChunk, cap = nb * kChunk, spans = nb * kThreads;
+    if (!text.grow(cap) || !wids.grow(cap) || !cnt.grow(spans) || !inc.grow(spans)) return false;
+    size_t need = 0;
+    if (hipcub::DeviceScan::InclusiveSum(nullptr, need, CountIter(cnt.get(), Widen()), inc.get(), (u64)spans) !=
+        hipSuccess)
+      return false;
+    return tmp.grow(std::max<size_t>(need, 16));
+  }
+};
 
 }  // namespace
 
@@ -194,86 +247,8 @@ void EncodeDevice::set_specials(const uint8_t* bytes, const size_t* off, size_t 
   sx_dirty_ = true;
   // what was built from the old set: the span passes' length table, the decode vocabulary
   (void)hipSetDevice(device_);
-  for (void* p : {(void*)sp_lens_, (void*)dec_tok_off_, (void*)dec_arena_})
-    if (p) (void)hipFree(p);
-  sp_lens_ = nullptr;
-  dec_tok_off_ = nullptr;
-  dec_arena_ = nullptr;
-  dec_vocab_ = 0;
-}
-
-void EncodeDevice::free_special() {
-  for (void* p : {(void*)sx_tab_, (void*)sx_text_, (void*)sx_wids_, (void*)sx_cnt_, (void*)sx_inc_, sx_tmp_,
-                  (void*)sx_wstarts_, (void*)sx_mpos_, (void*)sx_midx_, (void*)sx_flag_})
-    if (p) (void)hipFree(p);
-  if (sx_host_) (void)hipHostFree(sx_host_);
-  for (void* e : sx_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
-}
-
-// The scan table when the set changed; scratch grown to the largest call seen: 5 B per text byte
-// (the blanked copy, its word ids) + 12 B per 32-byte span (counts, their sums), the scan's scratch.
-bool EncodeDevice::reserve_special(size_t n) {
-  if (sx_dirty_) {
-    const size_t K = sx_off_.size() - 1;
-    std::vector<uint32_t> order(K);
-    std::iota(order.begin(), order.end(), 0u);
-    auto len = [&](uint32_t i) { return sx_off_[i + 1] - sx_off_[i]; };
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-      const uint8_t ca = sx_bytes_[sx_off_[a]], cb = sx_bytes_[sx_off_[b]];
-      return ca != cb ? ca < cb : len(a) != len(b) ? len(a) > len(b) : a < b;
-    });
-    std::vector<uint32_t> set(kSetWords, 0);
-    std::vector<uint16_t> grp;
-    for (size_t e = 0; e < K; ++e) {
-      const uint8_t c = sx_bytes_[sx_off_[order[e]]];
-      if (!(set[c >> 5] >> (c & 31) & 1u)) grp.push_back((uint16_t)e);
-      set[c >> 5] |= 1u << (c & 31);
-    }
-    grp.push_back((uint16_t)K);
-    if (grp.size() & 1) grp.push_back(0);
-    const uint32_t ent = kSetWords + (uint32_t)grp.size() / 2, bytes = ent + (uint32_t)K;
-    std::vector<uint32_t> tab(bytes + (sx_bytes_.size() + 3) / 4, 0);
-    std::copy(set.begin(), set.end(), tab.begin());
-    for (size_t g = 0; g < grp.size(); ++g) tab[kSetWords + g / 2] |= (uint32_t)grp[g] << (16 * (g & 1));
-    for (size_t e = 0; e < K; ++e)  // (offsets < 2^14, lengths <= 64, indices < 256)
-      tab[ent + e] = sx_off_[order[e]] | len(order[e]) << 16 | order[e] << 24;
-    for (size_t i = 0; i < sx_bytes_.size(); ++i) tab[bytes + i / 4] |= (uint32_t)sx_bytes_[i] << (8 * (i & 3));
-    if (sx_tab_) (void)hipFree(sx_tab_);
-    sx_tab_ = nullptr;
-    if (hipMalloc(&sx_tab_, tab.size() * 4) != hipSuccess) return false;
-    if (hipMemcpy(sx_tab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
-    sx_tab_words_ = (uint32_t)tab.size();
-    sx_tab_ent_ = ent;
-    sx_tab_bytes_ = bytes;
-    sx_dirty_ = false;
-  }
-  if (!sx_flag_ && hipMalloc(&sx_flag_, 8) != hipSuccess) return false;
-  if (!sx_host_ && hipHostMalloc(&sx_host_, 16, hipHostMallocDefault) != hipSuccess) return false;
-  for (void*& e : sx_ev_) {
-    if (e) continue;
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return false;
-    e = ev;
-  }
-  if (n <= sx_cap_) return true;
-  for (void* p : {(void*)sx_text_, (void*)sx_wids_, (void*)sx_cnt_, (void*)sx_inc_, sx_tmp_})
-    if (p) (void)hipFree(p);
-  sx_text_ = nullptr;
-  sx_wids_ = nullptr;
-  sx_cnt_ = nullptr;
-  sx_inc_ = nullptr;
-  sx_tmp_ = nullptr;
-  sx_cap_ = 0;
-  const size_t nb = (n + kChunk - 1) / kChunk, cap = nb * kChunk, spans = nb * kThreads;
-  if (hipMalloc(&sx_text_, cap) != hipSuccess || hipMalloc(&sx_wids_, cap * 4) != hipSuccess ||
-      hipMalloc(&sx_cnt_, spans * 4) != hipSuccess || hipMalloc(&sx_inc_, spans * 8) != hipSuccess ||
-      hipcub::DeviceScan::InclusiveSum(nullptr, sx_tmp_bytes_, CountIter(sx_cnt_, Widen()), sx_inc_, (u64)spans) !=
-          hipSuccess ||
-      hipMalloc(&sx_tmp_, sx_tmp_bytes_ ? sx_tmp_bytes_ : 16) != hipSuccess)
-    return false;
-  sx_cap_ = cap;
-  return true;
+  for (auto& p : pass_)
+    if (p) p->specials_changed();
 }
 
 int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out, size_t cap,
@@ -286,78 +261,68 @@ int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out
   if (!text || !out) return -1;
   DeviceGuard guard;
   ENC_OK(hipSetDevice(device_));
-  if (!reserve_special(n)) {
+  SpecialState& sx = pass_state<SpecialState>(pass_[kSpecial]);
+  if ((sx_dirty_ && !sx.upload_table(sx_bytes_, sx_off_)) || !sx.reserve(n)) {
     std::fprintf(stderr, "[ERROR]\t encoder: special-token scratch allocation failed (%zu bytes)\n", n);
     return -1;
   }
+  sx_dirty_ = false;
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  hipEvent_t* ev = reinterpret_cast<hipEvent_t*>(sx_ev_);
+  const EventSet<4>& ev = sx.ev;
   const u64 nb = (n + kChunk - 1) / kChunk, spans = nb * kThreads;
-  const SpecialTab tab{sx_tab_, sx_tab_words_, sx_tab_ent_, sx_tab_bytes_};
-  const size_t lds = (size_t)sx_tab_words_ * 4;
+  const SpecialTab tab{sx.tab.get(), (uint32_t)sx.tab.cap(), sx.tab_ent, sx.tab_bytes};
+  const size_t lds = sx.tab.cap() * 4;
+  uint32_t* const cnt = sx.cnt.get();
+  u64* const inc = sx.inc.get();
   ENC_OK(hipEventRecord(ev[0], st));
-  ENC_OK(hipMemsetAsync(sx_flag_, 0, 8, st));
-  k_special_scan<false><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, sx_cnt_, nullptr, nullptr,
-                                                                         nullptr, 0, nullptr, sx_flag_);
+  ENC_OK(hipMemsetAsync(sx.flag.get(), 0, 8, st));
+  k_special_scan<false><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, cnt, nullptr, nullptr, nullptr,
+                                                                         0, nullptr, sx.flag.get());
   ENC_OK(hipGetLastError());
-  size_t tmp = sx_tmp_bytes_;
-  ENC_OK(hipcub::DeviceScan::InclusiveSum(sx_tmp_, tmp, CountIter(sx_cnt_, Widen()), sx_inc_, spans, st));
-  ENC_OK(hipMemcpyAsync(sx_host_, sx_inc_ + spans - 1, 8, hipMemcpyDeviceToHost, st));
-  ENC_OK(hipMemcpyAsync(sx_host_ + 1, sx_flag_, 8, hipMemcpyDeviceToHost, st));
+  size_t tmp = sx.tmp.cap();
+  ENC_OK(hipcub::DeviceScan::InclusiveSum(sx.tmp.get(), tmp, CountIter(cnt, Widen()), inc, spans, st));
+  ENC_OK(hipMemcpyAsync(sx.host.get(), inc + spans - 1, 8, hipMemcpyDeviceToHost, st));
+  ENC_OK(hipMemcpyAsync(sx.host.get() + 1, sx.flag.get(), 8, hipMemcpyDeviceToHost, st));
   ENC_OK(hipStreamSynchronize(st));
-  if (sx_host_[1]) return -3;
-  const size_t M = (size_t)sx_host_[0];
-  float a = 0, b = 0;
+  if (sx.host[1]) return -3;
+  const size_t M = (size_t)sx.host[0];
   if (M == 0) {  // no match: the plain encode
     ENC_OK(hipEventRecord(ev[1], st));
     const int64_t T = encode(text, n, out, cap, stream, enc_ms);
-    if (T >= 0 && special_ms) {
-      ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-      *special_ms = (double)a;
-    }
+    if (T >= 0 && special_ms) ENC_OK(ev.sum_ms(1, special_ms));
     return T;
   }
-  if (M > sx_matches_) {
-    for (void* p : {(void*)sx_mpos_, (void*)sx_midx_})
-      if (p) (void)hipFree(p);
-    sx_mpos_ = nullptr;
-    sx_midx_ = nullptr;
-    sx_matches_ = 0;
-    if (hipMalloc(&sx_mpos_, M * 8) != hipSuccess || hipMalloc(&sx_midx_, M * 4) != hipSuccess) return -1;
-    sx_matches_ = M;
-  }
-  ENC_OK(hipMemcpyAsync(sx_text_, text, n, hipMemcpyDeviceToDevice, st));
-  k_special_scan<true><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, sx_cnt_, sx_inc_, sx_mpos_,
-                                                                        sx_midx_, (u64)M, sx_text_, sx_flag_);
+  if (!sx.mpos.grow(M) || !sx.midx.grow(M)) return -1;
+  uint8_t* const masked = sx.text.get();
+  int32_t* const wids = sx.wids.get();
+  ENC_OK(hipMemcpyAsync(masked, text, n, hipMemcpyDeviceToDevice, st));
+  k_special_scan<true><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, cnt, inc, sx.mpos.get(),
+                                                                        sx.midx.get(), (u64)M, masked, sx.flag.get());
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[1], st));
-  const int64_t Tw = encode(sx_text_, n, sx_wids_, sx_cap_, stream, enc_ms);
+  const int64_t Tw = encode(masked, n, wids, sx.wids.cap(), stream, enc_ms);
   if (Tw < 0) return Tw;
   ENC_OK(hipSetDevice(device_));  // (encode's guard restored the caller's)
   const size_t T = (size_t)Tw + M;
   if (T > cap) return -2;
   ENC_OK(hipEventRecord(ev[2], st));
   if (Tw) {
-    if (!regrow(&sx_wstarts_, &sx_ids_, (size_t)Tw)) return -1;
+    if (!sx.wstarts.grow((size_t)Tw)) return -1;
     size_t nl = 0;
     uint8_t last = 0;
-    if (span_passes(sx_text_, n, sx_wids_, (size_t)Tw, sx_wstarts_, nullptr, 0, 0, 0, false, lens, st, &nl,
-                    &last, nullptr) < 0)
+    if (span_passes(masked, n, wids, (size_t)Tw, sx.wstarts.get(), nullptr, 0, 0, 0, false, lens, st, &nl, &last,
+                    nullptr) < 0)
       return -1;
     k_special_merge_words<<<dim3((unsigned)(((u64)Tw + kMergeTile - 1) / kMergeTile)), dim3(kMergeThreads), 0, st>>>(
-        sx_wids_, sx_wstarts_, (u64)Tw, sx_mpos_, (u64)M, out);
+        wids, sx.wstarts.get(), (u64)Tw, sx.mpos.get(), (u64)M, out);
     ENC_OK(hipGetLastError());
   }
   k_special_merge_specials<<<dim3((unsigned)((M + kMergeThreads - 1) / kMergeThreads)), dim3(kMergeThreads), 0, st>>>(
-      sx_wstarts_, (u64)Tw, sx_mpos_, sx_midx_, (u64)M, sx_first_id_, out);
+      sx.wstarts.get(), (u64)Tw, sx.mpos.get(), sx.midx.get(), (u64)M, sx_first_id_, out);
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[3], st));
   ENC_OK(hipStreamSynchronize(st));
-  if (special_ms) {
-    ENC_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    ENC_OK(hipEventElapsedTime(&b, ev[2], ev[3]));
-    *special_ms = (double)a + (double)b;
-  }
+  if (special_ms) ENC_OK(ev.sum_ms(2, special_ms));
   return (int64_t)T;
 }
 

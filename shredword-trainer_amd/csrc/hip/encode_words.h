@@ -1,6 +1,7 @@
 // The word walk of the encoder kernels (encode_device.hip) and of the special-token scan
 // (encode_special.hip): one workgroup per 4096-byte chunk, one thread per 32-byte span, a word
-// belongs to the span it starts in.  Device code; included by those two .hip files only.
+// belongs to the span it starts in; the span passes (encode_spans.hip) share the geometry and the
+// block scan.  Device code; included by those three .hip files only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,28 @@ constexpr int kSpan = 32;                  // bytes whose word starts one thread
 constexpr int kChunk = kThreads * kSpan;   // bytes per workgroup
 
 __device__ __forceinline__ uint32_t is_delim(uint32_t c) { return c == 9u || c == 13u || c == 10u || c == 32u; }
+
+// In-place inclusive scan of s_inc[0 .. kThreads), of which every thread has just written its own
+// entry (the first barrier orders those stores).
+__device__ __forceinline__ void block_inclusive_scan(uint32_t* s_inc, int tid) {
+  __syncthreads();
+  for (int d = 1; d < kThreads; d <<= 1) {
+    const uint32_t v = tid >= d ? s_inc[tid - d] : 0;
+    __syncthreads();
+    s_inc[tid] += v;
+    __syncthreads();
+  }
+}
+
+// The first thread whose scanned count (s_inc[t] & mask) exceeds i; i is below the last count.
+__device__ __forceinline__ int first_above(const uint32_t* s_inc, uint32_t i, uint32_t mask) {
+  int lo = 0, hi = kThreads - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((s_inc[mid] & mask) > i) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
 
 // The chunk's text staged in LDS (coalesced 4-byte loads), with a few bytes before it and
 // kOverhang after: word scans, hashes and compares read LDS, and global memory only for bytes

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -30,6 +31,13 @@ constexpr uint64_t kDecMaxVocabBytes = 1ull << 30;  // SHRED_DECODE_MAX_VOCAB_BY
 constexpr int kDecMaxUnk = 8;                       // SHRED_DECODE_MAX_UNK
 bool enc_build_arena(const std::vector<int32_t>& first, const std::vector<int32_t>& second,
                      std::vector<uint32_t>* off, std::vector<uint8_t>* bytes);
+
+// What one family of passes owns on the device; the units derive theirs from the resources of
+// hip/encode_common.h.
+struct PassState {
+  virtual ~PassState() = default;
+  virtual void specials_changed() {}  // set_specials(): drop what was built from the old set
+};
 
 class EncodeDevice {
  public:
@@ -126,8 +134,6 @@ class EncodeDevice {
 
  private:
   EncodeDevice() = default;
-  bool reserve(size_t n, std::string* why);
-  bool reserve_host(size_t n);
   // Span passes over n text bytes and their T ids (both on the device): starts[k] = start_base +
   // byte offset, line[q + 1] = id_base + id offset of the line after the q-th '\n' (line[0] is
   // not written; line_cap entries).  *newlines / *last_byte: the text's '\n' count and last byte.
@@ -136,143 +142,20 @@ class EncodeDevice {
   int span_passes(const uint8_t* text, size_t n, const int32_t* ids, size_t T, int64_t* starts, int64_t* line,
                   size_t line_cap, uint64_t start_base, uint64_t id_base, bool whole,
                   const std::vector<int32_t>& lens, void* stream, size_t* newlines, uint8_t* last_byte, double* ms);
-  bool reserve_spans(size_t n, size_t T, const std::vector<int32_t>& lens);
-  void free_spans();  // called by the destructor
   int device_ = 0;
-  void* stream_ = nullptr;      // hipStream_t
-  uint64_t* table_ = nullptr;
-  uint64_t mask_ = 0;
-  bool packed_ = false;         // 16-bit LDS strips (ids < 0xFFFF)
-  int32_t* byte_map_ = nullptr;
-  // scratch sized for the largest text seen: ids per word span, rank cache of long words,
-  // per-thread counts, per-block counts / offsets, total + error word
-  size_t cap_bytes_ = 0;
-  int32_t* pad_ = nullptr;
-  int32_t* rank_ = nullptr;
-  uint32_t* tcnt_ = nullptr;
-  uint64_t* bcnt_ = nullptr;    // [0, nb) block counts, [nb, 2 nb) inclusive sums
-  void* scan_tmp_ = nullptr;     // hipCUB scan scratch
-  size_t scan_tmp_bytes_ = 0;
-  uint64_t* misc_ = nullptr;    // [0] total ids, [1] flags: 1 long word, 2 probe window full, 4 collision,
-                                // 8 arena full; [2] word-cache arena top
-  // word cache (one 16-byte slot per distinct word): 64-bit word hash, payload (an occurrence's
-  // offset, then arena offset | length << 32 | id count << 48); the arena is rank_
-  size_t ccap_ = 0, ccap_min_ = 0;  // allocated slots; slots a call starts with
-  uint64_t* cslot_ = nullptr;
-  uint64_t* host_misc_ = nullptr;  // pinned
-  // host-path staging
-  size_t host_cap_ = 0;
-  uint8_t* dtext_ = nullptr;
-  int32_t* dout_ = nullptr;
-  void* ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  void* stream_ = nullptr;  // hipStream_t
+  uint64_t mask_ = 0;       // of the merge-rank table
+  bool packed_ = false;     // 16-bit LDS strips (ids < 0xFFFF)
   uint64_t fallbacks_ = 0;
-  // span passes (encode_spans.hip): allocated on the first spans call, never by encode()
-  int32_t* sp_lens_ = nullptr;     // 256 + M token lengths
-  size_t sp_chunks_ = 0;           // chunks sp_cnt_ holds
-  uint64_t* sp_cnt_ = nullptr;     // 4 x chunks: non-delimiter / '\n' counts, their inclusive sums
-  size_t sp_ids_ = 0;              // ids sp_prefix_ holds
-  uint64_t* sp_prefix_ = nullptr;  // P[k]: source bytes of the ids before k
-  void* sp_tmp_ = nullptr;         // hipCUB scan scratch
-  size_t sp_tmp_bytes_ = 0;
-  uint64_t* sp_host_ = nullptr;    // pinned: '\n' total, last text byte
-  void* sp_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  // host-path staging of the span outputs
-  size_t sp_hstarts_cap_ = 0, sp_hline_cap_ = 0;
-  int64_t* sp_hstarts_ = nullptr;
-  int64_t* sp_hline_ = nullptr;
-
-  // special passes (encode_special.hip): allocated on the first special call, never by the others
-  bool reserve_special(size_t n);
-  void free_special();  // called by the destructor
-  std::vector<uint8_t> sx_bytes_;    // the registered specials' bytes, in id order
-  std::vector<uint32_t> sx_off_;     // K + 1 offsets into sx_bytes_
-  int32_t sx_first_id_ = 0;          // id of special 0
-  bool sx_dirty_ = false;            // the device table is older than the set
-  uint32_t* sx_tab_ = nullptr;       // scan table: first-byte set, groups, entries, bytes
-  uint32_t sx_tab_words_ = 0, sx_tab_ent_ = 0, sx_tab_bytes_ = 0;  // its size, entry and byte word offsets
-  size_t sx_cap_ = 0;                // text bytes the scratch below holds
-  uint8_t* sx_text_ = nullptr;       // the text with the accepted matches blanked
-  int32_t* sx_wids_ = nullptr;       // ids of the blanked text's words
-  uint32_t* sx_cnt_ = nullptr;       // matches of the runs that start in each 32-byte span
-  uint64_t* sx_inc_ = nullptr;       // their inclusive sum
-  void* sx_tmp_ = nullptr;           // hipCUB scan scratch
-  size_t sx_tmp_bytes_ = 0;
-  size_t sx_ids_ = 0;                // entries sx_wstarts_ holds
-  int64_t* sx_wstarts_ = nullptr;    // byte offsets of the word ids
-  size_t sx_matches_ = 0;            // entries sx_mpos_ / sx_midx_ hold
-  uint64_t* sx_mpos_ = nullptr;      // match positions, ascending
-  uint32_t* sx_midx_ = nullptr;      // their specials
-  uint64_t* sx_flag_ = nullptr;      // device: a run past kEncMaxWord
-  uint64_t* sx_host_ = nullptr;      // pinned: match total, the flag
-  void* sx_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-
-  // document passes (encode_docs.hip): allocated on the first docs call, never by the others
-  bool reserve_docs(size_t total);
-  void free_docs();  // called by the destructor
-  size_t dx_cap_ = 0;                // bytes dx_text_ holds
-  uint8_t* dx_text_ = nullptr;       // the copy: every document followed by a '\n', none inside
-  uint64_t* dx_flag_ = nullptr;      // device: bad doc_off
-  uint64_t* dx_host_ = nullptr;      // pinned: the flag
-  void* dx_ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around the check, the copy, the starts pass
-  // host-path staging: a piece's document offsets, row offsets, starts (text and ids: dtext_ / dout_)
-  size_t dx_hoff_cap_ = 0, dx_hrow_cap_ = 0, dx_hstarts_cap_ = 0;
-  int64_t* dx_hoff_ = nullptr;
-  int64_t* dx_hrow_ = nullptr;
-  int64_t* dx_hstarts_ = nullptr;
-
-  // decode passes (decode_device.hip): allocated on the first decode call, never by the encode calls
-  struct DecodeCall;  // one call's arguments, as the kernels take them
-  bool reserve_decode(size_t n, size_t rows, const std::vector<int32_t>& first, const std::vector<int32_t>& second);
-  // Length passes over n device ids and their row_off (nullptr, or rows + 1 entries whose end
-  // points are checked when c.ends): Q into dec_q_, *total = the bytes needed.  0, -1, -6.
-  int decode_lengths(const DecodeCall& c, void* stream, uint64_t* total);
-  // byte_off (nullptr, or as the header defines it, plus c.base) and the total bytes into out.
-  int decode_expand(const DecodeCall& c, uint64_t total, uint8_t* out, int64_t* byte_off, void* stream);
-  void free_decode();  // called by the destructor
-  uint32_t dec_vocab_ = 0;           // 256 + M
-  uint32_t* dec_tok_off_ = nullptr;  // 256 + M + 1 offsets into dec_arena_
-  uint8_t* dec_arena_ = nullptr;     // the bytes of every token
-  size_t dec_ids_ = 0;               // dec_q_ holds dec_ids_ + 1 entries
-  uint64_t* dec_q_ = nullptr;        // Q[k]: output offset of token k; Q[n] = the total
-  size_t dec_marks_ = 0;             // dec_mark_ holds dec_marks_ + 1 entries
-  uint32_t* dec_mark_ = nullptr;     // rows that end just before id k (separators in front of it)
-  void* dec_tmp_ = nullptr;          // hipCUB scan scratch
-  size_t dec_tmp_bytes_ = 0;
-  uint64_t* dec_err_ = nullptr;      // device: [0] an id outside the vocabulary, [1] bad row_off
-  uint64_t* dec_host_ = nullptr;     // pinned: total, the two error words
-  void* dec_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  // host-path staging: ids, row offsets, byte offsets, output bytes of a piece
-  size_t dec_hids_cap_ = 0, dec_hrow_cap_ = 0, dec_hout_cap_ = 0;
-  int32_t* dec_hids_ = nullptr;
-  int64_t* dec_hrow_ = nullptr;      // 2 x dec_hrow_cap_: row offsets, then byte offsets
-  uint8_t* dec_hout_ = nullptr;
-
-  // batch passes (batch_device.hip): allocated on the first pad / pack call, never by the encode
-  // or decode calls
-  struct BatchCall;  // one call's (or piece's) rows, as the kernels take them
-  bool reserve_batch(size_t rows);
-  // Row checks (when c.row), E into bat_e_ (when scan) and max e_r over c's rows: 0, -1, -6.
-  int batch_lengths(const BatchCall& c, bool scan, void* stream, uint64_t* total, uint64_t* widest);
-  int pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
-                 uint8_t* mask, void* stream);
-  // Stream positions [c.base, c.base + limit) into out / pos / seg (which point at position
-  // c.base), pad_id from the rows' end on; row_start[r] = c.base + E[r] for the call's rows.
-  int pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out, int32_t* pos,
-                  int32_t* seg, int64_t* row_start, void* stream);
-  void free_batch();  // called by the destructor
-  size_t bat_rows_ = 0;              // bat_e_ holds bat_rows_ + 1 entries
-  uint64_t* bat_e_ = nullptr;        // E[r]: stream offset of emitted row r; E[rows] = T
-  void* bat_tmp_ = nullptr;          // hipCUB scan / reduce scratch
-  size_t bat_tmp_bytes_ = 0;
-  uint64_t* bat_res_ = nullptr;      // device: [0] bad row_off, [1] an e_r past int32, [2] max e_r
-  uint64_t* bat_host_ = nullptr;     // pinned: T, then the three words of bat_res_
-  void* bat_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  // host-path staging: ids, row offsets, a piece's int32 outputs, its mask
-  size_t bat_hids_cap_ = 0, bat_hrow_cap_ = 0, bat_hout_cap_ = 0, bat_hmask_cap_ = 0;
-  int32_t* bat_hids_ = nullptr;
-  int64_t* bat_hrow_ = nullptr;      // 2 x bat_hrow_cap_: row offsets, then row_start
-  int32_t* bat_hout_ = nullptr;      // 3 x bat_hout_cap_: out, then pos / lengths, then seg
-  uint8_t* bat_hmask_ = nullptr;
+  // The registered special tokens (set_specials); the units build their device tables from them.
+  std::vector<uint8_t> sx_bytes_;  // the specials' bytes, in id order
+  std::vector<uint32_t> sx_off_;   // K + 1 offsets into sx_bytes_
+  int32_t sx_first_id_ = 0;        // id of special 0
+  bool sx_dirty_ = false;          // the scan table on the device is older than the set
+  // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
+  // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kPasses };
+  std::unique_ptr<PassState> pass_[kPasses];
 };
 
 }  // namespace shred
