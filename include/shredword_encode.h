@@ -333,6 +333,65 @@ int64_t shred_pack_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const i
                         int32_t pad_id, int drop_last, int32_t* out, size_t cap, int32_t* pos, int32_t* seg,
                         int64_t* row_start);
 
+/* ---- long rows cut into overlapping windows on the GPU ("overflowing tokens with a stride") --------
+ *
+ * Pad with max_len keeps one end of a long row; these keep all of it, as several rows of the batch
+ * that still belong to the input row.  ids, row_off / rows (the NULL / rows == 0 rule, -6), bos, eos
+ * and add are those of the batch calls above.
+ *   max_len     required: every window holds at most max_len ids, the added ones included, so
+ *               C = max_len - add ids of its row.  1 <= C and max_len <= INT32_MAX, else -1.
+ *   stride      consecutive windows of a row share exactly stride ids: window j starts
+ *               step = C - stride ids after window j - 1.  0 <= stride < C, else -1.
+ *
+ * Row r of len_r ids has w_r = 1 windows if len_r <= C, else 1 + ceil((len_r - C) / step).  Window j
+ * holds the row's ids [j * step, min(j * step + C, len_r)) and is emitted as [bos] + those ids +
+ * [eos], of length e = add + their count: only a row's last window can be shorter than max_len.
+ * An empty row has one window that holds only the added ids (with add == 0: only padding), so
+ * every input row is represented, as in pad.  WO[r] is the sum of w_r' over r' < r, Wn = WO[rows].
+ * There is no trunc_side: nothing is dropped.
+ *
+ * Outputs (width = W, pad_id, pad_side as in pad); all but out may be NULL:
+ *   out         [Wn, W] int32, row-major: window w as pad writes an emitted row.
+ *   lengths     Wn int32: e of each window.
+ *   mask        [Wn, W] uint8: 1 where a token sits, 0 where padding sits.
+ *   win_row     Wn int32: the row r of each window.  rows > INT32_MAX returns -1 when it is asked for.
+ *   win_src     Wn int64: the index in ids of the window's first kept id, row_off[r] + j * step.  The
+ *               kept id at emitted position c in [bos != NULL, e - (eos != NULL)) is
+ *               ids[win_src[w] + c - (bos != NULL)], and the same index into starts (shred_encode_spans,
+ *               shred_encode_docs) is that token's byte offset: the offset mapping of a window.
+ *   row_win     rows + 1 int64 (1 + 1 when row_off is NULL): WO[0 .. rows]; row r owns the windows
+ *               [row_win[r], row_win[r+1]).
+ *   widest      NULL, or a host size_t that receives the largest e (0 for rows == 0).
+ *
+ * Returns Wn.  Nothing is written but *widest if out is NULL, or width is smaller than *widest, or
+ * cap < Wn * width (cap counts int32 entries): the sizing call, only the length passes run.
+ * width = max_len always suffices.  Errors, with nothing written at all: -1 bad argument, HIP
+ * error, or a Wn * width that does not fit an int64; -6 bad row_off.  (A HIP error after the first
+ * piece of shred_window_rows leaves the earlier pieces' output in place.)
+ *
+ * The window scratch (8 B per row for WO, the scan's temporaries, a pinned result word, events) is
+ * allocated on the first window call and freed with the encoder, so the other calls' footprints
+ * are unchanged.
+ */
+
+/* All buffers on the encoder's device (row_off is validated there); stream, alignment and
+ * kernel_ms as shred_pad_device. */
+int64_t shred_window_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                            const int32_t* bos, const int32_t* eos, size_t max_len, size_t stride, size_t width,
+                            int32_t pad_id, int pad_side, void* out, size_t cap, void* lengths, void* mask,
+                            void* win_row, void* win_src, void* row_win, size_t* widest, void* stream,
+                            double* kernel_ms);
+
+/* Host buffers; row_off, Wn and the widest window are settled on the host before anything is
+ * staged.  Staged like shred_pad_rows in pieces of whole rows: a piece takes rows while its ids,
+ * its rows and its output entries (windows * width, at most 4 per id of the budget) stay within
+ * the piece budget, and one row is taken whole, however long.  A piece writes its own windows of
+ * every output. */
+int64_t shred_window_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          const int32_t* bos, const int32_t* eos, size_t max_len, size_t stride, size_t width,
+                          int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask,
+                          int32_t* win_row, int64_t* win_src, int64_t* row_win, size_t* widest);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -1,5 +1,6 @@
-// Rows of token ids to rectangular model inputs on gfx950: padded batches and packed sequences
-// (C ABI and definitions: include/shredword_encode.h, shred_pad_* / shred_pack_*).  The passes use
+// Rows of token ids to rectangular model inputs on gfx950: padded batches, packed sequences and
+// overlapping windows of long rows (C ABI and definitions: include/shredword_encode.h,
+// shred_pad_* / shred_pack_* / shred_window_*).  The passes use
 // none of the encoder's or the decoder's kernels.
 //
 // Row r keeps keep_r of its len_r ids (from either end) and emits e_r = add + keep_r ids: an
@@ -33,6 +34,33 @@
 // the two offsets of every row it touches through the caches.  Pack: reads 4 (ids), writes 4: 8
 // bytes, + 4 each for pos and seg; per row 8 (row pass) + 8 (scan reads row_off) = 16 B, and E is
 // written once and read back with row_off by the tiles (24 B per row, through the caches).
+//
+// Windows (shred_window_*): row r is cut into w_r overlapping windows of at most C = max_len - add
+// ids, step = C - stride ids apart; WO is the exclusive prefix sum of w_r, WO[rows] = Wn, and it is
+// strictly increasing, since every row has a window.
+//
+//   k_bat_rows       as above, with keep_max = C: e_r is then the length of row r's first window;
+//   hipCUB scan      inclusive sum over k = 0 .. rows of (k ? w_{k-1} : 0): WO[0 .. rows];
+//   hipCUB reduce    the maximum of e_r: the longest window (a row's first is its longest);
+//   k_bat_row_start  row_win[r] = WO[r];
+//   k_bat_window     output-centric like k_bat_pad: one workgroup per kTile consecutive entries of
+//                    the flat [Wn, W] array, 4 consecutive entries per lane, the (window, column)
+//                    split of a lane's first entry done once and then walked.  The row of the tile's
+//                    first window by one search of WO per workgroup (its first wave probes 64
+//                    entries a step); then rounds of kStage rows staged in LDS as k_bat_pack stages
+//                    them (WO relative to the tile's first window, the index in ids that the row's
+//                    window at the tile's first window would start at, the row's end).  A lane finds
+//                    the row under its first entry by a binary search of the LDS offsets and walks
+//                    forward.  A tile of narrow windows can hold more than kStage rows and takes
+//                    more rounds; a row whose windows cover many tiles needs no special case.  The
+//                    lane that owns column 0 of a window writes its lengths, win_row and win_src;
+//   k_bat_window_meta  W == 0 only (rows that are all empty, nothing added): no lane owns a column,
+//                    so one thread per window writes the three.
+//
+// Window traffic per output entry is pad's: 4 + 4 f bytes at fill f = sum e / (Wn W), + 1 with the
+// mask; per window 4 (lengths) + 4 (win_row) + 8 (win_src) = 16 B for those asked for; per row 8
+// (row pass) + 8 (scan) + 8 (reduce) reads of row_off, 8 written for WO and 8 for row_win, and the
+// tiles read WO and row_off back through the caches.
 // All global indices are 64-bit; every store is an ordinary vector store.  Output pointers are
 // only element-aligned (tensor views), so the 16-byte (mask: 4-byte) stores have a scalar form.
 #include <hip/hip_runtime.h>
@@ -310,6 +338,177 @@ __global__ __launch_bounds__(kThreads) void k_bat_pack(const int32_t* __restrict
   }
 }
 
+// How a row turns into its windows.  rw.keep_max is C (never kNoLimit), so rw.emit(r) is the length
+// of row r's first window; rw.left is 0.
+struct Windows {
+  Rows rw;
+  u64 step;  // C - stride >= 1
+  __host__ __device__ __forceinline__ u64 count(u64 r) const {
+    u64 a, b;
+    rw.bounds(r, &a, &b);
+    return window_count(b - a, rw.keep_max, step);
+  }
+};
+
+Windows windows_of(const EncodeDevice::BatchOpts& o, u64 stride, const int64_t* row, u64 n) {
+  const Rows rw = rows_of(o, row, n);
+  return Windows{rw, rw.keep_max - stride};
+}
+
+// Element k of the scan: the window count of row k - 1.
+struct WOInput {
+  Windows wn;
+  __host__ __device__ __forceinline__ u64 operator()(u64 k) const { return k ? wn.count(k - 1) : 0ull; }
+};
+typedef hipcub::TransformInputIterator<u64, WOInput, hipcub::CountingInputIterator<u64>> WOIter;
+
+// upper_bound by the 64 lanes of one wave (all active): a step probes 64 entries spread over
+// [lo, hi), so a search of 2^24 entries takes 4 rounds of loads instead of 24.
+__device__ __forceinline__ u64 wave_upper_bound(const u64* __restrict__ E, u64 lo, u64 hi, u64 v, int lane) {
+  while (lo < hi) {
+    const u64 gap = (hi - lo) / 64 + 1;
+    const u64 k = lo + (u64)lane * gap;
+    // E does not decrease: the lanes that see an entry <= v are the first `le`
+    const u64 le = (u64)__popcll(__ballot(k < hi && E[k] <= v));
+    if (le == 0) {
+      hi = lo;
+    } else {
+      const u64 next = lo + le * gap;
+      lo += (le - 1) * gap + 1;
+      hi = next < hi ? next : hi;
+    }
+  }
+  return lo;
+}
+
+// total = Wn * W > 0, W >= every window's length; WO: rows + 1 entries, strictly increasing from 0
+// to Wn.  Window w of the call goes to out[w * W ..], lengths[w], win_row[w], win_src[w].
+template <bool kAligned>
+__global__ __launch_bounds__(kThreads) void k_bat_window(const int32_t* __restrict__ ids, Windows wn, u64 rows,
+                                                         const u64* __restrict__ WO, u64 W, u64 total, int32_t pad_id,
+                                                         uint32_t pad_left, u64 row_base, u64 id_base,
+                                                         int32_t* __restrict__ out, int32_t* __restrict__ lengths,
+                                                         uint8_t* __restrict__ mask, uint32_t mask_aligned,
+                                                         int32_t* __restrict__ win_row, int64_t* __restrict__ win_src) {
+  __shared__ int32_t s_w[kStage + 1];  // WO[k] - the tile's first window, clamped to [-INT32_MAX, kTile + 1]
+  __shared__ u64 s_src[kStage];        // index in ids at which the row's window at the tile's first window
+                                       // starts (modulo 2^64: rows that begin later lie before their ids)
+  __shared__ u64 s_end[kStage];        // the row's end in ids
+  __shared__ u64 s_k;
+  const int tid = threadIdx.x;
+  const u64 t0 = (u64)blockIdx.x * kTile;
+  const int tlen = (int)(total - t0 < (u64)kTile ? total - t0 : (u64)kTile);
+  const u64 w0 = t0 / W, c0 = t0 - w0 * W;                // the tile's first entry: window, column
+  const int wlast = (int)((c0 + (u64)(tlen - 1)) / W);    // its last entry's window, relative to w0
+  if (tid < 64) {  // the row of window w0: the last k with WO[k] <= w0 (WO[0] = 0, WO[rows] = Wn > w0)
+    const u64 ub = wave_upper_bound(WO, 0, rows + 1, w0, tid);
+    if (tid == 0) s_k = ub == 0 ? 0 : ub > rows ? rows - 1 : ub - 1;
+  }
+  __syncthreads();
+  u64 ks = s_k;
+  const int p0 = tid * kLane;
+  const int cnt = p0 >= tlen ? 0 : tlen - p0 < kLane ? tlen - p0 : kLane;
+  const u64 first = c0 + (u64)p0;
+  const int wr0 = (int)(first / W);  // the lane's first entry: window relative to w0 (<= kTile), column
+  const u64 cl0 = first - (u64)wr0 * W;
+  const u64 add = (u64)(wn.rw.bos_n + wn.rw.eos_n);
+  int32_t v[kLane] = {pad_id, pad_id, pad_id, pad_id};
+  uint32_t mk = 0;
+  for (;;) {
+    // rows ks .. ks + m - 1, and the offset of row ks + m (k == rows: Wn)
+    const int m = (int)(rows - ks < (u64)kStage ? rows - ks : (u64)kStage);
+    for (int i = tid; i <= m; i += kThreads) {
+      const u64 k = ks + (u64)i;
+      const int64_t rel = (int64_t)(WO[k] - w0);
+      s_w[i] = (int32_t)(rel < -(int64_t)INT32_MAX ? -(int64_t)INT32_MAX : rel > kTile + 1 ? (int64_t)(kTile + 1) : rel);
+      if (i < m) {
+        u64 a, b;
+        wn.rw.bounds(k, &a, &b);
+        s_src[i] = a - (u64)rel * wn.step;
+        s_end[i] = b;
+      }
+    }
+    __syncthreads();
+    // this round resolves the windows [from, lim) relative to w0: those of the staged rows
+    const int from = s_w[0], lim = s_w[m];
+    int wr = wr0, j = -1;
+    u64 c = cl0, start = 0, e = 0, lead = 0;
+    bool fresh = true;
+#pragma unroll
+    for (int i = 0; i < kLane; ++i) {
+      if (i < cnt && wr >= from && wr < lim) {
+        if (fresh) {
+          if (j < 0) {  // the last staged row that starts at or before window wr
+            int a = 0, b = m;
+            while (a < b) {
+              const int mid = (a + b) >> 1;
+              if (s_w[mid] <= wr) a = mid + 1; else b = mid;
+            }
+            j = a - 1;  // >= 0: s_w[0] = from <= wr
+          } else {
+            while (j + 1 < m && s_w[j + 1] <= wr) ++j;
+          }
+          start = s_src[j] + (u64)wr * wn.step;
+          const u64 left = s_end[j] - start;
+          e = add + (left < wn.rw.keep_max ? left : wn.rw.keep_max);
+          lead = pad_left ? W - e : 0;
+          fresh = false;
+          if (c == 0) {
+            const u64 w = w0 + (u64)wr;
+            if (lengths) lengths[w] = (int32_t)e;
+            if (win_row) win_row[w] = (int32_t)(row_base + ks + (u64)j);
+            if (win_src) win_src[w] = (int64_t)(id_base + start);
+          }
+        }
+        if (c >= lead && c - lead < e) {
+          v[i] = wn.rw.id(ids, e, start - (u64)wn.rw.bos_n, c - lead);
+          mk |= 1u << (8 * i);
+        }
+      }
+      if (++c == W) {
+        c = 0;
+        ++wr;
+        fresh = true;
+      }
+    }
+    if (lim > wlast || ks + (u64)m >= rows) break;
+    ks += (u64)m;
+    __syncthreads();
+  }
+  if (cnt == 0) return;
+  const u64 g = t0 + (u64)p0;
+  if (kAligned && cnt == kLane) {
+    *reinterpret_cast<int4*>(out + g) = make_int4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLane; ++i)
+      if (i < cnt) out[g + i] = v[i];
+  }
+  if (mask) {
+    if (mask_aligned && cnt == kLane) {
+      *reinterpret_cast<uint32_t*>(mask + g) = mk;
+    } else {
+#pragma unroll
+      for (int i = 0; i < kLane; ++i)
+        if (i < cnt) mask[g + i] = (uint8_t)(mk >> (8 * i));
+    }
+  }
+}
+
+// W == 0: every row is empty and nothing is added, so window r is row r and holds nothing.
+__global__ __launch_bounds__(kThreads) void k_bat_window_meta(Rows rw, u64 rows, u64 row_base, u64 id_base,
+                                                              int32_t* __restrict__ lengths,
+                                                              int32_t* __restrict__ win_row,
+                                                              int64_t* __restrict__ win_src) {
+  const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= rows) return;
+  u64 a, b;
+  rw.bounds(r, &a, &b);
+  if (lengths) lengths[r] = 0;
+  if (win_row) win_row[r] = (int32_t)(row_base + r);
+  if (win_src) win_src[r] = (int64_t)(id_base + a);
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Grids are one workgroup per tile / 256 rows.
@@ -425,7 +624,121 @@ struct BatchState : PassState {
   }
 };
 
+// The window passes' state, allocated on the first window call (the host path stages through
+// BatchState's buffers and hsrc).  Scratch grown to the most rows seen: 8 B per row (WO) and what
+// the scan and the reduction ask for.
+struct WindowState : PassState {
+  DeviceBuf<u64> wo;           // WO[r]: index of row r's first window; WO[rows] = Wn
+  DeviceBuf<uint8_t> tmp;      // hipCUB scan / reduce scratch
+  DeviceWords res;             // k_bat_rows' words ([0] bad row_off, [1] never set: e_r <= max_len), [2] max e
+  PinnedWords host;            // Wn, then the three words of res
+  EventSet<4> ev;
+  DeviceBuf<int64_t> hsrc;     // host path: a piece's win_src
+
+  bool reserve(size_t rows) {
+    if (!res.ensure(4) || !host.ensure(4) || !ev.ensure() || !wo.grow(rows + 1)) return false;
+    const Rows rw{nullptr, 0, 1, 0, 0, 0, 0, 0};
+    size_t scan = 0, red = 0;
+    if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, WOIter(hipcub::CountingInputIterator<u64>(0), WOInput{{rw, 1}}),
+                                         wo.get(), (u64)rows + 1) != hipSuccess)
+      return false;
+    if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
+                                  res.get() + 2, (u64)std::max<size_t>(rows, 1)) != hipSuccess)
+      return false;
+    return tmp.grow(std::max<size_t>(std::max(scan, red), 16));
+  }
+
+  // Row checks (when c.row), WO into wo and the longest window over c's rows: 0, -1, -6.
+  int lengths(const BatchCall& c, const Windows& wn, hipStream_t st, uint64_t* windows, uint64_t* widest) {
+    ENC_OK(hipMemsetAsync(res.get(), 0, 32, st));
+    if (c.row) {
+      k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(wn.rw, c.rows,
+                                                                                              c.ends ? 1 : 0, res.get());
+      ENC_OK(hipGetLastError());
+    }
+    size_t bytes = tmp.cap();
+    ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, WOIter(hipcub::CountingInputIterator<u64>(0), WOInput{wn}),
+                                            wo.get(), c.rows + 1, st));
+    ENC_OK(hipMemcpyAsync(host.get(), wo.get() + c.rows, 8, hipMemcpyDeviceToHost, st));
+    if (c.rows) {
+      bytes = tmp.cap();
+      ENC_OK(hipcub::DeviceReduce::Max(tmp.get(), bytes, WIter(hipcub::CountingInputIterator<u64>(0), WInput{wn.rw}),
+                                       res.get() + 2, c.rows, st));
+    }
+    ENC_OK(hipMemcpyAsync(host.get() + 1, res.get(), 24, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    if (host[1]) return -6;
+    *windows = host[0];
+    *widest = host[3];
+    return 0;
+  }
+
+  // The call's windows [0, windows) from wo into out / lengths / mask / win_row / win_src (which
+  // point at the call's first window); win_row gets c.row_base added and win_src c.base.
+  int expand(const BatchCall& c, const Windows& wn, uint64_t windows, uint64_t width, int32_t pad_id, int pad_side,
+             int32_t* out, int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, hipStream_t st) {
+    const u64 total = windows * width;
+    if (!windows) return 0;
+    if (!total) {  // width == 0: every row is empty, window r is row r
+      if (lengths || win_row || win_src) {
+        k_bat_window_meta<<<dim3((unsigned)((c.rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(
+            wn.rw, c.rows, c.row_base, c.base, lengths, win_row, win_src);
+        ENC_OK(hipGetLastError());
+      }
+      return 0;
+    }
+    const u64 tiles = (total + kTile - 1) / kTile;
+    (aligned16(out) ? k_bat_window<true> : k_bat_window<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
+        c.ids, wn, c.rows, wo.get(), width, total, pad_id, pad_side ? 1u : 0u, c.row_base, c.base, out, lengths, mask,
+        (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? 1u : 0u, win_row, win_src);
+    ENC_OK(hipGetLastError());
+    return 0;
+  }
+};
+
 }  // namespace
+
+int64_t EncodeDevice::window(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                             size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap,
+                             int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, int64_t* row_win,
+                             size_t* widest_out, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  const u64 R = row_off ? rows : 1;
+  if (!rows_fit(R)) return -1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  WindowState& ws = pass_state<WindowState>(pass_[kWindow]);
+  if (!ws.reserve(R)) {
+    std::fprintf(stderr, "[ERROR]\t encoder: window allocation failed (%zu rows)\n", (size_t)R);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
+  const EventSet<4>& ev = ws.ev;
+  const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
+  const Windows wn = windows_of(o, stride, row_off, n);
+  u64 windows = 0, widest = 0;
+  ENC_OK(hipEventRecord(ev[0], st));
+  const int r = ws.lengths(c, wn, st, &windows, &widest);
+  if (r < 0) return r;
+  ENC_OK(hipEventRecord(ev[1], st));
+  if (windows > (u64)INT64_MAX || (width && windows > (u64)INT64_MAX / width)) return -1;
+  const bool expand = out && width >= widest && cap >= windows * width;
+  if (expand) {
+    if (!tiles_fit(windows * width)) return -1;
+    ENC_OK(hipEventRecord(ev[2], st));
+    if (row_win) {
+      k_bat_row_start<<<dim3((unsigned)((R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(ws.wo.get(), R, 0,
+                                                                                              row_win);
+      ENC_OK(hipGetLastError());
+    }
+    if (ws.expand(c, wn, windows, width, pad_id, pad_side, out, lengths, mask, win_row, win_src, st) < 0) return -1;
+    ENC_OK(hipEventRecord(ev[3], st));
+  }
+  ENC_OK(hipStreamSynchronize(st));
+  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
+  if (widest_out) *widest_out = (size_t)widest;
+  return (int64_t)windows;
+}
 
 int64_t EncodeDevice::pad(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                           size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths,
@@ -587,6 +900,74 @@ int EncodeDevice::pack_host(const int32_t* ids, size_t n, const int64_t* row_off
     if (row_start) ENC_OK(hipMemcpyAsync(row_start + r0 + 1, dstart + 1, m * 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
     done += total;
+    r0 = r1;
+  }
+  return 0;
+}
+
+// A window piece is the windows of its own rows, written to windows [w0, w1) of the outputs.  The
+// caller has validated row_off, width and cap on the host, so no length pass runs: the piece's WO
+// is made here and uploaded, and row_win is written from it.  A piece takes whole rows while it
+// holds at most `piece` ids, `piece` rows and 4 x piece output entries; at least one row.
+int EncodeDevice::window_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                              size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out,
+                              int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, int64_t* row_win) {
+  const size_t R = row_off ? rows : 1;
+  DeviceGuard guard;
+  ENC_OK(hipSetDevice(device_));
+  const size_t piece = piece_ids();
+  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
+  WindowState& ws = pass_state<WindowState>(pass_[kWindow]);
+  hipStream_t st = (hipStream_t)stream_;
+  const u64 C = o.max_len - ((o.has_bos ? 1 : 0) + (o.has_eos ? 1 : 0)), step = C - stride;
+  const auto count = [&](size_t r) {
+    return window_count(row_off ? (u64)(row_off[r + 1] - row_off[r]) : (u64)n, C, step);
+  };
+  std::vector<int64_t> local;
+  std::vector<u64> wo;
+  u64 w0 = 0;
+  if (row_win) row_win[0] = 0;
+  for (size_t r0 = 0; r0 < R;) {
+    wo.assign(1, 0);
+    size_t r1 = r0;
+    do {
+      wo.push_back(wo.back() + count(r1));
+      ++r1;
+    } while (r1 < R && r1 - r0 < piece && (u64)(row_off[r1 + 1] - row_off[r0]) <= (u64)piece &&
+             (wo.back() + count(r1)) * width <= 4 * (u64)piece);
+    const size_t m = r1 - r0, wp = (size_t)wo.back();
+    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
+    const size_t cells = wp * width;
+    if (!tiles_fit(cells) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2) || !ws.wo.grow(m + 1) ||
+        !bs.hout.grow(std::max(cells, wp), 3) || (mask && !bs.hmask.grow(std::max<size_t>(cells, 1))) ||
+        (win_src && !ws.hsrc.grow(wp))) {
+      std::fprintf(stderr, "[ERROR]\t encoder: window staging allocation failed (%zu ids, %zu rows, %zu windows)\n", len,
+                   m, wp);
+      return -1;
+    }
+    int32_t *const dids = bs.hids.get(), *const dout = bs.hout.get(), *const dlen = dout + bs.hout.cap(),
+                   *const drow = dlen + bs.hout.cap();
+    if (len) ENC_OK(hipMemcpyAsync(dids, ids + a, len * 4, hipMemcpyHostToDevice, st));
+    if (row_off) {
+      local.resize(m + 1);
+      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
+      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    ENC_OK(hipMemcpyAsync(ws.wo.get(), wo.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
+    const BatchCall c{dids, len, row_off ? bs.hrow.get() : nullptr, m, false, o, a, r0};
+    const Windows wn = windows_of(o, stride, c.row, len);
+    if (ws.expand(c, wn, wp, width, pad_id, pad_side, dout, lengths ? dlen : nullptr, mask ? bs.hmask.get() : nullptr,
+                  win_row ? drow : nullptr, win_src ? ws.hsrc.get() : nullptr, st) < 0)
+      return -1;
+    if (cells) ENC_OK(hipMemcpyAsync(out + w0 * width, dout, cells * 4, hipMemcpyDeviceToHost, st));
+    if (lengths) ENC_OK(hipMemcpyAsync(lengths + w0, dlen, wp * 4, hipMemcpyDeviceToHost, st));
+    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + w0 * width, bs.hmask.get(), cells, hipMemcpyDeviceToHost, st));
+    if (win_row) ENC_OK(hipMemcpyAsync(win_row + w0, drow, wp * 4, hipMemcpyDeviceToHost, st));
+    if (win_src) ENC_OK(hipMemcpyAsync(win_src + w0, ws.hsrc.get(), wp * 8, hipMemcpyDeviceToHost, st));
+    if (row_win)
+      for (size_t i = 1; i <= m; ++i) row_win[r0 + i] = (int64_t)(w0 + wo[i]);
+    ENC_OK(hipStreamSynchronize(st));
+    w0 += wp;
     r0 = r1;
   }
   return 0;

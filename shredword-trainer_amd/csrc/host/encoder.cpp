@@ -459,4 +459,52 @@ int64_t shred_pack_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const i
   return r < 0 ? r : (int64_t)S;
 }
 
+namespace {
+// What the two window calls refuse before any work (0 or -1), and their options.
+int window_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                const int32_t* bos, const int32_t* eos, size_t max_len, size_t stride, int pad_side,
+                const void* win_row, shred::EncodeDevice::BatchOpts* o) {
+  if (batch_args(enc, ids, n, row_off, rows, bos, eos, max_len, 0, o) || pad_side < 0 || pad_side > 1) return -1;
+  const size_t add = (bos ? 1 : 0) + (eos ? 1 : 0);
+  if (max_len <= add || max_len > (size_t)INT32_MAX || stride >= max_len - add) return -1;
+  if (win_row && rows > (size_t)INT32_MAX) return -1;
+  return 0;
+}
+}  // namespace
+
+int64_t shred_window_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                            const int32_t* bos, const int32_t* eos, size_t max_len, size_t stride, size_t width,
+                            int32_t pad_id, int pad_side, void* out, size_t cap, void* lengths, void* mask,
+                            void* win_row, void* win_src, void* row_win, size_t* widest, void* stream,
+                            double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::BatchOpts o;
+  if (window_args(enc, ids, n, row_off, rows, bos, eos, max_len, stride, pad_side, win_row, &o)) return -1;
+  return enc->dev->window((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, stride, width, pad_id, pad_side,
+                          (int32_t*)out, cap, (int32_t*)lengths, (uint8_t*)mask, (int32_t*)win_row, (int64_t*)win_src,
+                          (int64_t*)row_win, widest, stream, kernel_ms);
+}
+
+int64_t shred_window_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          const int32_t* bos, const int32_t* eos, size_t max_len, size_t stride, size_t width,
+                          int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask,
+                          int32_t* win_row, int64_t* win_src, int64_t* row_win, size_t* widest) {
+  shred::EncodeDevice::BatchOpts o;
+  if (window_args(enc, ids, n, row_off, rows, bos, eos, max_len, stride, pad_side, win_row, &o)) return -1;
+  // the length pass of host rows: max_len bounds every window, so only row_off can be wrong
+  uint64_t total = 0, first = 0;
+  if (const int r = batch_host_lengths(n, row_off, rows, o, &total, &first)) return r;
+  const uint64_t add = (bos ? 1 : 0) + (eos ? 1 : 0), C = max_len - add, step = C - stride;
+  const uint64_t R = row_off ? rows : 1;
+  uint64_t Wn = 0;
+  for (size_t r = 0; r < R; ++r)
+    Wn += shred::window_count(row_off ? (uint64_t)(row_off[r + 1] - row_off[r]) : (uint64_t)n, C, step);
+  if (Wn > (uint64_t)INT64_MAX || (width && Wn > (uint64_t)INT64_MAX / width)) return -1;
+  if (widest) *widest = (size_t)first;
+  if (!out || width < first || cap < Wn * width) return (int64_t)Wn;
+  const int r = enc->dev->window_host(ids, n, row_off, rows, o, stride, width, pad_id, pad_side, out, lengths, mask,
+                                      win_row, win_src, row_win);
+  return r < 0 ? r : (int64_t)Wn;
+}
+
 }  // extern "C"

@@ -32,6 +32,12 @@ constexpr int kDecMaxUnk = 8;                       // SHRED_DECODE_MAX_UNK
 bool enc_build_arena(const std::vector<int32_t>& first, const std::vector<int32_t>& second,
                      std::vector<uint32_t>* off, std::vector<uint8_t>* bytes);
 
+// Windows of a row of len ids, C ids each and step ids apart (shred_window_*): the host's count and
+// the kernels' (constexpr: usable in device code too).
+constexpr uint64_t window_count(uint64_t len, uint64_t C, uint64_t step) {
+  return len <= C ? 1 : 1 + (len - C + step - 1) / step;
+}
+
 // What one family of passes owns on the device; the units derive theirs from the resources of
 // hip/encode_common.h.
 struct PassState {
@@ -132,6 +138,18 @@ class EncodeDevice {
   int pack_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                 uint64_t out_len, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg, int64_t* row_start);
 
+  // ---- long rows cut into overlapping windows (batch_device.hip; shred_window_*).  o.max_len is C +
+  // add with C >= 1, o.trunc_side 0, stride < C (the callers have checked).  window takes device
+  // buffers and returns Wn, -1 or -6, with the longest window in *widest; window_host takes host
+  // buffers whose row_off, width and cap the caller has checked on the host and returns 0 or -1.
+  int64_t window(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o, size_t stride,
+                 size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask,
+                 int32_t* win_row, int64_t* win_src, int64_t* row_win, size_t* widest, void* stream,
+                 double* kernel_ms);
+  int window_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o, size_t stride,
+                  size_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths, uint8_t* mask,
+                  int32_t* win_row, int64_t* win_src, int64_t* row_win);
+
  private:
   EncodeDevice() = default;
   // Span passes over n text bytes and their T ids (both on the device): starts[k] = start_base +
@@ -154,7 +172,7 @@ class EncodeDevice {
   bool sx_dirty_ = false;          // the scan table on the device is older than the set
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
-  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kPasses };
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -197,3 +197,11 @@ lib.shred_pack_device.restype = c_int64
 lib.shred_pack_rows.argtypes = _batch_rows + [c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                               c_void_p]
 lib.shred_pack_rows.restype = c_int64
+# long rows cut into overlapping windows: max_len, stride, width, pad_id, pad_side, out, cap, lengths, mask, win_row,
+# win_src, row_win, widest
+_window_rows = _batch_rows[:-1] + [c_size_t, c_size_t, c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, POINTER(c_size_t)]
+lib.shred_window_device.argtypes = _window_rows + [c_void_p, POINTER(c_double)]
+lib.shred_window_device.restype = c_int64
+lib.shred_window_rows.argtypes = _window_rows
+lib.shred_window_rows.restype = c_int64

@@ -24,8 +24,8 @@ MAX_SPECIAL_LEN = 64   # SHRED_SPECIAL_MAX_LEN
 # the strict-mode id check (kChunk)
 DECODE_TILE = 4096
 DECODE_CHUNK = 4096
-# batch_device.hip: output entries per workgroup of the pad and pack kernels (kTile), rows the pack
-# kernel stages in LDS per round (kStage)
+# batch_device.hip: output entries per workgroup of the pad, pack and window kernels (kTile), rows the
+# pack and window kernels stage in LDS per round (kStage)
 BATCH_TILE = 1024
 BATCH_STAGE = 512
 
@@ -541,6 +541,81 @@ class BPEEncoder:
         res += (pos[:S * L].view(S, L),) if positions else ()
         return res + ((seg[:S * L].view(S, L),) if segments else ()) + (ms.value,)
 
+    # ---- long rows cut into overlapping windows (include/shredword_encode.h, shred_window_*) -------
+
+    @classmethod
+    def _window_args(cls, bos, eos, max_len, stride, pad_id, pad):
+        """-> (bos pointer, eos pointer, max_len, stride, pad_id, pad_side) as the C ABI takes them."""
+        if pad not in ("left", "right"):
+            raise ValueError('pad must be "left" or "right"')
+        add = (bos is not None) + (eos is not None)
+        ml, sd = int(max_len), int(stride)
+        if not add < ml < 2 ** 31:
+            raise ValueError(f"max_len must hold the {add} added ids and at least one more, and fit an int32")
+        if not 0 <= sd < ml - add:
+            raise ValueError(f"stride must be in [0, max_len - {add}): a window must move on by at least one id")
+        b, e, _, _, pid = cls._batch_args(bos, eos, ml, "right", pad_id)
+        return b, e, ml, sd, pid, int(pad == "left")
+
+    def window_rows(self, ids, row_offsets=None, *, max_len, stride=0, bos=None, eos=None, pad_id=0, pad="right",
+                    width=None, mask=False):
+        """-> (batch, lengths, window_rows, window_src, row_windows[, mask]): every row
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row) cut into windows of at most max_len ids,
+        [bos] and [eos] included, that overlap by `stride` ids ("overflowing tokens with a stride").
+        Nothing is dropped: a row longer than a window takes several rows of the batch, and an empty
+        row one.  batch: int32 [windows, width] (width None: the longest window), padded with pad_id on
+        the `pad` side; lengths: int32 [windows]; window_rows: int32 [windows], the row of each window;
+        window_src: int64 [windows], the index in ids of the window's first id (ids[window_src[w] + c -
+        (bos is not None)] sits at batch[w, c], and the same index into the starts of encode_spans /
+        encode_docs is its byte offset); row_windows: int64 [rows + 1], row r owns the windows
+        [row_windows[r], row_windows[r + 1]); mask: uint8 [windows, width], 1 on tokens.  Built on the GPU."""
+        b, e, ml, sd, pid, ps = self._window_args(bos, eos, max_len, stride, pad_id, pad)
+        a, row, R = self._host_rows(ids, row_offsets)
+        args = (self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data,
+                0 if row is None else R, b, e, ml, sd)
+        widest = ctypes.c_size_t()
+        Wn = self._check_batch(lib.shred_window_rows(*args, 0, pid, ps, None, 0, None, None, None, None, None,
+                                                     ctypes.byref(widest)))
+        W = widest.value if width is None else int(width)
+        if W < widest.value:
+            raise ValueError(f"width {W} is smaller than the longest window ({widest.value} ids)")
+        out = np.empty(max(1, Wn * W), dtype=np.int32)
+        lengths, wrow = (np.empty(max(1, Wn), dtype=np.int32) for _ in range(2))
+        wsrc = np.empty(max(1, Wn), dtype=np.int64)
+        roww = np.empty(R + 1, dtype=np.int64)
+        m = np.empty(max(1, Wn * W), dtype=np.uint8) if mask else None
+        self._check_batch(lib.shred_window_rows(*args, W, pid, ps, out.ctypes.data, Wn * W, lengths.ctypes.data,
+                                                None if m is None else m.ctypes.data, wrow.ctypes.data,
+                                                wsrc.ctypes.data, roww.ctypes.data, None))
+        res = (out[:Wn * W].reshape(Wn, W), lengths[:Wn], wrow[:Wn], wsrc[:Wn], roww)
+        return res + ((m[:Wn * W].reshape(Wn, W),) if mask else ())
+
+    def window_device(self, ids, row_offsets=None, *, max_len, stride=0, bos=None, eos=None, pad_id=0, pad="right",
+                      width=None, mask=False, stream=None):
+        """window_rows on device tensors (as pad_device takes them) -> (batch, lengths, window_rows,
+        window_src, row_windows[, mask], device milliseconds of the window passes)."""
+        import torch
+        b, e, ml, sd, pid, ps = self._window_args(bos, eos, max_len, stride, pad_id, pad)
+        R = self._device_rows(ids, row_offsets)
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
+                0 if row_offsets is None else R, b, e, ml, sd)
+        widest, ms = ctypes.c_size_t(), ctypes.c_double()
+        Wn = self._check_batch(lib.shred_window_device(*args, 0, pid, ps, None, 0, None, None, None, None, None,
+                                                       ctypes.byref(widest), st, None))
+        W = widest.value if width is None else int(width)
+        if W < widest.value:
+            raise ValueError(f"width {W} is smaller than the longest window ({widest.value} ids)")
+        new = lambda dt, k: torch.empty(max(1, k), dtype=dt, device=ids.device)
+        out, lengths, wrow = new(torch.int32, Wn * W), new(torch.int32, Wn), new(torch.int32, Wn)
+        wsrc, roww = new(torch.int64, Wn), new(torch.int64, R + 1)
+        m = new(torch.uint8, Wn * W) if mask else None
+        self._check_batch(lib.shred_window_device(*args, W, pid, ps, out.data_ptr(), Wn * W, lengths.data_ptr(),
+                                                  None if m is None else m.data_ptr(), wrow.data_ptr(),
+                                                  wsrc.data_ptr(), roww.data_ptr(), None, st, ctypes.byref(ms)))
+        res = (out[:Wn * W].view(Wn, W), lengths[:Wn], wrow[:Wn], wsrc[:Wn], roww)
+        return res + ((m[:Wn * W].view(Wn, W),) if mask else ()) + (ms.value,)
+
     def _encode_rows(self, text, specials, doc_offsets):
         """(ids, row_offsets): documents when text is a list / tuple or doc_offsets is given, else lines."""
         if isinstance(text, (list, tuple)):
@@ -562,6 +637,12 @@ class BPEEncoder:
         a list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): every document is."""
         ids, row = self._encode_rows(text, specials, doc_offsets)
         return self.pack_rows(ids, row, **kw)
+
+    def encode_windows(self, text, *, specials: bool = False, doc_offsets=None, **kw):
+        """encode_lines, then window_rows(**kw): every '\\n' line of the text is cut into windows.  With
+        a list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): every document is."""
+        ids, row = self._encode_rows(text, specials, doc_offsets)
+        return self.window_rows(ids, row, **kw)
 
     def destroy(self):
         if getattr(self, "enc", None):

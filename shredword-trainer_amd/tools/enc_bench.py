@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | special | docs]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs]   (SHREDWORD_LIB picks the build)
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
 GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
@@ -7,7 +7,11 @@ trailing `batch`, the decode leg and then pad_device (rows cut to 1024 ids, with
 pack_device (an eos per row, sequences of 2048, positions and segments) on the corpus's ids and line
 offsets: device ms and effective GB/s by the traffic model of batch_device.hip, and the torch
 composition (torch.full, an index from repeat_interleave of the lengths, a scatter) on the same
-tensors, timed with device events in the same process after a warm-up; with a trailing `special`,
+tensors, timed with device events in the same process after a warm-up; with a trailing `window`,
+window_device (max_len 1024, stride 128, with the mask) on the corpus's ids and line offsets: device ms
+and effective GB/s by the traffic model of batch_device.hip, pad_device at the same width on the same
+rows (rows cut to 1024 ids: the same output size when no line is longer than a window), and a torch
+gather (an index of window starts plus columns, a masked take) on the same tensors; with a trailing `special`,
 "<|endoftext|>" is put in front of the first '\\n' after every 2048th byte of the corpus, and that
 text is timed through encode_spans_device without and with specials=True (the encode, span and
 special passes of one call each); with a trailing `docs`, the corpus is one document per line (doc_offsets
@@ -42,8 +46,8 @@ else:
     args = sys.argv[3:]
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
-    special, docs = args[-1] == "special", args[-1] == "docs"
-    if spans or decode or special or docs:
+    special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
+    if spans or decode or special or docs or window:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -229,4 +233,58 @@ else:
               nbytes / ms[len(ms) // 2] / 1e6, "of 8 TB/s", nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0],
               "max", ms[-1], "| whole call (sizing call, allocation, passes) ms", c[0],
               "| torch ms", t[0], "min", t[1], "max", t[2], flush=True)
+    if window:
+        del out
+        reps = max(reps, 5)
+        ids, _, line, _ = enc.encode_spans_device(text, starts=False)
+        R, n, W, S = line.numel() - 1, ids.numel(), 1024, 128
+        step = W - S
+
+        def timed(fn):
+            """median / min / max device ms of fn() over reps runs, after two warm-up runs"""
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            ms.sort()
+            return ms[len(ms) // 2], ms[0], ms[-1]
+
+        def torch_window():
+            lens = line[1:] - line[:-1]
+            w = torch.where(lens <= W, torch.ones_like(lens), 1 + (lens - W + step - 1) // step)
+            wo = torch.cat([w.new_zeros(1), w.cumsum(0)])
+            Wn = int(wo[-1].item())
+            wrow = torch.repeat_interleave(torch.arange(R, device="cuda"), w, output_size=Wn)
+            src = line[:-1][wrow] + (torch.arange(Wn, device="cuda") - wo[:-1][wrow]) * step
+            cnt = (line[1:][wrow] - src).clamp(max=W)
+            col = torch.arange(W, device="cuda")
+            m = col[None, :] < cnt[:, None]
+            out = torch.where(m, ids[(src[:, None] + col[None, :]).clamp(max=max(n - 1, 0))], -1)
+            return out, cnt.to(torch.int32), wrow.to(torch.int32), src, wo, m.to(torch.uint8)
+
+        kw = dict(max_len=W, stride=S, width=W, pad_id=-1, mask=True)
+        ours = enc.window_device(ids, line, **kw)  # first call: allocates the window scratch
+        assert all(torch.equal(a, b) for a, b in zip(ours[:6], torch_window()))
+        Wn = ours[0].shape[0]
+        ms = sorted(enc.window_device(ids, line, **kw)[6] for _ in range(reps))
+        fill = ours[1].sum().item() / (Wn * W)
+        nbytes = Wn * W * (4 + 4 * fill + 1) + 16 * Wn + 40 * R
+        t, c = timed(torch_window), timed(lambda: enc.window_device(ids, line, **kw))
+        print("window: rows", R, "windows", Wn, "width", W, "stride", S, "fill", fill, "ms", ms[len(ms) // 2], "GB/s",
+              nbytes / ms[len(ms) // 2] / 1e6, "of 8 TB/s", nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0], "max",
+              ms[-1], "| whole call (sizing call, allocation, passes) ms", c[0],
+              "| torch gather ms", t[0], "min", t[1], "max", t[2], flush=True)
+        pad_kw = dict(max_len=W, width=W, pad_id=-1, mask=True)
+        ours = enc.pad_device(ids, line, **pad_kw)
+        ms = sorted(enc.pad_device(ids, line, **pad_kw)[3] for _ in range(reps))
+        fill = ours[1].sum().item() / (R * W)
+        nbytes = R * W * (4 + 4 * fill + 1) + 16 * R
+        print("pad at the same width: rows", R, "fill", fill, "ms", ms[len(ms) // 2], "GB/s",
+              nbytes / ms[len(ms) // 2] / 1e6, "min", ms[0], "max", ms[-1], flush=True)
     enc.destroy()
