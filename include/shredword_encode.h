@@ -26,9 +26,13 @@
 extern "C" {
 #endif
 
+/* Longest word an encoder in long-word mode accepts (bytes; shred_encoder_set_long_words below). */
+#define SHRED_ENCODE_MAX_LONG_WORD (1u << 20)
+
 typedef struct ShredEncoder ShredEncoder;
 
-/* Longest word the encoder accepts (bytes); a longer word fails the call with -3. */
+/* Longest word the encoder accepts (bytes); a longer word fails the call with -3, unless the
+ * encoder's long-word mode is on (below). */
 #define SHRED_ENCODE_MAX_WORD 1024
 
 /* merges: num_merges triples (first, second, new_id) as in a .model file; new_id must be 256 + m
@@ -48,9 +52,42 @@ void shred_encoder_destroy(ShredEncoder* enc);
 /* num_merges and the 256-entry byte map of an encoder (either pointer may be NULL). */
 int shred_encoder_info(const ShredEncoder* enc, size_t* num_merges, int32_t* byte_map);
 
+/* ---- words longer than SHRED_ENCODE_MAX_WORD ---------------------------------------------------
+ *
+ * Text without ASCII whitespace (CJK or Thai paragraphs, base64 blobs, minified code, long URLs)
+ * holds words of any length.  By default such a word fails the call; with the long-word mode on it
+ * is encoded, by a pass of its own in which one workgroup takes one word.  The ids are defined
+ * exactly as for every other word (merge m applied left to right without overlap, for m = 0, 1,
+ * ...), and nothing else about any output changes: word-begin rules, starts, line_off, row_off, the
+ * byte map and the token lengths are as described below.
+ *
+ * Where the limit applies is unchanged: for shred_encode_special to the run before it is cut, for
+ * shred_encode_docs to the words after the boundary cut.  The host calls keep cutting pieces after a
+ * delimiter; a piece budget that falls inside a long word extends the piece to the end of that
+ * word, which is staged whole (the rule a long document and a long row have).
+ *
+ * Cost.  With the mode off: none, and nothing is allocated.  With it on, every encode call reads
+ * the text once more to find the long words (and waits for the count).  Scratch is allocated on the
+ * first long word and freed with the encoder: 16 B per long word, 4 B per 32 text bytes, and, once
+ * a word above 18432 bytes is met, 4 B per text byte.  A long word takes one round per distinct merge
+ * rank that applies to it (at most min(num_merges, length - 1)), each round one pass of one
+ * workgroup over the word's current tokens: natural text of 1 MB in one word took 1.6 s
+ * under 7,936 merges, against 22 ms for 1 GB of ordinary text.
+ */
+/* on != 0: every encode call accepts words of up to SHRED_ENCODE_MAX_LONG_WORD bytes; words above
+ * SHRED_ENCODE_MAX_WORD are encoded by the long-word pass.  -3 then means a word above the long
+ * limit.  Default off.  Returns 0, -1 for NULL. */
+int shred_encoder_set_long_words(ShredEncoder* enc, int on);
+int shred_encoder_long_words(const ShredEncoder* enc);
+/* What the long-word pass holds and has done (each pointer may be NULL): the bytes of device
+ * scratch it has allocated (0 until a call meets a long word), the long words it has encoded and
+ * the rounds it has run since the encoder was created.  Returns 0, -1 for NULL. */
+int shred_encoder_long_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* words, uint64_t* rounds);
+
 /* Encodes n bytes of host text into host ids.  Returns the number of ids written (<= the number
  * of non-delimiter bytes, so cap >= n always suffices), or -1 on a bad argument / device error,
- * -2 when cap is smaller than the result, -3 when a word exceeds SHRED_ENCODE_MAX_WORD. */
+ * -2 when cap is smaller than the result, -3 when a word exceeds SHRED_ENCODE_MAX_WORD (with the
+ * long-word mode on: SHRED_ENCODE_MAX_LONG_WORD; so for every -3 below). */
 int64_t shred_encode(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap);
 
 /* The same on device buffers (text: n bytes, out: cap >= n int32, both on the encoder's device),

@@ -181,15 +181,24 @@ inline size_t piece_from_env(const char* name, size_t def, size_t minimum) {
 inline bool host_is_delim(uint8_t c) { return c == 9 || c == 10 || c == 13 || c == 32; }
 
 // Length of the text piece at pos: at most `piece` bytes, ending just after its last delimiter
-// (words never straddle two pieces, so the ids are those of one call); 0 = no delimiter in the
-// last kEncMaxWord + 1 bytes: a word past the limit.
-inline size_t host_piece_len(const uint8_t* text, size_t n, size_t pos, size_t piece) {
+// (words never straddle two pieces, so the ids are those of one call); 0 = a word past the limit
+// maxw.  With maxw == kEncMaxWord that is "no delimiter in the last kEncMaxWord + 1 bytes".  With a
+// larger maxw (long-word mode) a budget that falls inside a longer word extends the piece forward
+// to that word's end: the word is staged whole (pos is never inside a word).
+inline size_t host_piece_len(const uint8_t* text, size_t n, size_t pos, size_t piece,
+                             size_t maxw = (size_t)kEncMaxWord) {
   size_t len = std::min(piece, n - pos);
   if (pos + len < n) {
     size_t k = len;
     const size_t lo = len > (size_t)kEncMaxWord + 1 ? len - (size_t)kEncMaxWord - 1 : 0;
     while (k > lo && !host_is_delim(text[pos + k - 1])) --k;
-    if (k == lo) return 0;
+    if (k == lo) {
+      if (maxw <= (size_t)kEncMaxWord) return 0;
+      while (k > 0 && len - k <= maxw && !host_is_delim(text[pos + k - 1])) --k;  // the word starts at pos + k
+      size_t e = len;
+      while (pos + e < n && e - k <= maxw && !host_is_delim(text[pos + e])) ++e;
+      return e - k > maxw ? 0 : e;
+    }
     len = k;
   }
   return len;

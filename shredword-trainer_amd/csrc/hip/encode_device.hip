@@ -42,17 +42,7 @@ namespace {
 typedef uint64_t u64;
 
 constexpr int kStrip = 32;                 // tokens a word keeps in LDS (32 KB per workgroup)
-constexpr int kInf = 0x7fffffff;
-
-__device__ __forceinline__ int pair_rank(const u64* __restrict__ tab, u64 mask, int a, int b) {
-  if ((uint32_t)a >= (uint32_t)kEncIdLimit || (uint32_t)b >= (uint32_t)kEncIdLimit) return kInf;
-  const u64 key = (u64)(uint32_t)a << 20 | (u64)(uint32_t)b;
-  for (u64 i = ((key * 0x9E3779B97F4A7C15ull) >> 24) & mask;; i = (i + 1) & mask) {
-    const u64 e = tab[i];
-    if (e == kEncEmpty) return kInf;
-    if ((e >> 20) == key) return (int)(e & 0xFFFFFu);
-  }
-}
+// (pair_rank and kInf: encode_words.h)
 
 // Lowest-rank merging of tok[0..m) with cached ranks rk[0..m-1) (LDS strip or global scratch).
 // Returns the final length.
@@ -153,7 +143,8 @@ __global__ __launch_bounds__(kThreads) void k_encode_words(const uint8_t* __rest
                                                            const u64* __restrict__ tab, u64 mask,
                                                            int32_t* __restrict__ pad, int32_t* __restrict__ rank,
                                                            uint32_t* __restrict__ tcnt, u64* __restrict__ bcnt,
-                                                           u64* __restrict__ misc) {
+                                                           u64* __restrict__ misc,
+                                                           const uint32_t* __restrict__ lcnt) {
   __shared__ int s_map[256];
   __shared__ int s_strip[(kPacked ? 1 : 2) * kStrip * kThreads];
   __shared__ uint32_t s_sum;
@@ -194,7 +185,17 @@ __global__ __launch_bounds__(kThreads) void k_encode_words(const uint8_t* __rest
         L = e - s;
       }
       if (L > (u64)kEncMaxWord) {
-        atomicOr(reinterpret_cast<unsigned long long*>(misc + 1), 1ull);
+        if (!lcnt) {
+          atomicOr(reinterpret_cast<unsigned long long*>(misc + 1), 1ull);
+          continue;
+        }
+        // long-word mode: the long pass (encode_long.hip) left the ids at pad + s and their count
+        // at the span's entry of lcnt; wpos <= s, so the ascending copy is safe
+        const uint32_t m = lcnt[(u64)blockIdx.x * kThreads + tid];
+        if (wpos != s)
+          for (uint32_t k = 0; k < m; ++k) pad[wpos + k] = pad[s + k];
+        wpos += m;
+        cnt += m;
         continue;
       }
       // a long word's tokens at pad + s: wpos <= s, so the ascending copy to pad + wpos is safe
@@ -259,13 +260,14 @@ __device__ __forceinline__ void flag(u64* misc, u64 bit) {
 }
 
 __global__ __launch_bounds__(kThreads) void k_cache_insert(const uint8_t* __restrict__ text, u64 n,
-                                                           u64* __restrict__ slot, u64 cmask, u64* __restrict__ misc) {
+                                                           u64* __restrict__ slot, u64 cmask, u64* __restrict__ misc,
+                                                           bool long_words) {
   __shared__ uint32_t s_text[kStageBytes / 4];
   const TextView tv = stage_chunk(text, n, blockIdx.x, s_text);
   const u64 base = (u64)blockIdx.x * kChunk + (u64)threadIdx.x * kSpan;
   for_each_word(tv, n, base, [&](u64 s, u64 L, int) {
-    if (L > (u64)kEncMaxWord) {
-      flag(misc, 1);
+    if (L > (u64)kEncMaxWord) {  // never cached (the payload's fields hold 16 bits): the long pass's, or an error
+      if (!long_words) flag(misc, 1);
       return;
     }
     const u64 h = word_hash(tv, s, (uint32_t)L);
@@ -343,11 +345,14 @@ __global__ __launch_bounds__(kThreads) void k_cache_encode(const uint8_t* __rest
 // that also published its inclusive sum (status 2), and publishes its own.  The states are 8-B
 // agent atomics on both sides (cross-XCD coherent).  No staging copy of the ids.
 constexpr u64 kLbValue = (1ull << 62) - 1;
+constexpr uint32_t kLongEntry = 0xFFFFFFFFu;  // s_list: the span's long word (no slot has index 2^31 - 1)
 __global__ __launch_bounds__(kThreads) void k_cache_words(const uint8_t* __restrict__ text, u64 n,
                                                           const u64* __restrict__ slot, u64 cmask,
                                                           const int32_t* __restrict__ arena, int32_t* __restrict__ out,
                                                           u64 out_cap, u64* __restrict__ bcnt, u64* __restrict__ lb,
-                                                          u64 nb, u64* __restrict__ misc) {
+                                                          u64 nb, u64* __restrict__ misc,
+                                                          const int32_t* __restrict__ lids,
+                                                          const uint32_t* __restrict__ lcnt) {
   __shared__ uint32_t s_text[kStageBytes / 4];
   __shared__ uint32_t s_list[kSpanWords * kThreads];  // this chunk's words: arena offsets, column per thread
   __shared__ uint32_t s_inc[kThreads];
@@ -362,8 +367,19 @@ __global__ __launch_bounds__(kThreads) void k_cache_words(const uint8_t* __restr
   const u64 cbase = chunk * kChunk;
   const u64 base = cbase + (u64)tid * kSpan;
   uint32_t cnt = 0, nw = 0;
+  uint32_t lm = 0;  // long-word mode: the id count of the span's long word (its last word), ids at lids + ls
+  u64 ls = 0;
   for_each_word(tv, n, base, [&](u64 s, u64 L, int) {
-    if (L > (u64)kEncMaxWord) return;  // flagged by k_cache_insert
+    if (L > (u64)kEncMaxWord) {  // flagged by k_cache_insert, or encoded by the long pass
+      if (lcnt) {
+        lm = lcnt[chunk * kThreads + tid];
+        ls = s;
+        s_list[nw * kThreads + tid] = kLongEntry;
+        ++nw;
+        cnt += lm;
+      }
+      return;
+    }
     const u64 h = word_hash(tv, s, (uint32_t)L);
     u64 pay = 0, i = (h >> 17) & cmask;
     for (int p = 0; p < kCacheProbes; ++p, i = (i + 1) & cmask) {
@@ -427,6 +443,11 @@ __global__ __launch_bounds__(kThreads) void k_cache_words(const uint8_t* __restr
   int32_t* dst = out + s_prefix + (s_inc[tid] - cnt);
   for (uint32_t w = 0; w < nw; ++w) {
     const uint32_t e = s_list[w * kThreads + tid];
+    if (e == kLongEntry) {
+      for (uint32_t k = 0; k < lm; ++k) dst[k] = lids[ls + k];
+      dst += lm;
+      continue;
+    }
     if (e & 0x80000000u) {  // inline ids: the slot line the lookup just read
       const u64* sl = slot + kSlotU64 * (u64)(e & 0x7FFFFFFFu);
       const uint32_t m = (uint32_t)(sl[1] >> 48);
@@ -593,11 +614,18 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
   const bool debug = std::getenv("SHREDWORD_ENCODE_DEBUG") != nullptr;
   u64 *const misc = c.misc.get(), *const cslot = c.cslot.get(), *const bcnt = c.bcnt.get();
   int32_t *const pad = c.pad.get(), *const rank = c.rank.get();
+  // long-word mode: the words above kEncMaxWord are encoded first, ids at pad + their offset, id
+  // counts per span in lcnt; the word passes below then place them like any other word's ids
+  const uint32_t* lcnt = nullptr;
+  if (long_words_) {
+    const int r = long_pass(text, n, c.table.get(), c.byte_map.get(), pad, c.cap_bytes, st, &lcnt);
+    if (r < 0) return r;
+  }
   for (;;) {
     ENC_OK(hipMemsetAsync(misc, 0, 32, st));
     if (cached) {
       ENC_OK(hipMemsetAsync(cslot, 0, cc * kSlotU64 * 8, st));
-      k_cache_insert<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, misc);
+      k_cache_insert<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, misc, long_words_);
       ENC_OK(hipGetLastError());
       auto enck = packed_ ? k_cache_encode<true> : k_cache_encode<false>;
       // arena offsets must stay below 2^31: bit 31 of a payload tags "ids inline in the slot", so
@@ -609,13 +637,13 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
       // look-back states and the ticket (bcnt[2 nb, 3 nb], zero = "not published")
       ENC_OK(hipMemsetAsync(bcnt + 2 * nb, 0, (nb + 1) * 8, st));
       k_cache_words<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, rank, out, (u64)cap, bcnt,
-                                                                   bcnt + 2 * nb, nb, misc);
+                                                                   bcnt + 2 * nb, nb, misc, pad, lcnt);
     } else {
       const bool aligned = (reinterpret_cast<uintptr_t>(text) & 15) == 0;
       auto kern = aligned ? (packed_ ? k_encode_words<true, true> : k_encode_words<true, false>)
                           : (packed_ ? k_encode_words<false, true> : k_encode_words<false, false>);
       kern<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, c.byte_map.get(), c.table.get(), mask_, pad, rank,
-                                                          c.tcnt.get(), bcnt, misc);
+                                                          c.tcnt.get(), bcnt, misc, lcnt);
     }
     ENC_OK(hipGetLastError());
     // inclusive block sums into bcnt[nb, 2 nb); the last one is the total
@@ -670,8 +698,12 @@ int64_t EncodeDevice::encode_host(const uint8_t* text, size_t n, int32_t* out, s
   hipStream_t st = (hipStream_t)stream_;
   size_t pos = 0, done = 0;
   while (pos < n) {
-    const size_t len = host_piece_len(text, n, pos, piece);
+    const size_t len = host_piece_len(text, n, pos, piece, max_word());
     if (len == 0) return -3;
+    if (len > piece && !hs.reserve(len)) {  // a long word that the budget cut is staged whole
+      std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu bytes)\n", len);
+      return -1;
+    }
     ENC_OK(hipMemcpyAsync(hs.text.get(), text + pos, len, hipMemcpyHostToDevice, st));
     const int64_t r = encode(hs.text.get(), len, hs.out.get(), cap - done, nullptr, nullptr);
     if (r < 0) return r;

@@ -269,7 +269,7 @@ int64_t EncodeDevice::encode_docs_host(const uint8_t* text, size_t n, const int6
     for (size_t p = doc_begin(d), e = doc_begin(d + 1); p < e; ++p) {
       run = host_is_delim(text[p]) ? 0 : run + 1;
       non_delim += run != 0;
-      if (run > (size_t)kEncMaxWord) return -3;
+      if (run > max_word()) return -3;
     }
   }
   DeviceGuard guard;

@@ -346,13 +346,21 @@ int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* 
     return -1;
   }
   SpanState& sp = pass_state<SpanState>(pass_[kSpans]);
-  uint8_t* const dtext = hs.text.get();
-  int32_t* const dout = hs.out.get();
+  uint8_t* dtext = hs.text.get();
+  int32_t* dout = hs.out.get();
   hipStream_t st = (hipStream_t)stream_;
   size_t pos = 0, done = 0, lines_done = 0;
   while (pos < n) {
-    const size_t len = host_piece_len(text, n, pos, piece);
+    const size_t len = host_piece_len(text, n, pos, piece, max_word());
     if (len == 0) return -3;
+    if (len > hs.text.cap()) {  // a long word that the budget cut is staged whole
+      if (!hs.reserve(len)) {
+        std::fprintf(stderr, "[ERROR]\t encoder: staging allocation failed (%zu bytes)\n", len);
+        return -1;
+      }
+      dtext = hs.text.get();
+      dout = hs.out.get();
+    }
     ENC_OK(hipMemcpyAsync(dtext, text + pos, len, hipMemcpyHostToDevice, st));
     const int64_t r = specials ? encode_special(dtext, len, dout, cap - done, lens, nullptr, nullptr, nullptr)
                                : encode(dtext, len, dout, cap - done, nullptr, nullptr);

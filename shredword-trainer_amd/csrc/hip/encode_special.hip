@@ -12,7 +12,7 @@
 //                   first-byte set in LDS rejects almost every position; on a hit the specials
 //                   with that first byte are compared longest first against the table in LDS (one
 //                   word per special + their bytes: <= 17.5 KB, loaded per workgroup from L2).
-//                   Counts the span's matches; flags a run past kEncMaxWord.
+//                   Counts the span's matches; flags a run past the word limit in force.
 //   hipCUB scan     inclusive sum of the per-span counts (runs and their matches are ordered by
 //                   position, so the sum is each span's place in the match list).  No match:
 //                   the call continues as the plain encode.
@@ -87,14 +87,14 @@ __device__ __forceinline__ uint32_t match_at(const T& text, u64 p, u64 room, con
 }
 
 // kWrite false: cnt[span] = the matches of the runs starting in the span; *flag |= 1 for a run
-// past kEncMaxWord.  kWrite true: the same walk writes its matches from inc[span] - cnt[span] on
+// past maxw (kEncMaxWord, or the long-word limit).  kWrite true: the same walk writes its matches from inc[span] - cnt[span] on
 // (M entries in all) and blanks them in `masked` (a copy of the text).
 template <bool kWrite>
 __global__ __launch_bounds__(kThreads) void k_special_scan(const uint8_t* __restrict__ text, u64 n, SpecialTab tab,
                                                            uint32_t* __restrict__ cnt, const u64* __restrict__ inc,
                                                            u64* __restrict__ m_pos, uint32_t* __restrict__ m_idx,
                                                            u64 M, uint8_t* __restrict__ masked,
-                                                           u64* __restrict__ flag) {
+                                                           u64* __restrict__ flag, u64 maxw) {
   __shared__ uint32_t s_text[kStageBytes / 4];
   extern __shared__ uint32_t s_tab[];
   for (uint32_t i = threadIdx.x; i < tab.words; i += kThreads) s_tab[i] = tab.w[i];
@@ -104,8 +104,8 @@ __global__ __launch_bounds__(kThreads) void k_special_scan(const uint8_t* __rest
   u64 at = 0;
   if (kWrite) at = inc[span] - cnt[span];
   uint32_t c = 0;
-  for_each_word(tv, n, base, [&](u64 s, u64 L, int) {
-    if (L > (u64)kEncMaxWord) {
+  auto run = [&](u64 s, u64 L, int) {
+    if (L > maxw) {
       if (!kWrite) atomicOr(reinterpret_cast<unsigned long long*>(flag), 1ull);
       return;
     }
@@ -125,7 +125,9 @@ __global__ __launch_bounds__(kThreads) void k_special_scan(const uint8_t* __rest
       ++c;
       p += len;
     }
-  });
+  };
+  if (maxw > (u64)kEncMaxWord) for_each_word(tv, n, base, run, text, maxw);
+  else for_each_word(tv, n, base, run);
   if (!kWrite) cnt[span] = c;
 }
 
@@ -187,7 +189,7 @@ struct SpecialState : PassState {
   DeviceBuf<int64_t> wstarts;       // byte offsets of the word ids
   DeviceBuf<u64> mpos;              // match positions, ascending
   DeviceBuf<uint32_t> midx;         // their specials
-  DeviceWords flag;                 // a run past kEncMaxWord
+  DeviceWords flag;                 // a run past the word limit
   PinnedWords host;                 // match total, the flag
   EventSet<4> ev;
 
@@ -277,7 +279,7 @@ int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out
   ENC_OK(hipEventRecord(ev[0], st));
   ENC_OK(hipMemsetAsync(sx.flag.get(), 0, 8, st));
   k_special_scan<false><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, cnt, nullptr, nullptr, nullptr,
-                                                                         0, nullptr, sx.flag.get());
+                                                                         0, nullptr, sx.flag.get(), (u64)max_word());
   ENC_OK(hipGetLastError());
   size_t tmp = sx.tmp.cap();
   ENC_OK(hipcub::DeviceScan::InclusiveSum(sx.tmp.get(), tmp, CountIter(cnt, Widen()), inc, spans, st));
@@ -297,7 +299,8 @@ int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out
   int32_t* const wids = sx.wids.get();
   ENC_OK(hipMemcpyAsync(masked, text, n, hipMemcpyDeviceToDevice, st));
   k_special_scan<true><<<dim3((unsigned)nb), dim3(kThreads), lds, st>>>(text, n, tab, cnt, inc, sx.mpos.get(),
-                                                                        sx.midx.get(), (u64)M, masked, sx.flag.get());
+                                                                        sx.midx.get(), (u64)M, masked, sx.flag.get(),
+                                                                        (u64)max_word());
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[1], st));
   const int64_t Tw = encode(masked, n, wids, sx.wids.cap(), stream, enc_ms);

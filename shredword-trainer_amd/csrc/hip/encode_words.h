@@ -1,7 +1,8 @@
 // The word walk of the encoder kernels (encode_device.hip) and of the special-token scan
 // (encode_special.hip): one workgroup per 4096-byte chunk, one thread per 32-byte span, a word
 // belongs to the span it starts in; the span passes (encode_spans.hip) share the geometry and the
-// block scan.  Device code; included by those three .hip files only.
+// block scan; the long-word pass (encode_long.hip) shares the walk and the rank lookup.  Device code;
+// included by those .hip files only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,9 +70,47 @@ __device__ __forceinline__ TextView stage_chunk(const uint8_t* __restrict__ text
   return TextView{text, reinterpret_cast<const uint8_t*>(lds), lo, lo + 4 * words};
 }
 
-// Calls f(s, L, j) for every word starting in the span at `base` (L may exceed kEncMaxWord).
+// Rank of the pair (a, b) in the merge-rank table (host/encoder.h), kInf for none.
+constexpr int kInf = 0x7fffffff;
+__device__ __forceinline__ int pair_rank(const uint64_t* __restrict__ tab, uint64_t mask, int a, int b) {
+  if ((uint32_t)a >= (uint32_t)kEncIdLimit || (uint32_t)b >= (uint32_t)kEncIdLimit) return kInf;
+  const uint64_t key = (uint64_t)(uint32_t)a << 20 | (uint64_t)(uint32_t)b;
+  for (uint64_t i = ((key * 0x9E3779B97F4A7C15ull) >> 24) & mask;; i = (i + 1) & mask) {
+    const uint64_t e = tab[i];
+    if (e == kEncEmpty) return kInf;
+    if ((e >> 20) == key) return (int)(e & 0xFFFFFu);
+  }
+}
+
+// 0x80 in every byte of w that equals c.
+__device__ __forceinline__ uint64_t bytes_equal(uint64_t w, uint64_t c) {
+  const uint64_t x = w ^ (c * 0x0101010101010101ull);
+  return ~(((x & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | x | 0x7F7F7F7F7F7F7F7Full);
+}
+
+// The first delimiter of text[e .. stop), or stop (<= n): the tail of a word longer than the byte
+// walk below follows, read 8 bytes at a time once the address is aligned.
+__device__ __forceinline__ uint64_t long_word_end(const uint8_t* __restrict__ text, uint64_t e, uint64_t stop) {
+  while (e < stop && (reinterpret_cast<uintptr_t>(text + e) & 7)) {
+    if (is_delim(text[e])) return e;
+    ++e;
+  }
+  while (e + 8 <= stop) {
+    const uint64_t w = *reinterpret_cast<const uint64_t*>(text + e);
+    if (bytes_equal(w, 9) | bytes_equal(w, 10) | bytes_equal(w, 13) | bytes_equal(w, 32)) break;
+    e += 8;
+  }
+  while (e < stop && !is_delim(text[e])) ++e;
+  return e;
+}
+
+// Calls f(s, L, j) for every word starting in the span at `base` (L may exceed kEncMaxWord: it is
+// then kEncMaxWord + 1, or with the text's global pointer g and a limit maxw above kEncMaxWord the
+// word's length up to maxw + 1).
 template <typename T, typename F>
-__device__ __forceinline__ void for_each_word(const T& text, uint64_t n, uint64_t base, F f) {
+__device__ __forceinline__ void for_each_word(const T& text, uint64_t n, uint64_t base, F f,
+                                              const uint8_t* __restrict__ g = nullptr,
+                                              uint64_t maxw = (uint64_t)kEncMaxWord) {
   if (base >= n) return;
   const uint64_t lim = n - base < (uint64_t)kSpan ? n - base : (uint64_t)kSpan;
   uint32_t dm = 0;
@@ -89,6 +128,7 @@ __device__ __forceinline__ void for_each_word(const T& text, uint64_t n, uint64_
     } else {
       uint64_t e = base + kSpan;
       while (e < n && e - s <= (uint64_t)kEncMaxWord && !is_delim(text[e])) ++e;
+      if (g && e - s > (uint64_t)kEncMaxWord) e = long_word_end(g, e, n - s > maxw + 1 ? s + maxw + 1 : n);
       L = e - s;
     }
     f(s, L, j);

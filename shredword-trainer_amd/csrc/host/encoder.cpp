@@ -213,6 +213,20 @@ int shred_encoder_info(const ShredEncoder* enc, size_t* num_merges, int32_t* byt
   return 0;
 }
 
+int shred_encoder_set_long_words(ShredEncoder* enc, int on) {
+  if (!enc) return -1;
+  enc->dev->set_long_words(on != 0);
+  return 0;
+}
+
+int shred_encoder_long_words(const ShredEncoder* enc) { return enc && enc->dev->long_words() ? 1 : 0; }
+
+int shred_encoder_long_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* words, uint64_t* rounds) {
+  if (!enc) return -1;
+  enc->dev->long_stats(scratch_bytes, words, rounds);
+  return 0;
+}
+
 int64_t shred_encode(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap) {
   if (!enc || (n && (!text || !out))) return -1;
   return enc->dev->encode_host(text, n, out, cap);

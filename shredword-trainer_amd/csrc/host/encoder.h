@@ -17,6 +17,7 @@ namespace shred {
 constexpr uint64_t kEncEmpty = ~0ull;
 constexpr int32_t kEncIdLimit = 1 << 20;
 constexpr int kEncMaxWord = 1024;  // SHRED_ENCODE_MAX_WORD
+constexpr uint32_t kEncMaxLongWord = 1u << 20;  // SHRED_ENCODE_MAX_LONG_WORD
 
 inline uint64_t enc_key(int32_t a, int32_t b) { return (uint64_t)(uint32_t)a << 20 | (uint64_t)(uint32_t)b; }
 inline uint64_t enc_slot(uint64_t key) { return (key * 0x9E3779B97F4A7C15ull) >> 24; }
@@ -52,7 +53,7 @@ class EncodeDevice {
                               std::string* why);
   ~EncodeDevice();
   // text / out on the device; stream = hipStream_t or nullptr.  Returns ids, -1 device error,
-  // -2 cap too small, -3 word longer than kEncMaxWord.
+  // -2 cap too small, -3 word longer than max_word().
   int64_t encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms);
   // Host buffers: staged through cached device buffers in pieces of <= kHostPiece bytes cut at
   // delimiters (device memory ~14 B per piece byte, whatever n is).
@@ -60,6 +61,15 @@ class EncodeDevice {
   int64_t encode_host(const uint8_t* text, size_t n, int32_t* out, size_t cap);
   // Calls that fell back from the word cache to the direct path (overflow or hash collision).
   uint64_t fallbacks() const { return fallbacks_; }
+
+  // ---- words above kEncMaxWord (encode_long.hip; shred_encoder_set_long_words) ----
+  // on: every encode call takes words of up to kEncMaxLongWord bytes; -3 then means a longer one.
+  void set_long_words(bool on) { long_words_ = on; }
+  bool long_words() const { return long_words_; }
+  size_t max_word() const { return long_words_ ? (size_t)kEncMaxLongWord : (size_t)kEncMaxWord; }
+  // What the long pass holds and has done: bytes of device scratch allocated for long words (0
+  // until a call meets one), long words encoded, rounds run.
+  void long_stats(uint64_t* scratch_bytes, uint64_t* words, uint64_t* rounds) const;
 
   // encode() plus the span passes (encode_spans.hip): starts (nullptr or cap int64) and line_off
   // (nullptr or line_cap int64) on the device, as include/shredword_encode.h defines them.
@@ -160,11 +170,18 @@ class EncodeDevice {
   int span_passes(const uint8_t* text, size_t n, const int32_t* ids, size_t T, int64_t* starts, int64_t* line,
                   size_t line_cap, uint64_t start_base, uint64_t id_base, bool whole,
                   const std::vector<int32_t>& lens, void* stream, size_t* newlines, uint8_t* last_byte, double* ms);
+  // The long pass of encode(): finds the words of text above kEncMaxWord bytes and encodes each with
+  // one workgroup, its ids to pad + the word's offset (pad: pad_cap >= n int32), its id count to
+  // (*cnt)[offset / 32] (device memory of the pass; nullptr entries' worth when there is no long
+  // word).  Returns 0, -1 on a device error, -3 for a word above kEncMaxLongWord.
+  int long_pass(const uint8_t* text, size_t n, const uint64_t* table, const int32_t* byte_map, int32_t* pad,
+                size_t pad_cap, void* stream, const uint32_t** cnt);
   int device_ = 0;
   void* stream_ = nullptr;  // hipStream_t
   uint64_t mask_ = 0;       // of the merge-rank table
   bool packed_ = false;     // 16-bit LDS strips (ids < 0xFFFF)
   uint64_t fallbacks_ = 0;
+  bool long_words_ = false;  // words above kEncMaxWord go to the long pass
   // The registered special tokens (set_specials); the units build their device tables from them.
   std::vector<uint8_t> sx_bytes_;  // the specials' bytes, in id order
   std::vector<uint32_t> sx_off_;   // K + 1 offsets into sx_bytes_
@@ -172,7 +189,7 @@ class EncodeDevice {
   bool sx_dirty_ = false;          // the scan table on the device is older than the set
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
-  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kPasses };
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

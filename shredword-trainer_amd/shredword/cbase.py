@@ -154,6 +154,11 @@ lib.shred_encode_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_siz
 lib.shred_encode_device.restype = c_int64
 lib.shred_decode.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t]
 lib.shred_decode.restype = c_int64
+# words above SHRED_ENCODE_MAX_WORD
+lib.shred_encoder_set_long_words.argtypes, lib.shred_encoder_set_long_words.restype = [Encoder, c_int], c_int
+lib.shred_encoder_long_words.argtypes, lib.shred_encoder_long_words.restype = [Encoder], c_int
+lib.shred_encoder_long_stats.argtypes = [Encoder, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
+lib.shred_encoder_long_stats.restype = c_int
 # token byte offsets and per-line id offsets
 lib.shred_encoder_token_lengths.argtypes = [Encoder, POINTER(c_int32), c_size_t]
 lib.shred_encoder_token_lengths.restype = c_int

@@ -17,6 +17,7 @@ import numpy as np
 from .cbase import lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
+MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
 MAX_UNK = 8      # SHRED_DECODE_MAX_UNK
 MAX_SPECIALS = 256     # SHRED_SPECIAL_MAX
 MAX_SPECIAL_LEN = 64   # SHRED_SPECIAL_MAX_LEN
@@ -52,8 +53,9 @@ def join_docs(texts):
 
 class BPEEncoder:
     def __init__(self, model_path: str, vocab_path: str = None, unk_id: int = 0, device: int = 0,
-                 special_tokens=None):
-        """special_tokens: None or a list of bytes / str, see set_special_tokens."""
+                 special_tokens=None, *, long_words: bool = False):
+        """special_tokens: None or a list of bytes / str, see set_special_tokens.  long_words: see the
+        property of that name."""
         self.enc = lib.shred_encoder_load(model_path.encode("utf-8"),
                                           vocab_path.encode("utf-8") if vocab_path else None,
                                           int(unk_id), int(device))
@@ -62,11 +64,12 @@ class BPEEncoder:
             raise RuntimeError(f"Failed to create the encoder for {model_path} (see stderr; a GPU is required)")
         _LIVE.add(self)
         self._specials = []
+        self.long_words = long_words
         if special_tokens:
             self.set_special_tokens(special_tokens)
 
     @classmethod
-    def from_merges(cls, merges, byte_map=None, device: int = 0, special_tokens=None):
+    def from_merges(cls, merges, byte_map=None, device: int = 0, special_tokens=None, *, long_words: bool = False):
         """merges: (M, 3) int32 array of (first, second, 256 + m) as in a .model file."""
         m = np.ascontiguousarray(np.asarray(merges, dtype=np.int32).reshape(-1, 3))
         bm = None if byte_map is None else np.ascontiguousarray(np.asarray(byte_map, dtype=np.int32))
@@ -81,9 +84,30 @@ class BPEEncoder:
             raise RuntimeError("Failed to create the encoder (invalid merges or no GPU; see stderr)")
         _LIVE.add(self)
         self._specials = []
+        self.long_words = long_words
         if special_tokens:
             self.set_special_tokens(special_tokens)
         return self
+
+    @property
+    def long_words(self) -> bool:
+        """False (the default): a word longer than MAX_WORD bytes fails the call with ValueError.  True:
+        every encode call takes words of up to MAX_LONG_WORD bytes; one workgroup encodes each word above
+        MAX_WORD, to the ids the merge list defines for it.  A call then reads the text once more to find
+        such words."""
+        return bool(lib.shred_encoder_long_words(self.enc))
+
+    @long_words.setter
+    def long_words(self, on: bool):
+        lib.shred_encoder_set_long_words(self.enc, int(bool(on)))
+
+    @property
+    def long_word_stats(self) -> dict:
+        """The long-word pass so far: scratch_bytes it has allocated on the device (0 until a call meets a
+        long word), the long words it has encoded, the rounds it has run."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        lib.shred_encoder_long_stats(self.enc, *(ctypes.byref(x) for x in v))
+        return dict(zip(("scratch_bytes", "words", "rounds"), (x.value for x in v)))
 
     def set_special_tokens(self, tokens):
         """Replaces the encoder's special tokens (an empty list clears them).  tokens: bytes / str, at most
@@ -126,10 +150,9 @@ class BPEEncoder:
             raise RuntimeError("token_lengths failed")
         return out
 
-    @staticmethod
-    def _check(r: int) -> int:
+    def _check(self, r: int) -> int:
         if r == -3:
-            raise ValueError(f"a word is longer than {MAX_WORD} bytes")
+            raise ValueError(f"a word is longer than {MAX_LONG_WORD if self.long_words else MAX_WORD} bytes")
         if r == -4:
             raise ValueError("the byte map holds an id >= 256: token lengths are undefined")
         if r < 0:
@@ -230,11 +253,10 @@ class BPEEncoder:
 
     # ---- batches of documents: rows cut at given byte offsets (include/shredword_encode.h) --------
 
-    @classmethod
-    def _check_docs(cls, r: int) -> int:
+    def _check_docs(self, r: int) -> int:
         if r == -6:
             raise ValueError("doc_offsets must be 0 = doc_offsets[0] <= ... <= doc_offsets[docs] = len(text)")
-        return cls._check(r)
+        return self._check(r)
 
     def encode_docs(self, text, doc_offsets=None, *, starts: bool = False, specials: bool = False):
         """-> (ids, row_offsets) or (ids, row_offsets, starts).  text holds the documents concatenated with

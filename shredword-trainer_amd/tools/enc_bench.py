@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs | long]   (SHREDWORD_LIB picks the build)
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
 GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
@@ -19,7 +19,11 @@ after every '\\n') and goes through encode_docs_device with starts, then, after 
 encode_spans_device(lines=True) on the same text, each also as a whole call between device events, and a
 device-to-device copy of the text's bytes is timed beside the copy kernel of the document passes, whose
 time the library prints under SHREDWORD_ENCODE_DEBUG (set here for the last calls: the corpus one document
-per line, as one document and as 16 documents), and beside a copy of 1 GiB, which the cache does not hold."""
+per line, as one document and as 16 documents), and beside a copy of 1 GiB, which the cache does not hold; with
+a trailing `long`, the long-word mode (long_words=True): encode_device on the corpus as it is (no long word: the
+cost of the find pass, against the first line's time with the mode off), on the corpus with the delimiters of a
+4 KB stretch taken out after every 64 KB (one long word per 64 KB), and on single words of 4 KB, 64 KB and 1 MB
+cut from the corpus without its delimiters, with the rounds each word took."""
 import os
 import subprocess
 import sys
@@ -47,7 +51,8 @@ else:
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
-    if spans or decode or special or docs or window:
+    long_leg = args[-1] == "long"
+    if spans or decode or special or docs or window or long_leg:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -85,6 +90,41 @@ else:
         print("special: bytes", text.numel(), "matches", found, "plain encode_ms", med(plain, 0), "spans_ms",
               med(plain, 1), "| specials=True encode_ms", med(runs, 0), "spans_ms", med(runs, 1), "special_ms",
               med(runs, 2), "min", min(t[2] for t in runs), "max", max(t[2] for t in runs), flush=True)
+    if long_leg:
+        reps = max(reps, 5)
+        stats = lambda v: (sorted(v)[len(v) // 2], min(v), max(v))
+        off_ms = stats([enc.encode_device(text, out)[1] for _ in range(reps)])
+        enc.long_words = True
+        assert torch.equal(enc.encode_device(text, out)[0], ids)
+        on_ms = stats([enc.encode_device(text, out)[1] for _ in range(reps)])
+        print("long: no long word, bytes", text.numel(), "| mode off ms", off_ms[0], "min", off_ms[1], "max", off_ms[2],
+              "| mode on ms", on_ms[0], "min", on_ms[1], "max", on_ms[2], "ratio", on_ms[0] / off_ms[0],
+              "scratch", enc.long_word_stats["scratch_bytes"], flush=True)
+        host = text.cpu().numpy()
+        glued = host.copy()
+        delim = np.isin(host, np.frombuffer(b"\t\r\n ", dtype=np.uint8))
+        for at in range(65536, host.size - 4096, 65536):
+            glued[at:at + 4096][delim[at:at + 4096]] = ord("x")
+        gt = torch.from_numpy(glued).cuda()
+        before = enc.long_word_stats
+        enc.encode_device(gt, out)
+        words = enc.long_word_stats["words"] - before["words"]
+        ms = stats([enc.encode_device(gt, out)[1] for _ in range(reps)])
+        print("long: one 4 KB word per 64 KB, long words", words, "ms", ms[0], "min", ms[1], "max", ms[2], "GB/s",
+              gt.numel() / ms[0] / 1e6, "scratch", enc.long_word_stats["scratch_bytes"], flush=True)
+        solid = host[~delim]
+        for size in (4096, 65536, 1 << 20):
+            if solid.size < size:
+                break
+            w = torch.from_numpy(solid[:size].copy()).cuda()
+            o = torch.empty(size, dtype=torch.int32, device="cuda")
+            before = enc.long_word_stats["rounds"]
+            got = enc.encode_device(w, o)[0].numel()
+            rounds = enc.long_word_stats["rounds"] - before
+            ms = stats([enc.encode_device(w, o)[1] for _ in range(3 if size > 65536 else reps)])
+            print("long: one word of", size, "bytes: ids", got, "rounds", rounds, "of", enc.num_merges, "merges | ms", ms[0],
+                  "min", ms[1], "max", ms[2], "MB/s", size / ms[0] / 1e3, flush=True)
+        enc.long_words = False
     if docs:
         del out
         reps = max(reps, 5)
