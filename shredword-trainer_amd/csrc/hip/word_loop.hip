@@ -1,4 +1,7 @@
-// MI355X (gfx950) kernels of the indexed merge loop (host/word_loop.h) and its host driver.
+// MI355X (gfx950) kernel of the indexed merge loop (host/word_loop.h) and the host protocol that
+// drives it: the command ring, the record slots and the checksummed small-merge hand-off.  The word
+// table and its index are word_index.hip, tiebreak=device outside the kernel is word_select.hip;
+// word_loop_dev.h holds what the three units share.
 //
 //   k_word_loop       the merge loop: one persistent workgroup (16 wave64s) that takes merge /
 //                     undo commands from a ring in pinned host memory.  Per merge (a, b) -> X:
@@ -10,49 +13,24 @@
 //                     (FreqChangeMap, bpe.cpp:9-50), compacts the word in place and appends it to
 //                     the words of X when it changed; the records go to host memory behind one
 //                     system release and a flag.
-//   k_wl_emit_pairs   initial index: every adjacent non-unk pair of every word -> (key, word)
-//   k_wl_mark / k_wl_scatter / k_wl_counts / k_wl_dir_init   sorted runs -> pool + directory
-//   k_words_to_tiles  the word table back into the tile stream (headers + tokens)
 //
 // Integer and index work only: no MFMA.  Everything the loop touches per merge is a few KB of
 // the word table and the index, so the bound is the chain of dependent memory round trips, not
 // bandwidth.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <thread>
 #include <vector>
 
-#include "../host/common.h"
-#include "../host/word_loop.h"
-#include "hip_common.h"
+#include "word_loop_dev.h"
 
 namespace shred {
 
 namespace {
 
-constexpr int kWlThreads = 512;
 constexpr int kDh = 2048;               // LDS delta hash slots
-constexpr int kStripV = 7;              // 16-B loads per word run: [length][weight lo, hi][25 tokens]
-constexpr int kStrip = 4 * kStripV;     // ints per lane in the LDS strip
-// A run's header: its live length, then the word's weight (u64, the count of the word) inline, so
-// that the run's loads bring it and a scanned word costs no separate weight line (round 6: a third
-// of the loop's HBM read requests were those lines)
-constexpr uint32_t kRunHdr = 3;
-constexpr uint32_t kStripTok = kStrip - kRunHdr;
-// Runs are 16-B aligned with a capacity of whole 16-B groups.  (Round 6 measured 128-B aligned
-// runs: one L2 line per run load, HBM reads of the loop -30%, but the table grew 2.5x, past what
-// the MALL keeps, and the loop got slower; the groups a word needs ride in its pool entries
-// instead, see WEnt.)
-constexpr uint32_t kRunAlign = 4;  // ints
-__host__ __device__ constexpr uint32_t run_cap(uint32_t len) {
-  return (kRunHdr + len + kRunAlign - 1u) & ~(kRunAlign - 1u);
-}
 constexpr int kB = 8;                   // pool entries per lane per scan round (one load batch)
 #ifdef SHRED_WL_NO_PREFETCH
 constexpr bool kWlPrefetch = false;     // (A/B builds) each word's run loaded in its own iteration
@@ -99,41 +77,8 @@ constexpr uint32_t kDeltaBucketsDev = 1024;  // the reference's FREQ_CHANGE_BUCK
 constexpr uint32_t kRing = 64;          // command ring entries
 constexpr uint32_t kOpMerge = 1, kOpStop = 2, kOpTimeout = 3, kOpUnmerge = 4;
 constexpr uint32_t kNoList = 0xFFFFFFFFu;
-// dstate words: [1] pool top, [3] error
-constexpr int kStPoolTop = 1, kStError = 3;
-// error codes (dstate[kStError], reported by the host)
-constexpr uint32_t kErrPool = 1, kErrList = 2, kErrLookup = 4;
-
-struct WlCmd {
-  // granules (seq | value << 32): op | slot << 8, a, b, X, then the words-of list of max(a, b)
-  // when the host knows it (offset, count + 1; 0: look it up), one 64-B line
-  u64 g[8];
-};
 constexpr int kCmdGranules = 6;
 
-struct WlSlotDev {
-  DeltaRecord* recs;  // host-visible
-  uint32_t* hdr;      // host-visible: [0] records, [1] flag, [2] listed words, [3] changed words,
-                      //   [4..5] occurrences (u64), [6..7] device ticks command -> flag (u64),
-                      //   [8..9] ticks command -> list known, [10..11] ticks command -> words merged,
-                      //   [12] words whose runs were read, [13] 1: a filtered words-of list,
-                      //   [14] run ints read (length + tokens), [15] run ints written back,
-                      //   [16..18] stamps (10 ns ticks after the command, thread 0): pool entries
-                      //   loaded, first run loaded, first word merged
-  uint32_t rec_cap;
-};
-
-// A pool entry: the word and a 64-bit filter.  In the words-of list of id M (the words merge M
-// changed) the filter holds a bit per (neighbour, side) of M in the word right after merge M:
-// nbit(p, 0) for each left neighbour p (X when just produced), nbit(n, 1) for each original
-// token n after the pair.  A merge never makes two older ids adjacent, so every adjacency
-// (c, M) / (M, d) the word holds later it held right after merge M: a word holding the pair
-// now has its bit.  Initial-index entries (exact lists) hold all ones.
-struct WEnt {
-  u64 e;    // run offset << 32 | groups << 28 | word id (groups: the 16-B groups of the word's run
-            // capacity, at most kStripV: a word's run load issues only those, round 6)
-  u64 sig;
-};
 // The small-merge path hands its records over without ordering them before the flag (round 6):
 // the records, the header and two tagged checksum granules go out back to back behind one release
 // fence, and the host accepts them once both granules carry the command's tag and the checksum of
@@ -142,49 +87,7 @@ struct WEnt {
 // or a stale block do not cancel out.
 __host__ __device__ __forceinline__ u64 hand_weight(uint32_t i) { return 0x9E3779B97F4A7C15ull + 2ull * i; }
 constexpr int kCksWord = 30;  // header u64 words 30, 31: seq << 32 | checksum low / high half
-constexpr int kGroupShift = 28;
-constexpr u64 kWordMask = (1ull << kGroupShift) - 1;
-__host__ __device__ __forceinline__ uint32_t ent_groups(u64 e) { return (uint32_t)(e >> kGroupShift) & 0xFu; }
 
-// tiebreak=device (K5 as the selector, WordLoop::run_select): the loop picks its own merges from
-// a pair table on the device.  Table: open addressing on the pair key, 16 B a slot -- the key,
-// then a word holding the count (low 48 bits) and the slot's frontier position + 1 (high 16
-// bits, 0: not in the frontier), so one atomicAdd on the word both counts and tells where the
-// LDS copy is (pairs holding unk are never in it).  Frontier: the slots of every pair ranked at or above a threshold
-// (count desc, key asc) plus stale ones; each merge takes the best live frontier entry, and pairs
-// a merge creates above the threshold join it (only new pairs ever gain: every other count only
-// falls).  An empty frontier sends the launch back to the host, which rebuilds it whole-chip.
-struct SelParams {
-  u64* tab;           // slot h: tab[2h] pair key (kEmpty64 = empty), tab[2h + 1] count | pos + 1 << 48
-  u64 pmask;
-  uint32_t* fr[2];    // frontier buffers (slots); st[kSelBuf] says which is current
-  uint32_t fcap;
-  uint32_t* st;       // see kSel* below
-  const u64* thr;     // threshold (count, key): every pair ranked at or above it is in the frontier
-  u64* out;           // per merge: key, count
-  u64* log;           // the launch's pair-count changes (key, signed delta), applied to the table between launches
-  u64 log_cap;        //   entries
-  int32_t X0;         // id of merge 0 of this training
-  uint32_t n_max;     // merges wanted
-  u64 min_freq;
-  uint32_t fill_max;  // inserts allowed before the table counts as full
-  uint32_t probe;     // diagnostic (SHREDWORD_SEL_PROBE): 1 skips the table's HBM updates (timing only: wrong counts)
-};
-// st words
-constexpr int kSelM = 0, kSelNF = 1, kSelBuf = 2, kSelStatus = 3, kSelIns = 4, kSelErr = 5, kSelStats = 6;
-constexpr int kSelWords = kSelStats + 2 * 12 + 2;  // st: 6 words, then 12 u64 statistics, then the log's length (u64)
-constexpr int kSelLogW = kSelStats + 2 * 12;
-// exit status: merges done (target reached / below min_pair_freq), frontier to rebuild, table full
-// (the in-kernel fill bound: one more merge's new pairs might not fit; the host grows the table)
-constexpr uint32_t kSelDone = 1, kSelRebuild = 2, kSelFull = 3;
-// The frontier lives in LDS for the whole launch: each entry's count follows the table's (the
-// merge's records add to both; inf[slot] = LDS position + 1), so a select is an LDS scan.  A
-// rebuild picks kSelK entries; merges append, and past kSelF - kSelSlack entries the dead ones
-// (below the threshold, or merged) are compacted away in LDS.  When more than kSelF - kSelRoom
-// stay live the launch ends for a rebuild (a compaction per merge would cost more).
-constexpr uint32_t kSelF = 1536, kSelK = 768, kSelRoom = 384, kSelSlack = 96;
-constexpr u64 kCntMask = (1ull << 48) - 1;  // the count in a slot's count word; pos + 1 above it
-constexpr int kPosShift = 48;
 template <bool kOn>
 struct SelLds {  // k_word_loop<false>: none
   u64 key[1], cnt[1];
@@ -199,43 +102,7 @@ struct SelLds<true> {
   u64 key[kSelF], cnt[kSelF];
   uint32_t idx[kSelIdx / 2], n;
 };
-struct WlParams {
-  int32_t* wtok;
-  const u64* weight;
-  WEnt* pool;
-  u64 pool_cap;
-  const u64* dkey;
-  const u64* dval;
-  u64 dir_mask;
-  u64* lst;          // per id: words-of list, pool offset | count << 32
-  uint32_t* lseq;    // per id: the command that made it (~0: none)
-  uint32_t id_cap;
-  u64* dsum;
-  u64* dft;
-  uint32_t* dlist;
-  uint32_t* dstate;
-  uint32_t cap;     // delta slots: ids in [0, cap) have slot id + 1, others (unk) slot 0
-  int32_t unk;
-  const WlCmd* ring;
-  uint32_t* status;  // host-visible: [0] exit op
-  uint32_t seq0;
-  uint32_t idle_polls;
-  uint32_t fin_max;  // K4 on the device: merges with at most this many records leave as ordered changes (0: off)
-  uint32_t fin_min;  //   and at least this many (> 0: the small-merge path stays on; its merges leave raw)
-  uint32_t prefetch;  // 1: the poller wave reads the next command while the records go out (exact mode)
-  // 1: the merge's barriers drain every wave's stores (0: only with spills or K4).  With 0 the
-  // word-run (wtok), pool and lst stores of a merge may still be in flight when its flag is raised;
-  // that is sound only because nothing reads them before the next command's __syncthreads, which
-  // drains them, and the host never reads them while the loop runs.  Any new reader of wtok, pool
-  // or lst inside a merge's records phase, or on the host after a flag, needs drain = 1 (K4 sets
-  // it: finalize reads the merged words).  tests/test_gpu_parity.py runs both modes.
-  uint32_t drain;
-  uint32_t fast;      // 1: merges listing <= kWlThreads words take the small-merge path (exact mode)
-  WlSlotDev sl[WordLoop::kSlots];
-  SelParams sel;  // k_word_loop<true> only
-};
 
-__device__ __forceinline__ u64 pair_key(int32_t a, int32_t b) { return ((u64)(uint32_t)a << 32) | (uint32_t)b; }
 __device__ __forceinline__ uint32_t sel_idx_home(u64 k) { return (uint32_t)(mix64(k) >> 40) & (kSelIdx - 1); }
 // position of key in the frontier, or -1 (also for a dead entry never compacted: those are found
 // and their counts kept, harmlessly)
@@ -270,36 +137,6 @@ __device__ __forceinline__ bool sel_idx_insert(SelLds<true>& F, u64 k, uint32_t 
 __device__ __forceinline__ u64 nbit(int32_t id, uint32_t s) {
   const uint32_t v = (uint32_t)id * 2u + s;
   return 1ull << ((v ^ (v >> 6) ^ (v >> 12) ^ (v >> 18)) & 63u);
-}
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 ld_agent64(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// tiebreak=device order: larger count first, then the smaller key
-__device__ __forceinline__ bool sel_better(u64 c, u64 k, u64 c2, u64 k2) { return c > c2 || (c == c2 && k < k2); }
-__device__ __forceinline__ bool sel_at_least(u64 c, u64 k, u64 tc, u64 tk) { return c > tc || (c == tc && k <= tk); }
-// The table slot of pair key pk, inserted when absent (~0 when the table is past its probe bound).
-// ins / err: counters of inserts and probe overflows (LDS in the loop, global in k_sel_insert).
-__device__ __forceinline__ u64 sel_slot(const SelParams& q, u64 pk, uint32_t* ins, uint32_t* err) {
-  u64 h = mix64(pk) & q.pmask;
-#pragma unroll 1
-  for (uint32_t probe = 0; probe < 4096u; ++probe) {
-    const u64 cur = ld_agent64(q.tab + 2 * h);
-    if (cur == pk) return h;
-    if (cur == kEmpty64) {
-      const u64 prev = atomicCAS(q.tab + 2 * h, kEmpty64, pk);
-      if (prev == kEmpty64) {
-        atomicAdd(ins, 1u);
-        return h;
-      }
-      if (prev == pk) return h;
-    }
-    h = (h + 1) & q.pmask;
-  }
-  atomicMax(err, 1u);
-  return ~0ull;
 }
 // One combined record of merge (a, b) -> X as a change of a pair's count (the reference's
 // FreqChangeMap entry, bpe.cpp:297-313, minus the pair merged and pairs holding unk).  The table
@@ -575,16 +412,6 @@ __device__ __forceinline__ uint32_t unmerge_run(int32_t* t, uint32_t L, int32_t 
 // The wave's max of a u64 (identity 0), as a scalar.
 __device__ __forceinline__ u64 wave_max64(u64 x) { return lane_read64(wave_scan_max64(x), 63); }
 
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t x) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
 // The loop's state in LDS.
 struct LoopS {
   alignas(16) uint32_t hs[32];  // the small-merge path's header, staged for 16-B stores (word 1 = 0: not the flag)
@@ -609,7 +436,6 @@ struct LoopS {
   u64 bc[kWlThreads / 64], bk[kWlThreads / 64];
   uint32_t bs[kWlThreads / 64];
 };
-
 
 // K4 on the device (reference FreqChangeMap, bpe.cpp:9-50, applied at :297-313):
 // the merge's n records (LDS hash + spilled keys) leave as the reference's changes, in the order
@@ -804,6 +630,9 @@ __device__ uint32_t finalize_changes(const WlParams& p, DeltaH& h, LoopS& S, u64
 // table's frontier (p.sel) and folds the merge's records back into the table.
 // kProbes: the LDS delta hash's probe bound (kProbesDefault; 0 and 1 force the HBM spill path).
 template <bool kSelf, int kProbes>
+#ifndef __HIP_DEVICE_COMPILE__
+__attribute__((visibility("hidden")))  // WlParams has a name now: the host stubs stay out of the library's exports
+#endif
 __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
   __shared__ int32_t s_strip[kStrip * kWlThreads];  // [position][lane]: conflict-free per wave
   __shared__ DeltaH s_h;
@@ -1721,262 +1550,6 @@ __global__ __launch_bounds__(kWlThreads) void k_word_loop(WlParams p) {
   }
 }
 
-namespace {
-
-// Initial index, compact (round 6: the sort no longer spans the runs' padding): word w's
-// adjacent pairs go to entries base[w] .. base[w] + L - 2 (base: exclusive sum of the words' pair
-// counts, k_wl_pair_counts); pairs holding unk emit EMPTY.
-__global__ void k_wl_pair_counts(const int32_t* wtok, const uint32_t* woff, uint32_t W, uint32_t* cnt) {
-  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w <= W; w += gridDim.x * blockDim.x) {
-    const uint32_t L = w < W ? (uint32_t)wtok[woff[w]] : 0u;
-    cnt[w] = L >= 2 ? L - 1 : 0u;
-  }
-}
-__global__ void k_wl_emit_pairs(const int32_t* wtok, const uint32_t* woff, const uint32_t* base, uint32_t W,
-                                int32_t unk, u64* key, uint32_t* val) {
-  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += gridDim.x * blockDim.x) {
-    const uint32_t o = woff[w], b = base[w], np = base[w + 1] - b;
-    const int32_t* t = wtok + o + kRunHdr;
-    for (uint32_t j = 0; j < np; ++j) {
-      const int32_t x = t[j], y = t[j + 1];
-      key[b + j] = (x != unk && y != unk) ? pair_key(x, y) : kEmpty64;
-      val[b + j] = w;
-    }
-  }
-}
-
-// Sorted (key, word) runs: keep the first of equal (key, word) entries; mark the first entry of
-// each key.  Word ids are ascending inside a key (stable sort of entries emitted in word order).
-__global__ void k_wl_mark(const u64* key, const uint32_t* val, uint64_t n, uint32_t* keep, uint32_t* head) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const u64 k = key[i];
-    const bool valid = k != kEmpty64;
-    const bool first_key = valid && (i == 0 || key[i - 1] != k);
-    keep[i] = valid && (first_key || val[i - 1] != val[i]);
-    head[i] = first_key;
-  }
-}
-
-__global__ void k_wl_scatter(const u64* key, const uint32_t* val, uint64_t n, const uint32_t* keep,
-                             const uint32_t* pos, const uint32_t* head, const uint32_t* kidx, const uint32_t* woff,
-                             WEnt* pool, u64* ikey, u64* ival) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    if (keep[i]) {
-      WEnt ent;
-      const uint32_t w = val[i], cap4 = (woff[w + 1] - woff[w]) >> 2;  // the run's 16-B groups
-      ent.e = ((u64)woff[w] << 32) | ((u64)min(cap4, (uint32_t)kStripV) << kGroupShift) | w;
-      ent.sig = ~0ull;  // an exact list: no filter
-      pool[pos[i]] = ent;
-    }
-    if (head[i]) {
-      ikey[kidx[i]] = key[i];
-      ival[kidx[i]] = pos[i];  // offset; the count is filled in by k_wl_counts
-    }
-  }
-}
-
-__global__ void k_wl_counts(u64* ival, uint64_t nk, uint64_t total) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < nk; i += (uint64_t)gridDim.x * blockDim.x) {
-    const u64 o = ival[i] & 0xFFFFFFFFull;
-    const u64 e = i + 1 < nk ? (ival[i + 1] & 0xFFFFFFFFull) : total;
-    ival[i] = o | ((e - o) << 32);
-  }
-}
-
-// The initial directory (after a memset of the keys to EMPTY): no key repeats.
-__global__ void k_wl_dir_init(const u64* ikey, const u64* ival, uint64_t nk, u64* dkey, u64* dval, u64 mask) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < nk; i += (uint64_t)gridDim.x * blockDim.x) {
-    const u64 key = ikey[i];
-    u64 h = mix64(key) & mask;
-    for (;;) {
-      const u64 prev = atomicCAS(&dkey[h], kEmpty64, key);
-      if (prev == kEmpty64) {
-        dval[h] = ival[i];
-        break;
-      }
-      h = (h + 1) & mask;
-    }
-  }
-}
-
-// Each run's header gets its word's weight (ints 1-2), after a host upload of the runs.
-__global__ void k_wl_set_weights(int32_t* wtok, const uint32_t* woff, uint32_t W, const u64* weight) {
-  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < W; w += gridDim.x * blockDim.x) {
-    const u64 c = weight[w];
-    wtok[woff[w] + 1] = (int32_t)(uint32_t)c;
-    wtok[woff[w] + 2] = (int32_t)(uint32_t)(c >> 32);
-  }
-}
-
-// Words -> tiles: a wave per tile writes [header][tokens] for its words in rank order and the
-// tile's live length; the old tail up to the previous length becomes padding.
-__global__ void k_words_to_tiles(const int32_t* wtok, const uint32_t* woff, const uint32_t* tile_first,
-                                 const uint32_t* tile_nw, uint32_t ntiles, int32_t* tok, const uint64_t* tile_off,
-                                 uint32_t* tile_len) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t waves = gridDim.x * (blockDim.x / 64);
-  for (uint32_t t = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); t < ntiles; t += waves) {
-    int32_t* dst = tok + tile_off[t];
-    const uint32_t f = tile_first[t], nw = tile_nw[t];
-    uint32_t base = 0;
-    for (uint32_t q = 0; q < nw; q += 64) {
-      const uint32_t w = f + q + (uint32_t)lane;
-      const bool on = q + (uint32_t)lane < nw;
-      const int32_t* s = on ? wtok + woff[w] : wtok;
-      const uint32_t len = on ? (uint32_t)s[0] : 0u;
-      const uint32_t need = on ? len + 1u : 0u;
-      const uint32_t incl = wave_incl_add(need);
-      if (on) {
-        int32_t* d = dst + base + incl - need;
-        d[0] = (int32_t)((uint32_t)kHeaderBase + w);
-        for (uint32_t j = 0; j < len; ++j) d[1 + j] = s[kRunHdr + j];
-      }
-      base += __shfl(incl, 63, 64);
-    }
-    const uint32_t old = tile_len[t];
-    for (uint32_t i = base + (uint32_t)lane; i < old; i += 64) dst[i] = INT32_MIN;
-    if (lane == 0) tile_len[t] = base;
-  }
-}
-
-// Tiles -> words (inverse of k_words_to_tiles): a thread per tile walks its entries; each word's
-// tokens go to its run after the live length.
-__global__ void k_tiles_to_words(const int32_t* tok, const uint64_t* tile_off, const uint32_t* tile_len,
-                                 uint32_t ntiles, const uint32_t* woff, int32_t* wtok) {
-  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < ntiles; t += gridDim.x * blockDim.x) {
-    const int32_t* src = tok + tile_off[t];
-    const uint32_t n = tile_len[t];
-    int32_t* run = nullptr;
-    uint32_t len = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const int32_t v = src[i];
-      if (v < kHeaderLimit) {
-        if (run) run[0] = (int32_t)len;
-        const uint32_t w = (uint32_t)(v - kHeaderBase);
-        run = wtok + woff[w];
-        len = 0;
-      } else if (run) {
-        run[kRunHdr + len++] = v;
-      }
-    }
-    if (run) run[0] = (int32_t)len;
-  }
-}
-
-// ---- tiebreak=device: the frontier's rebuild (whole chip) and the table's initial pairs
-constexpr uint32_t kSelBuckets = 65536u + 48u * 256u;  // exact counts below 2^16, 256 per octave above
-constexpr uint32_t kSelLds = 16384;                    // buckets counted in LDS per workgroup
-__host__ __device__ __forceinline__ uint32_t sel_bucket(u64 c) {
-  if (c < 65536) return (uint32_t)c;
-  int lg = 63;
-  while (!((c >> lg) & 1ull)) --lg;
-  return 65536u + (uint32_t)(lg - 16) * 256u + (uint32_t)((c >> (lg - 8)) & 255u);
-}
-// the smallest count in bucket b
-inline u64 sel_bucket_lo(uint32_t b) {
-  if (b < 65536u) return b;
-  const uint32_t lg = 16u + (b - 65536u) / 256u, mant = (b - 65536u) % 256u;
-  return (u64)(256u + mant) << (lg - 8u);
-}
-
-__global__ void k_sel_hist(u64* tab, u64 n, u64 minf, uint32_t* hist) {
-  __shared__ uint32_t h[kSelLds];
-  for (uint32_t i = threadIdx.x; i < kSelLds; i += blockDim.x) h[i] = 0;
-  __syncthreads();
-  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    const u64 cv = tab[2 * i + 1], c = cv & kCntMask;
-    if (cv >> kPosShift) tab[2 * i + 1] = c;  // the last launch's frontier positions are void now
-    if (tab[2 * i] == kEmpty64 || c < minf) continue;
-    const uint32_t b = sel_bucket(c);
-    if (b < kSelLds) atomicAdd(&h[b], 1u);
-    else atomicAdd(&hist[b], 1u);
-  }
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < kSelLds; i += blockDim.x)
-    if (h[i]) atomicAdd(&hist[i], h[i]);
-}
-
-__global__ void k_sel_collect(const u64* tab, u64 n, u64 minf, uint32_t bstar, uint32_t* out, uint32_t* nout,
-                              u64 cap) {
-  const int lane = threadIdx.x & 63;
-  for (u64 i0 = blockIdx.x * (u64)blockDim.x; i0 < n; i0 += (u64)gridDim.x * blockDim.x) {
-    const u64 i = i0 + threadIdx.x;
-    bool take = false;
-    if (i < n) {
-      const u64 c = tab[2 * i + 1] & kCntMask;
-      take = tab[2 * i] != kEmpty64 && c >= minf && sel_bucket(c) >= bstar;
-    }
-    const u64 bl = __ballot(take);
-    if (!bl) continue;
-    const int lead = __ffsll((long long)bl) - 1;
-    uint32_t base = 0;
-    if (lane == lead) base = atomicAdd(nout, (uint32_t)__popcll(bl));
-    base = __shfl(base, lead, 64);
-    const uint32_t pos = base + (uint32_t)__popcll(bl & ((1ull << lane) - 1ull));
-    if (take && pos < cap) out[pos] = (uint32_t)i;
-  }
-}
-
-__global__ void k_sel_gather(const uint32_t* slots, uint32_t n, const u64* tab, u64* key, u64* negc, uint32_t* idx) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    key[i] = tab[2 * (u64)slots[i]];
-    negc[i] = ~(tab[2 * (u64)slots[i] + 1] & kCntMask);
-    idx[i] = i;
-  }
-}
-
-// idx: the sorted order; the first n of the collected slots in that order -> the frontier
-__global__ void k_sel_pick(const uint32_t* slots, const uint32_t* idx, uint32_t n, uint32_t* fr) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    fr[i] = slots[idx ? idx[i] : i];
-}
-
-__global__ void k_sel_insert(const PairCount* pc, uint64_t n, SelParams q) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const u64 h = sel_slot(q, pair_key(pc[i].a, pc[i].b), q.st + kSelIns, q.st + kSelErr);
-    if (h != ~0ull) q.tab[2 * h + 1] = pc[i].count & kCntMask;
-  }
-}
-
-// The launch's logged changes into the table (whole chip, between launches): each a slot
-// (inserted when new) and an add; the adds commute, so their order is free.
-__global__ void k_sel_apply_log(const u64* log, u64 n, SelParams q) {
-  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    const u64 h = sel_slot(q, log[2 * i], q.st + kSelIns, q.st + kSelErr);
-    if (h != ~0ull) atomicAdd(q.tab + 2 * h + 1, log[2 * i + 1]);
-  }
-}
-
-// An empty table: every key kEmpty64, every count word 0.
-__global__ void k_sel_clear(u64* tab, u64 n) {
-  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-    tab[2 * i] = kEmpty64;
-    tab[2 * i + 1] = 0;
-  }
-}
-
-// The live pairs of a table (count > 0), for a bigger one.
-__global__ void k_sel_export(const u64* tab, u64 cap, PairCount* out, uint32_t* n) {
-  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < cap; i += (u64)gridDim.x * blockDim.x) {
-    const u64 k = tab[2 * i], c = tab[2 * i + 1] & kCntMask;
-    if (k == kEmpty64 || c == 0) continue;
-    const uint32_t j = atomicAdd(n, 1u);
-    out[j] = PairCount{(int32_t)(uint32_t)(k >> 32), (int32_t)(uint32_t)k, c, 0};
-  }
-}
-
-template <class T>
-T* wl_alloc(size_t n, size_t* acc) {
-  void* p = nullptr;
-  HIP_OK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-  *acc += std::max<size_t>(n, 1) * sizeof(T);
-  return static_cast<T*>(p);
-}
-
-constexpr uint32_t kRunPad = 4 * kStripV + 4;  // ints past the last run (its 16-B loads may overrun)
-
-}  // namespace
-
 // ==========================================================================================
 WordLoop::WordLoop(int ordinal, void* stream, int32_t unk_id) : ordinal_(ordinal), stream_(stream), unk_(unk_id) {
   HIP_OK(hipSetDevice(ordinal_));
@@ -2034,297 +1607,6 @@ void WordLoop::free_all() {
   ready_ = false;
 }
 
-bool WordLoop::upload(const TiledStream& ts, const uint64_t* d_weight) {
-  HIP_OK(hipSetDevice(ordinal_));
-  if (running_) stop();
-  free_all();
-  // the words of the tile stream in rank order (types layout: one entry per distinct word), each
-  // as a 16-B aligned run [length][tokens] of round_up(1 + length, 4) ints.  Threads over tile
-  // ranges: a sizing pass (words and ints per tile, every header's rank checked against its
-  // position), a prefix over the tiles, then each range fills its part of the runs.
-  const size_t T = ts.num_tiles();
-  const int P = (int)std::max<size_t>(1, std::min<size_t>({16, std::max(1u, std::thread::hardware_concurrency()),
-                                                          T / 64 + 1}));
-  auto par = [&](const std::function<void(int)>& f) {
-    if (P == 1) return f(0);
-    std::vector<std::thread> pool;
-    for (int k = 0; k < P; ++k) pool.emplace_back(f, k);
-    for (auto& th : pool) th.join();
-  };
-  auto range = [&](int k, size_t* t0, size_t* t1) {
-    *t0 = T * (size_t)k / (size_t)P;
-    *t1 = T * (size_t)(k + 1) / (size_t)P;
-  };
-  std::vector<uint32_t> tnw(T, 0), tfirst(T, 0);
-  std::vector<uint64_t> tints(T + 1, 0), ttok(T, 0);
-  std::vector<int32_t> tr0(T, -1);  // the rank of the tile's first word (-1: none)
-  std::vector<char> bad((size_t)P, 0);
-  par([&](int k) {
-    size_t t0, t1;
-    range(k, &t0, &t1);
-    for (size_t t = t0; t < t1 && !bad[(size_t)k]; ++t) {
-      const int32_t* p = ts.tok.data() + ts.off[t];
-      uint32_t nw = 0, wl = 0;
-      uint64_t ints = 0, ntk = 0;
-      for (uint32_t i = 0; i < ts.len[t]; ++i) {
-        if (p[i] < kHeaderLimit) {
-          const int32_t r = (int32_t)(uint32_t)(p[i] - kHeaderBase);
-          if (nw == 0) tr0[t] = r;
-          else if (r != tr0[t] + (int32_t)nw) bad[(size_t)k] = 1;  // ranks not consecutive
-          if (nw) ints += run_cap(wl);
-          ++nw;
-          wl = 0;
-        } else {
-          if (nw == 0) bad[(size_t)k] = 1;  // tokens before any header
-          ++wl;
-          ++ntk;
-        }
-      }
-      if (nw) ints += run_cap(wl);
-      tnw[t] = nw;
-      tints[t] = ints;
-      ttok[t] = ntk;
-    }
-  });
-  for (char b : bad)
-    if (b) return false;  // not the whole table in rank order: not for this loop
-  uint64_t words = 0, ints = 0, ntok = 0;
-  for (size_t t = 0; t < T; ++t) {
-    if (tnw[t] && tr0[t] != (int32_t)words) return false;
-    tfirst[t] = (uint32_t)words;
-    const uint64_t n = tints[t];
-    tints[t] = ints;
-    words += tnw[t];
-    ints += n;
-    ntok += ttok[t];
-  }
-  tints[T] = ints;
-  if (ints >= 0xFFFFFF00ull) return false;  // offsets are 32-bit
-  std::vector<uint32_t> woff(words + 1);
-  std::vector<int32_t> wtok(ints + kRunPad, 0);
-  par([&](int k) {
-    size_t t0, t1;
-    range(k, &t0, &t1);
-    for (size_t t = t0; t < t1; ++t) {
-      const int32_t* p = ts.tok.data() + ts.off[t];
-      uint64_t o = tints[t], w = tfirst[t];
-      int32_t* len = nullptr;
-      for (uint32_t i = 0; i < ts.len[t]; ++i) {
-        if (p[i] < kHeaderLimit) {
-          if (len) o = (o + kRunAlign - 1u) & ~(uint64_t)(kRunAlign - 1u);
-          woff[w++] = (uint32_t)o;
-          len = &wtok[o];
-          o += kRunHdr;  // (the weight ints are filled on the device: k_wl_set_weights)
-        } else {
-          wtok[o++] = p[i];
-          ++*len;
-        }
-      }
-    }
-  });
-  woff[words] = (uint32_t)ints;
-  nwords_ = (uint32_t)(woff.size() - 1);
-  nint_ = ints;
-  ntok_ = ntok;
-  ntiles_ = (uint32_t)ts.num_tiles();
-  if (nwords_ == 0 || nint_ >= (1ull << 31)) return false;  // hipcub sizes are int
-  if (nwords_ > kWordMask) return false;  // word ids share the pool entry with the run's groups
-  // the pool (below) is addressed with 32-bit offsets (pool top, lst_, directory values)
-  if (3 * ntok_ + 4096 >= (1ull << 32)) return false;
-  for (uint32_t w = 0; w < nwords_; ++w)
-    if (wtok[woff[w]] == 0) return false;  // words are never empty (strtok)
-  weight_ = reinterpret_cast<const unsigned long long*>(d_weight);
-  woff_h_ = woff;
-  wtok_ = wl_alloc<int32_t>(nint_ + kRunPad, &bytes_);
-  wtok0_ = wl_alloc<int32_t>(nint_ + kRunPad, &bytes_);
-  woff_ = wl_alloc<uint32_t>(nwords_ + 1, &bytes_);
-  tile_first_ = wl_alloc<uint32_t>(ntiles_, &bytes_);
-  tile_nw_ = wl_alloc<uint32_t>(ntiles_, &bytes_);
-  hipStream_t s = S(stream_);
-  HIP_OK(hipMemcpyAsync(wtok0_, wtok.data(), (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(woff_, woff.data(), woff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  k_wl_set_weights<<<(int)std::min<uint32_t>((nwords_ + 255) / 256, 4096), 256, 0, s>>>(wtok0_, woff_, nwords_, weight_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(tile_first_, tfirst.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(tile_nw_, tnw.data(), ntiles_ * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  // pool: the initial index (<= one entry per adjacent pair), the words-of lists (a merge lists
-  // the words it shortened: Σ over a run <= Σ (length - 1)) and the pair groups (<= 2 entries
-  // per occurrence merged: Σ <= 2 Σ (length - 1)); undone guesses release theirs (each is the
-  // last when its undo runs)
-  pool_cap_ = 3 * ntok_ + 4096;
-  pool_ = wl_alloc<u64>(2 * pool_cap_, &bytes_);  // WEnt: entry + signature
-  dstate_ = wl_alloc<uint32_t>(8, &bytes_);
-  HIP_OK(hipMemsetAsync(dstate_, 0, 8 * sizeof(uint32_t), s));
-  HIP_OK(hipStreamSynchronize(s));
-  reserve(kBaseVocab + 1);
-  build_index();
-  ready_ = true;
-  dirty_ = false;
-  return true;
-}
-
-// The index of the current words: every (pair, word) once, grouped by pair.
-void WordLoop::build_index() {
-  hipStream_t s = S(stream_);
-  size_t acc = 0;
-  // the pairs of the current words, compactly: per-word counts, their exclusive sum
-  uint32_t* pbase = wl_alloc<uint32_t>((size_t)nwords_ + 2, &acc);
-  uint32_t* pcnt = wl_alloc<uint32_t>((size_t)nwords_ + 2, &acc);
-  k_wl_pair_counts<<<(int)std::min<uint32_t>((nwords_ + 256) / 256, 4096), 256, 0, s>>>(wtok_, woff_, nwords_, pcnt);
-  HIP_OK(hipGetLastError());
-  {
-    size_t tb = 0;
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pcnt, pbase, (int)nwords_ + 1, s));
-    void* t0 = wl_alloc<uint8_t>(tb, &acc);
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t0, tb, pcnt, pbase, (int)nwords_ + 1, s));
-    HIP_OK(hipStreamSynchronize(s));
-    HIP_OK(hipFree(t0));
-  }
-  uint32_t npairs = 0;
-  HIP_OK(hipMemcpy(&npairs, pbase + nwords_, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const uint64_t n = std::max<uint64_t>(npairs, 1);
-  u64* kin = wl_alloc<u64>(n, &acc);
-  u64* kout = wl_alloc<u64>(n, &acc);
-  uint32_t* vin = wl_alloc<uint32_t>(n, &acc);
-  uint32_t* vout = wl_alloc<uint32_t>(n, &acc);
-  uint32_t* keep = wl_alloc<uint32_t>(n + 1, &acc);
-  uint32_t* head = wl_alloc<uint32_t>(n + 1, &acc);
-  uint32_t* pos = wl_alloc<uint32_t>(n + 1, &acc);
-  uint32_t* kidx = wl_alloc<uint32_t>(n + 1, &acc);
-  const int grid = 2048;
-  if (npairs == 0) {
-    HIP_OK(hipMemsetAsync(kin, 0xFF, sizeof(u64), s));
-    HIP_OK(hipMemsetAsync(vin, 0, sizeof(uint32_t), s));
-  }
-  k_wl_emit_pairs<<<grid, 256, 0, s>>>(wtok_, woff_, pbase, nwords_, unk_, kin, vin);
-  HIP_OK(hipGetLastError());
-  size_t tmp_bytes = 0, tb2 = 0;
-  HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
-  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, keep, pos, (int)n + 1, s));
-  tmp_bytes = std::max(tmp_bytes, tb2);
-  void* tmp = wl_alloc<uint8_t>(tmp_bytes, &acc);
-  HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kin, kout, vin, vout, (int)n, 0, 64, s));
-  HIP_OK(hipMemsetAsync(keep + n, 0, sizeof(uint32_t), s));
-  HIP_OK(hipMemsetAsync(head + n, 0, sizeof(uint32_t), s));
-  k_wl_mark<<<grid, 256, 0, s>>>(kout, vout, n, keep, head);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, keep, pos, (int)n + 1, s));
-  HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, head, kidx, (int)n + 1, s));
-  uint32_t tot[2] = {0, 0};
-  HIP_OK(hipMemcpyAsync(&tot[0], pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(&tot[1], kidx + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  init_pool_n_ = tot[0];
-  init_keys_n_ = tot[1];
-  if (init_pool_n_ > pool_cap_) fatal("WordLoop: the initial index exceeds the pool");
-  if (init_key_) HIP_OK(hipFree(init_key_));
-  if (init_val_) HIP_OK(hipFree(init_val_));
-  init_key_ = wl_alloc<u64>(init_keys_n_, &bytes_);
-  init_val_ = wl_alloc<u64>(init_keys_n_, &bytes_);
-  k_wl_scatter<<<grid, 256, 0, s>>>(kout, vout, n, keep, pos, head, kidx, woff_, reinterpret_cast<WEnt*>(pool_),
-                                    init_key_, init_val_);
-  HIP_OK(hipGetLastError());
-  k_wl_counts<<<256, 256, 0, s>>>(init_val_, init_keys_n_, init_pool_n_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(s));
-  for (void* p : {(void*)kin, (void*)kout, (void*)vin, (void*)vout, (void*)keep, (void*)head, (void*)pos, (void*)kidx,
-                  tmp, (void*)pbase, (void*)pcnt})
-    HIP_OK(hipFree(p));
-  // the directory: at most half full
-  uint64_t want = 1024;
-  while (want < 2 * init_keys_n_) want <<= 1;
-  if (want != dir_cap_) {
-    if (dkey_) HIP_OK(hipFree(dkey_));
-    if (dval_) HIP_OK(hipFree(dval_));
-    dir_cap_ = want;
-    dkey_ = wl_alloc<u64>(dir_cap_, &bytes_);
-    dval_ = wl_alloc<u64>(dir_cap_, &bytes_);
-  }
-  restore_index();
-}
-
-// The directory, the words-of lists and the counters as right after build_index().
-void WordLoop::restore_index() {
-  hipStream_t s = S(stream_);
-  std::fill(lists_.begin(), lists_.end(), 0ull);  // no words-of lists: every merge looks its pair up
-  HIP_OK(hipMemsetAsync(dkey_, 0xFF, dir_cap_ * sizeof(u64), s));
-  if (init_keys_n_) {
-    k_wl_dir_init<<<1024, 256, 0, s>>>(init_key_, init_val_, init_keys_n_, dkey_, dval_, dir_cap_ - 1);
-    HIP_OK(hipGetLastError());
-  }
-  if (lseq_) HIP_OK(hipMemsetAsync(lseq_, 0xFF, id_cap_ * sizeof(uint32_t), s));
-  const uint32_t st[8] = {0, (uint32_t)init_pool_n_, 0, 0, 0, 0, 0, 0};
-  HIP_OK(hipMemcpyAsync(dstate_, st, sizeof(st), hipMemcpyHostToDevice, s));
-  HIP_OK(hipStreamSynchronize(s));
-}
-
-bool WordLoop::load_current(const TiledStream& ts) {
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!ready_ || !posted_.empty()) return false;
-  stop();
-  std::vector<int32_t> wtok(nint_ + kRunPad, 0);
-  uint32_t w = 0;
-  bool open = false;
-  for (size_t t = 0; t < ts.num_tiles(); ++t) {
-    const int32_t* p = ts.tok.data() + ts.off[t];
-    for (uint32_t i = 0; i < ts.len[t]; ++i) {
-      if (p[i] < kHeaderLimit) {
-        if (open) ++w;
-        if ((uint32_t)(p[i] - kHeaderBase) != w || w >= nwords_) return false;
-        open = true;
-      } else {
-        if (!open) return false;
-        int32_t& len = wtok[woff_h_[w]];
-        if (kRunHdr + (uint32_t)len >= woff_h_[w + 1] - woff_h_[w]) return false;  // past the run
-        wtok[woff_h_[w] + kRunHdr + (uint32_t)len] = p[i];
-        ++len;
-      }
-    }
-  }
-  if (!open || w + 1 != nwords_) return false;
-  hipStream_t s = S(stream_);
-  HIP_OK(hipMemcpyAsync(wtok_, wtok.data(), wtok.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  k_wl_set_weights<<<(int)std::min<uint32_t>((nwords_ + 255) / 256, 4096), 256, 0, s>>>(wtok_, woff_, nwords_, weight_);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(s));
-  build_index();
-  dirty_ = false;
-  return true;
-}
-
-void WordLoop::load_tiles(const int32_t* tok, const uint64_t* tile_off, const uint32_t* tile_len) {
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!ready_) return;
-  if (!posted_.empty()) fatal("WordLoop::load_tiles with a merge in flight");
-  stop();
-  const int grid = (int)std::min<uint32_t>((ntiles_ + 255) / 256, 4096);
-  k_tiles_to_words<<<std::max(grid, 1), 256, 0, S(stream_)>>>(tok, tile_off, tile_len, ntiles_, woff_, wtok_);
-  HIP_OK(hipGetLastError());
-  build_index();
-  dirty_ = false;
-}
-
-void WordLoop::reset_words() {
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!ready_) return;
-  if (!posted_.empty()) fatal("WordLoop::reset_words with a merge in flight");
-  stop();
-  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, S(stream_)));
-  dirty_ = false;
-}
-
-void WordLoop::reset() {
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!ready_) return;
-  if (!posted_.empty()) fatal("WordLoop::reset with a merge in flight");
-  stop();
-  hipStream_t s = S(stream_);
-  HIP_OK(hipMemcpyAsync(wtok_, wtok0_, (nint_ + kRunPad) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  restore_index();
-  dirty_ = false;
-}
-
 void WordLoop::ensure_slots(uint32_t cap) {
   const uint32_t rec_cap = 4 * (cap + 1) + 64;
   // records and headers: non-coherent pinned memory (the device's L2 holds the stores until the
@@ -2365,19 +1647,15 @@ void WordLoop::reserve(int32_t max_id) {
   // the words-of lists (ids past the old capacity have none)
   u64* nl = wl_alloc<u64>(cap, &bytes_);
   uint32_t* ns = wl_alloc<uint32_t>(cap, &bytes_);
-
   HIP_OK(hipMemsetAsync(ns, 0xFF, (size_t)cap * sizeof(uint32_t), s));
-
   if (lseq_) {
     HIP_OK(hipMemcpyAsync(nl, lst_, (size_t)id_cap_ * sizeof(u64), hipMemcpyDeviceToDevice, s));
     HIP_OK(hipMemcpyAsync(ns, lseq_, (size_t)id_cap_ * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-
     HIP_OK(hipStreamSynchronize(s));
     for (void* q : {(void*)lst_, (void*)lseq_}) HIP_OK(hipFree(q));
   }
   lst_ = nl;
   lseq_ = ns;
-
   id_cap_ = cap;
   cap_ = cap;
   lists_.resize(cap, 0ull);
@@ -2385,25 +1663,30 @@ void WordLoop::reserve(int32_t max_id) {
   HIP_OK(hipStreamSynchronize(s));
 }
 
+// The launch arguments both kinds of launch share; the rest stays zero.
+void WordLoop::fill_params(WlParams* p) const {
+  p->wtok = wtok_;
+  p->weight = weight_;
+  p->pool = reinterpret_cast<WEnt*>(pool_);
+  p->pool_cap = pool_cap_;
+  p->dkey = dkey_;
+  p->dval = dval_;
+  p->dir_mask = dir_cap_ - 1;
+  p->lst = lst_;
+  p->lseq = lseq_;
+  p->id_cap = id_cap_;
+  p->dsum = dsum_;
+  p->dft = dft_;
+  p->dlist = dlist_;
+  p->dstate = dstate_;
+  p->cap = cap_;
+  p->unk = unk_;
+  p->fast = fast_ ? 1u : 0u;
+}
+
 void WordLoop::launch(uint32_t seq0) {
   WlParams p{};
-  p.wtok = wtok_;
-  p.weight = weight_;
-  p.pool = reinterpret_cast<WEnt*>(pool_);
-  p.pool_cap = pool_cap_;
-  p.dkey = dkey_;
-  p.dval = dval_;
-  p.dir_mask = dir_cap_ - 1;
-  p.lst = lst_;
-  p.lseq = lseq_;
-
-  p.id_cap = id_cap_;
-  p.dsum = dsum_;
-  p.dft = dft_;
-  p.dlist = dlist_;
-  p.dstate = dstate_;
-  p.cap = cap_;
-  p.unk = unk_;
+  fill_params(&p);
   p.ring = static_cast<const WlCmd*>(ring_dev_);
   p.status = static_cast<uint32_t*>(status_dev_);
   p.seq0 = seq0;
@@ -2412,23 +1695,28 @@ void WordLoop::launch(uint32_t seq0) {
   p.fin_min = fin_min_;
   p.prefetch = prefetch_ ? 1u : 0u;
   p.drain = drain_ ? 1u : 0u;
-  p.fast = fast_ ? 1u : 0u;
   for (int k = 0; k < kSlots; ++k) {
     p.sl[k].recs = static_cast<DeltaRecord*>(slot_[k].dev_recs);
     p.sl[k].hdr = static_cast<uint32_t*>(slot_[k].dev_hdr);
     p.sl[k].rec_cap = slot_[k].rec_cap;
   }
   status_[0] = 0;
-  HIP_OK(hipEventRecord((hipEvent_t)ev_[0], S(stream_)));
-  switch (probes_) {  // SHREDWORD_WL_PROBES (tests): 0 / 1 force the delta hash's HBM spill path
-    case 0: k_word_loop<false, 0><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
-    case 1: k_word_loop<false, 1><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
-    default: k_word_loop<false, kProbesDefault><<<1, kWlThreads, 0, S(stream_)>>>(p); break;
-  }
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord((hipEvent_t)ev_[1], S(stream_)));
+  launch_kernel(false, p);
   running_ = true;
   ++st_.launches;
+}
+
+// k_word_loop<self, probes_> on the stream, between the two events that time the launch.
+// SHREDWORD_WL_PROBES (tests): 0 / 1 force the delta hash's HBM spill path.
+void WordLoop::launch_kernel(bool self, const WlParams& p) {
+  static constexpr void (*kInst[2][3])(WlParams) = {
+      {k_word_loop<false, 0>, k_word_loop<false, 1>, k_word_loop<false, kProbesDefault>},
+      {k_word_loop<true, 0>, k_word_loop<true, 1>, k_word_loop<true, kProbesDefault>}};
+  hipStream_t s = S(stream_);
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[0], s));
+  kInst[self][probes_ == 0 ? 0 : probes_ == 1 ? 1 : 2]<<<1, kWlThreads, 0, s>>>(p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[1], s));
 }
 
 // The launch ended itself after ~10 s without a command.  It may have done so between a post's
@@ -2602,7 +1890,6 @@ void WordLoop::stop() {
   st_.kernel_ms += ms;
   uint32_t ds[8];
   HIP_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
-
   if (std::getenv("SHREDWORD_WL_REPORT") && st_.merges)
     std::fprintf(stderr, "[WL] %llu merges: device %.2f us a merge, of it the flag's system release %.2f us, "
                  "records out %.2f us; %llu merges spilled %llu delta keys to HBM\n", (unsigned long long)st_.merges,
@@ -2616,358 +1903,6 @@ void WordLoop::stop() {
                  ds[kStError]);
     fatal("k_word_loop failed");
   }
-}
-
-// ==========================================================================================
-// tiebreak=device
-
-void WordLoop::sel_free() {
-  void* ptrs[] = {ptab_, fr_[0], fr_[1], sst_dev_, thr_, sout_, upd_, shist_, scol_};
-  for (void* q : ptrs)
-    if (q) HIP_OK(hipFree(q));
-  ptab_ = thr_ = sout_ = nullptr;
-  fr_[0] = fr_[1] = sst_dev_ = upd_ = shist_ = scol_ = nullptr;
-  pcap_ = sout_cap_ = upd_cap_ = scol_cap_ = 0;
-  fcap_ = 0;
-}
-
-// The frontier from the whole table: the kSelK best pairs by (count desc, key asc) among those
-// >= min_freq (all of them when few), their slots flagged; the threshold = the last one taken
-// (or, when every pair of the counts' top buckets was taken, the lowest count of those buckets).
-bool WordLoop::sel_rebuild(uint64_t min_freq) {
-  const double t0 = now_seconds();
-  hipStream_t s = S(stream_);
-  HIP_OK(hipMemsetAsync(shist_, 0, kSelBuckets * sizeof(uint32_t), s));
-  k_sel_hist<<<1024, 512, 0, s>>>(ptab_, pcap_, min_freq, shist_);
-  HIP_OK(hipGetLastError());
-  std::vector<uint32_t> hist(kSelBuckets);
-  HIP_OK(hipMemcpyAsync(hist.data(), shist_, kSelBuckets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  uint64_t acc = 0;
-  uint32_t bstar = kSelBuckets;
-  for (uint32_t b = kSelBuckets; b-- > 0;) {
-    if (!hist[b]) continue;
-    acc += hist[b];
-    bstar = b;
-    if (acc >= kSelK) break;
-  }
-  uint32_t st[kSelStats] = {};
-  HIP_OK(hipMemcpyAsync(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  u64 thr[2] = {~0ull, 0ull};
-  uint32_t nf = 0;
-  if (acc > 0) {
-    if (acc > scol_cap_) {
-      if (scol_) HIP_OK(hipFree(scol_));
-      scol_cap_ = std::max<uint64_t>(2 * acc, 1 << 16);
-      scol_ = wl_alloc<uint32_t>(scol_cap_ + 1, &bytes_);
-    }
-    uint32_t* ncol = scol_ + scol_cap_;
-    HIP_OK(hipMemsetAsync(ncol, 0, sizeof(uint32_t), s));
-    k_sel_collect<<<1024, 512, 0, s>>>(ptab_, pcap_, min_freq, bstar, scol_, ncol, scol_cap_);
-    HIP_OK(hipGetLastError());
-    uint32_t nc = 0;
-    HIP_OK(hipMemcpyAsync(&nc, ncol, sizeof(nc), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    if (nc != acc) fatal("tiebreak=device: the frontier's collect disagrees with its histogram");
-    if (nc <= kSelK) {  // every pair of the top buckets: the threshold is their lowest count
-      nf = nc;
-      k_sel_pick<<<64, 256, 0, s>>>(scol_, nullptr, nf, fr_[0]);
-      HIP_OK(hipGetLastError());
-      thr[0] = std::max<u64>(sel_bucket_lo(bstar), min_freq);
-      thr[1] = ~0ull;
-    } else {  // the top kSelK in (count desc, key asc) order: sort by key, then stably by count
-      size_t acc2 = 0;
-      u64* key = wl_alloc<u64>(nc, &acc2);
-      u64* key2 = wl_alloc<u64>(nc, &acc2);
-      u64* negc = wl_alloc<u64>(nc, &acc2);
-      u64* negc2 = wl_alloc<u64>(nc, &acc2);
-      uint32_t* idx = wl_alloc<uint32_t>(nc, &acc2);
-      uint32_t* idx2 = wl_alloc<uint32_t>(nc, &acc2);
-      k_sel_gather<<<256, 256, 0, s>>>(scol_, nc, ptab_, key, negc, idx);
-      HIP_OK(hipGetLastError());
-      size_t tb = 0, tb2 = 0;
-      HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
-      HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
-      void* tmp = wl_alloc<uint8_t>(std::max(tb, tb2), &acc2);
-      HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, idx, idx2, (int)nc, 0, 64, s));
-      // counts in key order, then a stable sort by ~count
-      k_sel_gather<<<256, 256, 0, s>>>(scol_, nc, ptab_, key, negc, idx);  // key/negc of slot order
-      HIP_OK(hipGetLastError());
-      std::vector<uint32_t> order(nc);
-      std::vector<u64> kc(nc), nn(nc);
-      HIP_OK(hipMemcpyAsync(order.data(), idx2, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIP_OK(hipMemcpyAsync(nn.data(), negc, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
-      HIP_OK(hipMemcpyAsync(kc.data(), key, nc * sizeof(u64), hipMemcpyDeviceToHost, s));
-      HIP_OK(hipStreamSynchronize(s));
-      // (host) ~count in key order, sorted stably on the device
-      std::vector<u64> nk(nc);
-      for (uint32_t i = 0; i < nc; ++i) nk[i] = nn[order[i]];
-      HIP_OK(hipMemcpyAsync(negc, nk.data(), nc * sizeof(u64), hipMemcpyHostToDevice, s));
-      HIP_OK(hipMemcpyAsync(idx, order.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, negc, negc2, idx, idx2, (int)nc, 0, 64, s));
-      nf = kSelK;
-      k_sel_pick<<<64, 256, 0, s>>>(scol_, idx2, nf, fr_[0]);
-      HIP_OK(hipGetLastError());
-      uint32_t last = 0;
-      HIP_OK(hipMemcpyAsync(&last, idx2 + (nf - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIP_OK(hipStreamSynchronize(s));
-      thr[0] = ~nn[last];
-      thr[1] = kc[last];
-      for (void* q : {(void*)key, (void*)key2, (void*)negc, (void*)negc2, (void*)idx, (void*)idx2, tmp}) HIP_OK(hipFree(q));
-    }
-  }
-  st[kSelNF] = nf;
-  st[kSelBuf] = 0;
-  st[kSelStatus] = 0;
-  HIP_OK(hipMemcpyAsync(sst_dev_, st, sizeof(st), hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(thr_, thr, sizeof(thr), hipMemcpyHostToDevice, s));
-  HIP_OK(hipStreamSynchronize(s));
-  sst_.rebuilds += 1;
-  sst_.rebuild_ms += 1e3 * (now_seconds() - t0);
-  sst_.frontier_max = std::max<uint64_t>(sst_.frontier_max, nf);
-  return nf > 0;
-}
-
-int WordLoop::run_select(const std::vector<PairCount>& pairs, int32_t X0, uint32_t n_max, uint64_t min_freq,
-                         std::vector<SelectedMerge>* out) {
-  out->clear();
-  if (!ready_ || !posted_.empty()) return -1;
-  HIP_OK(hipSetDevice(ordinal_));
-  stop();
-  if (n_max == 0) return 0;
-  reserve(X0 + (int32_t)n_max);
-  hipStream_t s = S(stream_);
-  // the table: room for the initial pairs and ~64 new pairs a merge (C3 makes 62), 1.5x over;
-  // past 3/4 full it is grown 4x between launches.  Round 5, with the table updated from a log
-  // per launch: a smaller table is faster -- its rebuild histogram reads fewer slots and its
-  // updates stay in L2 / MALL (C3 A/B on one box: 33.5 M slots 57.4-57.5 k merges/s, 8.4 M
-  // 59.8-60.1 k, 4.2 M 60.3-60.4 k; profiles/r05_c3_tiebreak_table_ab.txt)
-  uint64_t want = 1 << 16;
-  while (want < 3 * ((uint64_t)pairs.size() + 64ull * n_max) / 2) want <<= 1;
-  if (const char* e = std::getenv("SHREDWORD_SELECT_TABLE_SLOTS")) {  // tests: a table that must grow
-    const uint64_t t = std::strtoull(e, nullptr, 10);
-    if (t >= 1024) {  // never below what the initial pairs need (they must all fit)
-      want = 1024;
-      while (want < t || want < 2 * (uint64_t)pairs.size()) want <<= 1;
-    }
-  }
-  if (!fr_[0]) {
-    fcap_ = 16384;
-    fr_[0] = wl_alloc<uint32_t>(fcap_, &bytes_);
-    fr_[1] = wl_alloc<uint32_t>(fcap_, &bytes_);
-    sst_dev_ = wl_alloc<uint32_t>(kSelWords, &bytes_);
-    thr_ = wl_alloc<u64>(2, &bytes_);
-    shist_ = wl_alloc<uint32_t>(kSelBuckets, &bytes_);
-  }
-  if (2ull * n_max > sout_cap_) {
-    if (sout_) HIP_OK(hipFree(sout_));
-    sout_cap_ = 2ull * n_max;
-    sout_ = wl_alloc<u64>(sout_cap_, &bytes_);
-  }
-  // the table-change log: many merges' records between two applications (a launch ends early
-  // when one more merge might not fit)
-  const uint64_t need_log = std::max<uint64_t>(1ull << 22, 16ull * ((uint64_t)cap_ + 2));
-  if (need_log > upd_cap_) {
-    if (upd_) HIP_OK(hipFree(upd_));
-    upd_cap_ = need_log;
-    upd_ = wl_alloc<uint32_t>(4 * upd_cap_, &bytes_);  // (key, delta) u64 pairs
-  }
-  HIP_OK(hipMemsetAsync(sst_dev_, 0, kSelWords * sizeof(uint32_t), s));
-  SelParams q{};
-  auto table_from = [&](const PairCount* dp, size_t np, uint64_t cap) {  // a fresh table holding dp
-    if (cap != pcap_) {
-      if (ptab_) HIP_OK(hipFree(ptab_));
-      pcap_ = cap;
-      ptab_ = wl_alloc<u64>(2 * pcap_, &bytes_);
-    }
-    k_sel_clear<<<1024, 256, 0, s>>>(ptab_, pcap_);
-    HIP_OK(hipGetLastError());
-    q.tab = ptab_;
-    q.pmask = pcap_ - 1;
-    q.fr[0] = fr_[0];
-    q.fr[1] = fr_[1];
-    q.fcap = fcap_;
-    q.st = sst_dev_;
-    q.thr = thr_;
-    q.out = sout_;
-    q.log = reinterpret_cast<u64*>(upd_);
-    q.log_cap = upd_cap_;
-    q.X0 = X0;
-    q.n_max = n_max;
-    q.min_freq = min_freq;
-    q.fill_max = (uint32_t)std::min<uint64_t>(3 * pcap_ / 4, 0xFFFFFFF0ull);
-    if (const char* e = std::getenv("SHREDWORD_SEL_PROBE")) q.probe = (uint32_t)std::atoi(e);
-    uint32_t zero = 0;
-    HIP_OK(hipMemcpyAsync(sst_dev_ + kSelIns, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(sst_dev_ + kSelErr, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
-    if (np) {
-      k_sel_insert<<<512, 256, 0, s>>>(dp, np, q);
-      HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipStreamSynchronize(s));
-    uint32_t err = 0;  // a pair that found no slot within the probe bound would be a lost count
-    HIP_OK(hipMemcpy(&err, sst_dev_ + kSelErr, sizeof(err), hipMemcpyDeviceToHost));
-    if (err) fatal("tiebreak=device: the pair table's initial pairs overran the probe bound");
-  };
-  {
-    size_t acc = 0;
-    PairCount* dp = pairs.empty() ? nullptr : wl_alloc<PairCount>(pairs.size(), &acc);
-    if (dp) HIP_OK(hipMemcpyAsync(dp, pairs.data(), pairs.size() * sizeof(PairCount), hipMemcpyHostToDevice, s));
-    table_from(dp, pairs.size(), want);
-    if (dp) HIP_OK(hipFree(dp));
-  }
-  sst_.table_slots = pcap_;
-  uint32_t m = 0;
-  if (sel_rebuild(min_freq)) {
-    WlParams p{};
-    p.wtok = wtok_;
-    p.weight = weight_;
-    p.pool = reinterpret_cast<WEnt*>(pool_);
-    p.pool_cap = pool_cap_;
-    p.dkey = dkey_;
-    p.dval = dval_;
-    p.dir_mask = dir_cap_ - 1;
-    p.lst = lst_;
-    p.lseq = lseq_;
-    p.id_cap = id_cap_;
-    p.dsum = dsum_;
-    p.dft = dft_;
-    p.dlist = dlist_;
-    p.dstate = dstate_;
-    p.cap = cap_;
-    p.unk = unk_;
-    p.fast = fast_ ? 1u : 0u;  // small merges through the small-merge body (then the pair-table tail)
-    p.sel = q;
-    dirty_ = true;
-    int stalls = 0;
-    for (;;) {
-      p.seq0 = seq_ + 1;
-      HIP_OK(hipEventRecord((hipEvent_t)ev_[0], s));
-      switch (probes_) {
-        case 0: k_word_loop<true, 0><<<1, kWlThreads, 0, s>>>(p); break;
-        case 1: k_word_loop<true, 1><<<1, kWlThreads, 0, s>>>(p); break;
-        default: k_word_loop<true, kProbesDefault><<<1, kWlThreads, 0, s>>>(p); break;
-      }
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipEventRecord((hipEvent_t)ev_[1], s));
-      HIP_OK(hipStreamSynchronize(s));
-      float ms = 0;
-      HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
-      sst_.kernel_ms += ms;
-      sst_.launches += 1;
-      uint32_t st[kSelWords];
-      HIP_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
-      uint32_t ds[8];
-      HIP_OK(hipMemcpy(ds, dstate_, sizeof(ds), hipMemcpyDeviceToHost));
-      if (ds[kStError]) {
-        std::fprintf(stderr, "[ERROR]\t k_word_loop<true>: error code %u\n", ds[kStError]);
-        fatal("tiebreak=device merge loop failed");
-      }
-      if (sel_report_)
-        std::fprintf(stderr, "[SELECT] launch %llu: merges %u..%u in %.3f ms (%.2f us/merge), status %u, table %u, "
-                     "%u LDS compactions\n", (unsigned long long)sst_.launches, m, st[kSelM], ms,
-                     st[kSelM] > m ? 1e3 * ms / (st[kSelM] - m) : 0.0, st[kSelStatus], st[kSelIns], st[kSelBuf]);
-      const bool progressed = st[kSelM] != m;
-      m = st[kSelM];
-      // the launch's logged changes into the table
-      const u64 logn = *reinterpret_cast<const u64*>(st + kSelLogW);
-      if (logn) {
-        const double tl = now_seconds();
-        k_sel_apply_log<<<1024, 256, 0, s>>>(reinterpret_cast<const u64*>(upd_), logn, q);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemsetAsync(sst_dev_ + kSelLogW, 0, sizeof(u64), s));
-        HIP_OK(hipMemcpyAsync(st + kSelIns, sst_dev_ + kSelIns, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        sst_.log_ms += 1e3 * (now_seconds() - tl);
-        sst_.log_entries += logn;
-      }
-      // a change whose pair found no table slot within the probe bound would be lost: the table
-      // would no longer be the corpus's count, so there is nothing exact to grow from
-      if (st[kSelErr]) fatal("tiebreak=device: a pair-table update overran the probe bound");
-      const uint32_t status = st[kSelStatus];
-      if (status == kSelDone) break;
-      // a rebuild that merged nothing is not a full table: only kSelFull and the
-      // inserts past the bound grow it.  Right after a rebuild the frontier holds entries at or
-      // above the threshold, so two such launches in a row would be a loop that cannot progress.
-      if (status == kSelRebuild && !progressed) {
-        if (++stalls > 1) fatal("tiebreak=device: two launches in a row ended for a rebuild without a merge");
-      } else {
-        stalls = 0;
-      }
-      // the table past 3/4 full, or without room for one more merge's new pairs: 4x, live pairs moved
-      if (st[kSelIns] > q.fill_max || status == kSelFull) {
-        size_t acc = 0;
-        PairCount* dp = wl_alloc<PairCount>(pcap_, &acc);
-        uint32_t* dn = wl_alloc<uint32_t>(1, &acc);
-        HIP_OK(hipMemsetAsync(dn, 0, sizeof(uint32_t), s));
-        k_sel_export<<<1024, 256, 0, s>>>(ptab_, pcap_, dp, dn);
-        HIP_OK(hipGetLastError());
-        uint32_t np = 0;
-        HIP_OK(hipMemcpyAsync(&np, dn, sizeof(np), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        // the exported pairs must survive the old table's release: keep them in their own buffer
-        const uint64_t grown = 4 * pcap_;
-        u64* old = ptab_;
-        ptab_ = nullptr;
-        pcap_ = 0;
-        table_from(dp, np, grown);
-        HIP_OK(hipFree(old));
-        HIP_OK(hipFree(dp));
-        HIP_OK(hipFree(dn));
-        ++sst_.grows;
-        p.sel = q;
-        if (!sel_rebuild(min_freq)) break;
-        continue;
-      }
-      if (status != kSelRebuild) fatal("tiebreak=device: the merge loop ended without a status");
-      if (!sel_rebuild(min_freq)) break;
-    }
-    uint32_t st[kSelWords];
-    HIP_OK(hipMemcpy(st, sst_dev_, sizeof(st), hipMemcpyDeviceToHost));
-    const u64* t64 = reinterpret_cast<const u64*>(st + kSelStats);
-    sst_.select_us += 1e-2 * (double)t64[0];
-    sst_.merge_us += 1e-2 * (double)t64[1];
-    sst_.listed += t64[2];
-    sst_.changed += t64[3];
-    sst_.occurrences += t64[4];
-    sst_.new_pairs += t64[5];
-    sst_.table_us += 1e-2 * (double)t64[6];
-    sst_.rec_us += 1e-2 * (double)t64[8];
-    sst_.append_us += 1e-2 * (double)t64[9];
-    sst_.tail_us += 1e-2 * (double)t64[10];
-    if (sel_report_ && m)
-      std::fprintf(stderr, "[SELECT] %u merges: device select %.2f us, merge %.2f us (of it table + frontier %.2f us: "
-                   "records %.2f, appends %.2f, tail %.2f) per merge; %llu LDS compactions, %llu listed / %llu changed "
-                   "words\n", m, 1e-2 * (double)t64[0] / m, 1e-2 * (double)t64[1] / m, 1e-2 * (double)t64[6] / m,
-                   1e-2 * (double)t64[8] / m, 1e-2 * (double)t64[9] / m, 1e-2 * (double)t64[10] / m, (unsigned long long)t64[7],
-                   (unsigned long long)t64[2], (unsigned long long)t64[3]);
-    sst_.table_pairs = st[kSelIns];
-  }
-  sst_.table_slots = pcap_;
-  sst_.merges += m;
-  std::vector<u64> o(2 * (size_t)m);
-  if (m) HIP_OK(hipMemcpy(o.data(), sout_, o.size() * sizeof(u64), hipMemcpyDeviceToHost));
-  out->resize(m);
-  for (uint32_t i = 0; i < m; ++i)
-    (*out)[i] = SelectedMerge{(int32_t)(uint32_t)(o[2 * i] >> 32), (int32_t)(uint32_t)o[2 * i], o[2 * i + 1]};
-  return (int)m;
-}
-
-uint64_t WordLoop::pool_used() const {
-  uint32_t v = 0;
-  if (dstate_) HIP_OK(hipMemcpy(&v, dstate_ + kStPoolTop, sizeof(v), hipMemcpyDeviceToHost));
-  return v;
-}
-
-void WordLoop::sync_tiles(int32_t* tok, const uint64_t* tile_off, uint32_t* tile_len) {
-  if (!dirty_ || !ready_) return;
-  if (running_) stop();
-  const int grid = (int)std::min<uint32_t>((ntiles_ + 3) / 4, 4096);
-  k_words_to_tiles<<<std::max(grid, 1), 256, 0, S(stream_)>>>(wtok_, woff_, tile_first_, tile_nw_, ntiles_, tok,
-                                                           tile_off, tile_len);
-  HIP_OK(hipGetLastError());
-  dirty_ = false;
 }
 
 }  // namespace shred

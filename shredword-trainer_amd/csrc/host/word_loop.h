@@ -41,6 +41,8 @@
 
 namespace shred {
 
+struct WlParams;  // the kernel's launch arguments (hip/word_loop_dev.h)
+
 struct WordLoopStats {
   uint64_t merges = 0;        // merges collected
   uint64_t undos = 0;         // guesses undone
@@ -192,6 +194,8 @@ class WordLoop {
   void build_index();
   void restore_index();
   void launch(uint32_t seq0);  // the first command the launch takes
+  void fill_params(WlParams* p) const;               // the fields every launch shares (wtok .. unk, fast)
+  void launch_kernel(bool self, const WlParams& p);  // k_word_loop<self, probes_> between ev_[0] and ev_[1]
   void recover_timeout();
   // Writes one command; (loff, lcnt1): the words-of list of max(a, b) if known (count + 1; 0: none).
   uint32_t post(uint32_t op, int32_t a, int32_t b, int32_t X, uint32_t loff = 0, uint32_t lcnt1 = 0);
@@ -264,7 +268,7 @@ class WordLoop {
   bool fast_ = true;
   bool last_changes_ = false;
   std::vector<Post> posted_;
-  // tiebreak=device: pair table, frontier, state (see word_loop.hip SelParams)
+  // tiebreak=device: pair table, frontier, state (see word_loop_dev.h SelParams)
   void sel_free();
   bool sel_rebuild(uint64_t min_freq);  // false: no pair at or above min_freq is left
   unsigned long long* ptab_ = nullptr;  // tiebreak=device pair table: 16-B slots (key, count | pos)

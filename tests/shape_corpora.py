@@ -9,7 +9,7 @@ regenerate the shapes.
 ===============  ======================================================  ==========================
 shape            constant                                                what switches there
 ===============  ======================================================  ==========================
-strip_edge       kStripTok = 4*kStripV - kRunHdr = 25 (word_loop.hip)    ``L <= kStripTok``: the word
+strip_edge       kStripTok = 4*kStripV - kRunHdr = 25 (word_loop_dev.h)  ``L <= kStripTok``: the word
                                                                          is merged in registers, a
                                                                          longer one by the chain walk
 tile_edge        kTileTokens = kWaveTok = 1024, header included          ``fill + need > kTileTokens``

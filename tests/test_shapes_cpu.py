@@ -118,7 +118,7 @@ def _crossings(lens, bound, pick=lambda w: True):
 
 
 # bound = the largest token count on the near side, from the comparison in the code:
-#   word_loop.hip   `if (L <= kStripTok)`                              -> 25
+#   word_loop.hip   `if (L <= kStripTok)` (kStripTok: word_loop_dev.h) -> 25
 #   tiles.cpp       `fill + need > kTileTokens`, need = len + 1        -> 1023 shares a tile
 #   resident_loop   `len > kWaveTok` (a tile's length, header included) -> 1023
 #   pair_count.hip  `for (cs = 0; cs < len; cs += kChunk)`, len = tile  -> 4095 is one chunk
@@ -289,10 +289,10 @@ def _const(path, name):
 def test_constants_guard():
     """Whoever retunes one of these: regenerate tests/golden/shapes (make_golden.py shapes) with
     shape_corpora.py's lengths moved to the new boundary."""
-    assert int(_const("hip/word_loop.hip", "kStripV")) == sc.K_STRIP_V
-    assert int(_const("hip/word_loop.hip", "kRunHdr")) == sc.K_RUN_HDR
-    assert _const("hip/word_loop.hip", "kStrip") == "4 * kStripV"
-    assert _const("hip/word_loop.hip", "kStripTok") == "kStrip - kRunHdr"
+    assert int(_const("hip/word_loop_dev.h", "kStripV")) == sc.K_STRIP_V
+    assert int(_const("hip/word_loop_dev.h", "kRunHdr")) == sc.K_RUN_HDR
+    assert _const("hip/word_loop_dev.h", "kStrip") == "4 * kStripV"
+    assert _const("hip/word_loop_dev.h", "kStripTok") == "kStrip - kRunHdr"
     assert int(_const("host/tiles.h", "kTileTokens")) == sc.K_TILE_TOKENS
     assert int(_const("hip/hip_common.h", "kThreads")) == sc.K_THREADS
     assert int(_const("hip/hip_common.h", "kPer")) == sc.K_PER
