@@ -84,6 +84,59 @@ int shred_encoder_long_words(const ShredEncoder* enc);
  * the rounds it has run since the encoder was created.  Returns 0, -1 for NULL. */
 int shred_encoder_long_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* words, uint64_t* rounds);
 
+/* ---- BPE-dropout: seeded subword regularisation (Provilkov et al. 2020) -----------------------------
+ *
+ * An encoder holds a dropout probability p in [0, 1] and a 64-bit seed; the default is p = 0.  With
+ * p == 0 nothing below applies, and every call behaves, and is routed, as described elsewhere in this
+ * file.  With p > 0, for every word of at most SHRED_ENCODE_MAX_WORD bytes:
+ *
+ *   - The tokens start as the byte-map ids of the word's bytes.
+ *   - A candidate is an adjacent token pair (a, b) that the merge list knows; its rank is the first
+ *     merge that lists the pair.
+ *   - The candidate's position pos is the byte offset, in the text passed to the call, of the first
+ *     byte of the right token b (a 64-bit value).
+ *   - The candidate is dropped iff (u >> 32) < T, where
+ *       mix(x):  x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53;
+ *                x ^= x >> 33   (mod 2^64: murmur3's fmix64),
+ *       u = mix(mix(seed + 0x9E3779B97F4A7C15 * (pos + 1)) ^ rank),
+ *       T = (uint64_t)(p * 4294967296.0), computed once in double arithmetic (p = 1: T = 2^32, every
+ *           candidate is dropped and every non-delimiter byte keeps its byte-map id).
+ *   - Repeat: among the candidates that are not dropped, merge the one of lowest rank, the leftmost on
+ *     a tie.  Stop when none is left.
+ *
+ * A decision depends on (seed, pos, rank) alone: it is the same however often the loop meets that
+ * candidate, independent of the neighbouring boundaries, and independent of how the text was staged.
+ * This is the "drop a candidate once and for all" variant of BPE-dropout; it differs from the variants
+ * that draw again at every merge step.  The same (text, p, seed) always gives the same ids, on host
+ * and device calls alike; a new seed (per epoch, say) gives a new segmentation.  When p > 0 but
+ * T == 0 (p < 2^-32) the call behaves as with p == 0.
+ *
+ * "The text passed to the call":
+ *   shred_encode*, shred_encode_spans*, shred_encode_special*
+ *       pos is the offset in `text`; the pieces of the host calls add their own offset.  The special
+ *       calls encode a copy of the same length with the matches blanked, so the offsets are the
+ *       text's; no merge reaches across a special, and the specials themselves are never dropped.
+ *   shred_encode_docs*
+ *       these encode a copy in which every document is followed by one inserted byte (below), and pos
+ *       is the offset in that copy: for a byte of document d, its offset in the concatenated text
+ *       plus d.
+ * Everything behind the ids (starts, line_off, row_off, the special cut, decode, the batch calls)
+ * follows from the ids' byte lengths and is defined as without dropout.
+ *
+ * Dropout reaches words of at most SHRED_ENCODE_MAX_WORD (1024) bytes.  In long-word mode a longer
+ * word is encoded by the long-word pass exactly as without dropout; with the mode off it returns -3.
+ *
+ * Cost.  With p == 0: none, and nothing is allocated.  With p > 0 every call encodes each occurrence
+ * of each word on its own (the word cache is neither filled nor read, since every occurrence differs;
+ * such calls are not counted as cache fallbacks), and writes more ids.  Dropout's scratch (4 B per text
+ * byte of the largest call) is allocated on the first dropout call and freed with the encoder.
+ */
+/* p in [0, 1]; p == 0 turns dropout off.  Returns 0; -1 for NULL, p < 0, p > 1 or NaN (the previous
+ * setting stays). */
+int shred_encoder_set_dropout(ShredEncoder* enc, double p, uint64_t seed);
+/* The setting; either pointer may be NULL.  Returns 0, -1 for NULL. */
+int shred_encoder_dropout(const ShredEncoder* enc, double* p, uint64_t* seed);
+
 /* Encodes n bytes of host text into host ids.  Returns the number of ids written (<= the number
  * of non-delimiter bytes, so cap >= n always suffices), or -1 on a bad argument / device error,
  * -2 when cap is smaller than the result, -3 when a word exceeds SHRED_ENCODE_MAX_WORD (with the

@@ -579,7 +579,8 @@ EncodeDevice::~EncodeDevice() {
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
 }
 
-int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms) {
+int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms,
+                             uint64_t pos_base) {
   if (kernel_ms) *kernel_ms = 0;
   if (n == 0) return 0;
   if (!text || !out) return -1;
@@ -594,7 +595,10 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
   const u64 nb = (n + kChunk - 1) / kChunk;
   const char* env = std::getenv("SHREDWORD_ENCODE_CACHE");
-  bool cached = !(env && env[0] == '0');
+  // dropout: every occurrence of a word differs, so the word cache cannot serve it (and such a call
+  // is no fallback)
+  const bool drop = drop_thresh_ != 0;
+  bool cached = !drop && !(env && env[0] == '0');
   ENC_OK(hipEventRecord(c.ev[0], st));
   size_t cc = c.ccap_min, cmax = c.ccap;
   // tests: "<start>[:<max>]" slots for this call (powers of two in [kThreads, ccap]: the encode
@@ -638,6 +642,10 @@ int64_t EncodeDevice::encode(const uint8_t* text, size_t n, int32_t* out, size_t
       ENC_OK(hipMemsetAsync(bcnt + 2 * nb, 0, (nb + 1) * 8, st));
       k_cache_words<<<dim3((unsigned)nb), dim3(kThreads), 0, st>>>(text, n, cslot, cc - 1, rank, out, (u64)cap, bcnt,
                                                                    bcnt + 2 * nb, nb, misc, pad, lcnt);
+    } else if (drop) {
+      if (dropout_words(text, n, c.table.get(), c.byte_map.get(), pad, rank, c.cap_bytes, c.tcnt.get(), bcnt, misc, lcnt,
+                        pos_base, st) < 0)
+        return -1;
     } else {
       const bool aligned = (reinterpret_cast<uintptr_t>(text) & 15) == 0;
       auto kern = aligned ? (packed_ ? k_encode_words<true, true> : k_encode_words<true, false>)
@@ -705,7 +713,7 @@ int64_t EncodeDevice::encode_host(const uint8_t* text, size_t n, int32_t* out, s
       return -1;
     }
     ENC_OK(hipMemcpyAsync(hs.text.get(), text + pos, len, hipMemcpyHostToDevice, st));
-    const int64_t r = encode(hs.text.get(), len, hs.out.get(), cap - done, nullptr, nullptr);
+    const int64_t r = encode(hs.text.get(), len, hs.out.get(), cap - done, nullptr, nullptr, (uint64_t)pos);
     if (r < 0) return r;
     if (r > 0) {
       ENC_OK(hipMemcpyAsync(out + done, hs.out.get(), (size_t)r * 4, hipMemcpyDeviceToHost, st));

@@ -164,7 +164,8 @@ struct DocsState : PassState {
 
 int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials,
                                   int32_t* out, size_t cap, int64_t* starts, int64_t* row_off, uint64_t start_base,
-                                  const std::vector<int32_t>& lens, void* stream, double* kernel_ms) {
+                                  const std::vector<int32_t>& lens, void* stream, double* kernel_ms,
+                                  uint64_t pos_base) {
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0;
   if (!row_off || (n && (!text || !out)) || (!doc_off && docs)) return -1;
   const size_t rows = doc_off ? docs : 1;
@@ -208,8 +209,9 @@ int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* 
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[3], st));
   double enc_ms = 0, special_ms = 0, span_ms = 0;
-  const int64_t T = specials ? encode_special(copy, total, out, cap, lens, stream, &enc_ms, &special_ms)
-                             : encode(copy, total, out, cap, stream, &enc_ms);
+  // (dropout's positions are offsets in the copy: shredword_encode.h)
+  const int64_t T = specials ? encode_special(copy, total, out, cap, lens, stream, &enc_ms, &special_ms, pos_base)
+                             : encode(copy, total, out, cap, stream, &enc_ms, pos_base);
   if (T < 0) return T;
   ENC_OK(hipSetDevice(device_));  // (encode's guard restored the caller's)
   size_t nl = 0;
@@ -301,7 +303,7 @@ int64_t EncodeDevice::encode_docs_host(const uint8_t* text, size_t n, const int6
       const size_t room = pass ? std::min(cap - done, hs.out.cap()) : hs.out.cap();
       const int64_t r = encode_docs(hs.text.get(), len, doc_off ? dx.hoff.get() : nullptr, doc_off ? nd : 0, specials,
                                     hs.out.get(), room, pass && starts ? dx.hstarts.get() : nullptr, dx.hrow.get(),
-                                    (uint64_t)pos, lens, nullptr, nullptr);
+                                    (uint64_t)pos, lens, nullptr, nullptr, (uint64_t)(pos + d));
       if (r < 0) return r;
       ENC_OK(hipSetDevice(device_));
       const size_t T = (size_t)r;

@@ -362,8 +362,8 @@ int64_t EncodeDevice::encode_spans_host(const uint8_t* text, size_t n, int32_t* 
       dout = hs.out.get();
     }
     ENC_OK(hipMemcpyAsync(dtext, text + pos, len, hipMemcpyHostToDevice, st));
-    const int64_t r = specials ? encode_special(dtext, len, dout, cap - done, lens, nullptr, nullptr, nullptr)
-                               : encode(dtext, len, dout, cap - done, nullptr, nullptr);
+    const int64_t r = specials ? encode_special(dtext, len, dout, cap - done, lens, nullptr, nullptr, nullptr, (u64)pos)
+                               : encode(dtext, len, dout, cap - done, nullptr, nullptr, (u64)pos);
     if (r < 0) return r;
     ENC_OK(hipSetDevice(device_));
     const size_t T = (size_t)r;

@@ -255,10 +255,10 @@ void EncodeDevice::set_specials(const uint8_t* bytes, const size_t* off, size_t 
 
 int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out, size_t cap,
                                      const std::vector<int32_t>& lens, void* stream, double* enc_ms,
-                                     double* special_ms) {
+                                     double* special_ms, uint64_t pos_base) {
   if (enc_ms) *enc_ms = 0;
   if (special_ms) *special_ms = 0;
-  if (sx_off_.size() < 2) return encode(text, n, out, cap, stream, enc_ms);  // no special registered
+  if (sx_off_.size() < 2) return encode(text, n, out, cap, stream, enc_ms, pos_base);  // no special registered
   if (n == 0) return 0;
   if (!text || !out) return -1;
   DeviceGuard guard;
@@ -290,7 +290,7 @@ int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out
   const size_t M = (size_t)sx.host[0];
   if (M == 0) {  // no match: the plain encode
     ENC_OK(hipEventRecord(ev[1], st));
-    const int64_t T = encode(text, n, out, cap, stream, enc_ms);
+    const int64_t T = encode(text, n, out, cap, stream, enc_ms, pos_base);
     if (T >= 0 && special_ms) ENC_OK(ev.sum_ms(1, special_ms));
     return T;
   }
@@ -303,7 +303,8 @@ int64_t EncodeDevice::encode_special(const uint8_t* text, size_t n, int32_t* out
                                                                         (u64)max_word());
   ENC_OK(hipGetLastError());
   ENC_OK(hipEventRecord(ev[1], st));
-  const int64_t Tw = encode(masked, n, wids, sx.wids.cap(), stream, enc_ms);
+  // (the blanked copy has the text's length, so its offsets are the text's)
+  const int64_t Tw = encode(masked, n, wids, sx.wids.cap(), stream, enc_ms, pos_base);
   if (Tw < 0) return Tw;
   ENC_OK(hipSetDevice(device_));  // (encode's guard restored the caller's)
   const size_t T = (size_t)Tw + M;

@@ -227,6 +227,17 @@ int shred_encoder_long_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, u
   return 0;
 }
 
+int shred_encoder_set_dropout(ShredEncoder* enc, double p, uint64_t seed) {
+  return enc && enc->dev->set_dropout(p, seed) ? 0 : -1;
+}
+
+int shred_encoder_dropout(const ShredEncoder* enc, double* p, uint64_t* seed) {
+  if (!enc) return -1;
+  if (p) *p = enc->dev->dropout_p();
+  if (seed) *seed = enc->dev->dropout_seed();
+  return 0;
+}
+
 int64_t shred_encode(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* out, size_t cap) {
   if (!enc || (n && (!text || !out))) return -1;
   return enc->dev->encode_host(text, n, out, cap);

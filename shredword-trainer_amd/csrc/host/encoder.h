@@ -53,8 +53,10 @@ class EncodeDevice {
                               std::string* why);
   ~EncodeDevice();
   // text / out on the device; stream = hipStream_t or nullptr.  Returns ids, -1 device error,
-  // -2 cap too small, -3 word longer than max_word().
-  int64_t encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms);
+  // -2 cap too small, -3 word longer than max_word().  pos_base: the position of text[0] in the text
+  // passed to the C call (the host paths' pieces; only dropout looks at positions).
+  int64_t encode(const uint8_t* text, size_t n, int32_t* out, size_t cap, void* stream, double* kernel_ms,
+                 uint64_t pos_base = 0);
   // Host buffers: staged through cached device buffers in pieces of <= kHostPiece bytes cut at
   // delimiters (device memory ~14 B per piece byte, whatever n is).
   static constexpr size_t kHostPiece = size_t(256) << 20;
@@ -70,6 +72,13 @@ class EncodeDevice {
   // What the long pass holds and has done: bytes of device scratch allocated for long words (0
   // until a call meets one), long words encoded, rounds run.
   void long_stats(uint64_t* scratch_bytes, uint64_t* words, uint64_t* rounds) const;
+
+  // ---- BPE-dropout (encode_dropout.hip; shred_encoder_set_dropout defines it) ----
+  // p in [0, 1] and the seed; false (nothing changes) for any other p.  With a threshold
+  // T = (uint64_t)(p * 2^32) > 0 every encode call takes the direct dropout kernels.
+  bool set_dropout(double p, uint64_t seed);
+  double dropout_p() const { return drop_p_; }
+  uint64_t dropout_seed() const { return drop_seed_; }
 
   // encode() plus the span passes (encode_spans.hip): starts (nullptr or cap int64) and line_off
   // (nullptr or line_cap int64) on the device, as include/shredword_encode.h defines them.
@@ -94,18 +103,20 @@ class EncodeDevice {
   // encode() with the registered special tokens matched in the text: out receives the word ids
   // and the special ids in text order.  Returns as encode().  lens: as encode_spans takes it.
   // enc_ms / special_ms: nullptr or the device time of the encode passes / of the special passes.
+  // pos_base: as encode takes it.
   int64_t encode_special(const uint8_t* text, size_t n, int32_t* out, size_t cap, const std::vector<int32_t>& lens,
-                         void* stream, double* enc_ms, double* special_ms);
+                         void* stream, double* enc_ms, double* special_ms, uint64_t pos_base = 0);
 
   // ---- batches of documents (encode_docs.hip; include/shredword_encode.h defines the rows) ----
   // text (n bytes), doc_off (nullptr with docs == 0: one document; else docs + 1 entries, validated
   // on the device) and the outputs on the device: out (cap ids), starts (nullptr or cap int64; each
   // gets start_base added), row_off (rows + 1 int64).  specials: the ids come from encode_special().
   // kernel_ms: nullptr or 4 doubles (encode, span, special, document passes).  Returns as
-  // encode_spans(), -6 for a bad doc_off.
+  // encode_spans(), -6 for a bad doc_off.  pos_base: the position of the copy's first byte in the copy
+  // of the whole text (doc_off[first] + first for a piece that begins with document `first`).
   int64_t encode_docs(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials, int32_t* out,
                       size_t cap, int64_t* starts, int64_t* row_off, uint64_t start_base,
-                      const std::vector<int32_t>& lens, void* stream, double* kernel_ms);
+                      const std::vector<int32_t>& lens, void* stream, double* kernel_ms, uint64_t pos_base = 0);
   // The same on host buffers, in pieces of whole documents (doc_off is validated on the host).
   int64_t encode_docs_host(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, bool specials,
                            int32_t* out, size_t cap, int64_t* starts, int64_t* row_off,
@@ -176,12 +187,20 @@ class EncodeDevice {
   // word).  Returns 0, -1 on a device error, -3 for a word above kEncMaxLongWord.
   int long_pass(const uint8_t* text, size_t n, const uint64_t* table, const int32_t* byte_map, int32_t* pad,
                 size_t pad_cap, void* stream, const uint32_t** cnt);
+  // The word pass of encode() under dropout: what k_encode_words does (ids packed per span in pad,
+  // tcnt, bcnt, the long-word flag in misc[1]; rank: its scratch; pad and rank hold scratch_cap >= n
+  // int32), with the candidates at positions pos_base + offset dropped.  Returns 0, -1 on an error.
+  int dropout_words(const uint8_t* text, size_t n, const uint64_t* table, const int32_t* byte_map, int32_t* pad,
+                    int32_t* rank, size_t scratch_cap, uint32_t* tcnt, uint64_t* bcnt, uint64_t* misc,
+                    const uint32_t* lcnt, uint64_t pos_base, void* stream);
   int device_ = 0;
   void* stream_ = nullptr;  // hipStream_t
   uint64_t mask_ = 0;       // of the merge-rank table
   bool packed_ = false;     // 16-bit LDS strips (ids < 0xFFFF)
   uint64_t fallbacks_ = 0;
   bool long_words_ = false;  // words above kEncMaxWord go to the long pass
+  double drop_p_ = 0;        // dropout as set; drop_thresh_ = (uint64_t)(drop_p_ * 2^32), 0 = off
+  uint64_t drop_seed_ = 0, drop_thresh_ = 0;
   // The registered special tokens (set_specials); the units build their device tables from them.
   std::vector<uint8_t> sx_bytes_;  // the specials' bytes, in id order
   std::vector<uint32_t> sx_off_;   // K + 1 offsets into sx_bytes_
@@ -189,7 +208,7 @@ class EncodeDevice {
   bool sx_dirty_ = false;          // the scan table on the device is older than the set
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
-  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kPasses };
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

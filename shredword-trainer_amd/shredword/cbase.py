@@ -159,6 +159,10 @@ lib.shred_encoder_set_long_words.argtypes, lib.shred_encoder_set_long_words.rest
 lib.shred_encoder_long_words.argtypes, lib.shred_encoder_long_words.restype = [Encoder], c_int
 lib.shred_encoder_long_stats.argtypes = [Encoder, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
 lib.shred_encoder_long_stats.restype = c_int
+# BPE-dropout
+lib.shred_encoder_set_dropout.argtypes, lib.shred_encoder_set_dropout.restype = [Encoder, c_double, c_uint64], c_int
+lib.shred_encoder_dropout.argtypes = [Encoder, POINTER(c_double), POINTER(c_uint64)]
+lib.shred_encoder_dropout.restype = c_int
 # token byte offsets and per-line id offsets
 lib.shred_encoder_token_lengths.argtypes = [Encoder, POINTER(c_int32), c_size_t]
 lib.shred_encoder_token_lengths.restype = c_int

@@ -53,9 +53,9 @@ def join_docs(texts):
 
 class BPEEncoder:
     def __init__(self, model_path: str, vocab_path: str = None, unk_id: int = 0, device: int = 0,
-                 special_tokens=None, *, long_words: bool = False):
+                 special_tokens=None, *, long_words: bool = False, dropout: float = 0.0, seed: int = 0):
         """special_tokens: None or a list of bytes / str, see set_special_tokens.  long_words: see the
-        property of that name."""
+        property of that name.  dropout, seed: see set_dropout."""
         self.enc = lib.shred_encoder_load(model_path.encode("utf-8"),
                                           vocab_path.encode("utf-8") if vocab_path else None,
                                           int(unk_id), int(device))
@@ -65,11 +65,13 @@ class BPEEncoder:
         _LIVE.add(self)
         self._specials = []
         self.long_words = long_words
+        self.set_dropout(dropout, seed)
         if special_tokens:
             self.set_special_tokens(special_tokens)
 
     @classmethod
-    def from_merges(cls, merges, byte_map=None, device: int = 0, special_tokens=None, *, long_words: bool = False):
+    def from_merges(cls, merges, byte_map=None, device: int = 0, special_tokens=None, *, long_words: bool = False,
+                    dropout: float = 0.0, seed: int = 0):
         """merges: (M, 3) int32 array of (first, second, 256 + m) as in a .model file."""
         m = np.ascontiguousarray(np.asarray(merges, dtype=np.int32).reshape(-1, 3))
         bm = None if byte_map is None else np.ascontiguousarray(np.asarray(byte_map, dtype=np.int32))
@@ -85,6 +87,7 @@ class BPEEncoder:
         _LIVE.add(self)
         self._specials = []
         self.long_words = long_words
+        self.set_dropout(dropout, seed)
         if special_tokens:
             self.set_special_tokens(special_tokens)
         return self
@@ -108,6 +111,24 @@ class BPEEncoder:
         v = [ctypes.c_uint64() for _ in range(3)]
         lib.shred_encoder_long_stats(self.enc, *(ctypes.byref(x) for x in v))
         return dict(zip(("scratch_bytes", "words", "rounds"), (x.value for x in v)))
+
+    def set_dropout(self, p: float, seed: int = 0):
+        """BPE-dropout (subword regularisation): with p > 0 every encode call drops each candidate merge
+        with probability p, so a word's segmentation varies with its place in the text and with the seed;
+        p = 0 (the default) is the canonical segmentation, p = 1 leaves every byte on its own.  A candidate
+        is dropped once and for all, as a function of (seed, byte position in the text, merge rank): the
+        same (text, p, seed) always gives the same ids, on host and device calls alike, and a new seed (one
+        per epoch, say) a new segmentation.  Words above MAX_WORD bytes (long_words) are never dropped.
+        p outside [0, 1] raises ValueError and leaves the setting as it was."""
+        if lib.shred_encoder_set_dropout(self.enc, float(p), int(seed) & (2 ** 64 - 1)):
+            raise ValueError("dropout must be a probability in [0, 1]")
+
+    @property
+    def dropout(self) -> tuple:
+        """(p, seed) as set_dropout set them."""
+        p, seed = ctypes.c_double(), ctypes.c_uint64()
+        lib.shred_encoder_dropout(self.enc, ctypes.byref(p), ctypes.byref(seed))
+        return p.value, seed.value
 
     def set_special_tokens(self, tokens):
         """Replaces the encoder's special tokens (an empty list clears them).  tokens: bytes / str, at most

@@ -1,5 +1,7 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs | long]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs | long] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
+leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
 trailing `decode`, decode_device on the corpus's ids and line offsets (median / min / max ms and
 GB/s of output), and the host loop shred_decode on the same ids (wall time) for comparison; with a
@@ -33,6 +35,19 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, ".."))
+
+
+def option(name, conv, default):
+    """The value behind `name` on the command line, taken out of sys.argv."""
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    value = conv(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    return value
+
+
+dropout, seed = option("--dropout", float, 0.0), option("--seed", int, 0)
 mode, corpus = sys.argv[1], sys.argv[2]
 if mode == "prepare":
     nbytes, d = int(sys.argv[3]), sys.argv[4]
@@ -58,13 +73,14 @@ else:
     reps = int(args[1]) if len(args) > 1 else 5
     import torch
     from shredword.encoder import BPEEncoder
-    enc = BPEEncoder(os.path.join(d, "m.model"), os.path.join(d, "m.vocab"), unk_id=0)
+    enc = BPEEncoder(os.path.join(d, "m.model"), os.path.join(d, "m.vocab"), unk_id=0, dropout=dropout, seed=seed)
     text = torch.from_numpy(np.fromfile(corpus, dtype=np.uint8)).cuda()
     out = torch.empty(text.numel(), dtype=torch.int32, device="cuda")
     ids, _ = enc.encode_device(text, out)
     ms = sorted(enc.encode_device(text, out)[1] for _ in range(reps))
     print(os.environ.get("SHREDWORD_LIB", "default"), "ids", ids.numel(), "ms", ms[len(ms) // 2],
-          "GB/s", text.numel() / ms[len(ms) // 2] / 1e6, "min", ms[0], "max", ms[-1], flush=True)
+          "GB/s", text.numel() / ms[len(ms) // 2] / 1e6, "min", ms[0], "max", ms[-1],
+          *(("dropout", dropout, "seed", seed, "ids/byte", ids.numel() / text.numel()) if dropout else ()), flush=True)
     if spans:
         del out
         enc.encode_spans_device(text)  # first call: allocates the span scratch
