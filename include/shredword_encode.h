@@ -482,6 +482,105 @@ int64_t shred_window_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const
                           int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths, uint8_t* mask,
                           int32_t* win_row, int64_t* win_src, int64_t* row_win, size_t* widest);
 
+/* ---- row pairs to one model input on the GPU: two segments, one budget, token types ---------------
+ *
+ * The calls above take one row per example.  These take two (question and context, premise and
+ * hypothesis, prompt and response) and emit [bos] + kept_a + mid + kept_b + [eos].
+ *
+ * Inputs:
+ *   ids_a, row_a   n_a int32 with rows + 1 int64 offsets; ids_b, row_b: n_b int32 with rows + 1 int64
+ *               offsets.  Both offset arrays are in the line_off format (0 = row[0] <= ... <=
+ *               row[rows] = n, else -6) and neither may be NULL; they share the one row count.
+ *               Example r has la_r = row_a[r+1] - row_a[r] ids of a and lb_r ids of b.
+ *   bos, eos    each NULL for none, or a host pointer to one int32 id.
+ *   mid, mid_n  0 <= mid_n <= 2 ids between the segments (a host pointer; RoBERTa uses two).  Like
+ *               bos and eos they may be any int32 and are never looked up.
+ *               add = (bos != NULL) + mid_n + (eos != NULL).
+ *   max_len     0: unlimited, allowed for strategies 0 .. 2 only.  Otherwise B = max_len - add is the
+ *               budget of kept ids per emitted row; max_len < add returns -1.
+ *   trunc_side  0 keeps the first ids of a segment that is cut, 1 its last.
+ *   strategy    how a pair is made to fit, below; max_a and stride go with strategy 3 and must be 0
+ *               with the others.
+ *
+ * An emitted row is [bos] + kept_a + mid + kept_b + [eos], of length e = add + ka + kb.  Token
+ * types: bos, kept_a and mid have type 0, kept_b and eos type 1, padding type 0.
+ *
+ *   0  longest_first   while ka + kb > B, remove one id from the longer segment, from b on a tie.
+ *                      In closed form, with s = min(la, lb): if la + lb <= B both stay whole; else if
+ *                      2 s <= B the shorter stays whole and the longer keeps B - s; else
+ *                      ka = ceil(B / 2), kb = floor(B / 2).
+ *   1  only_first      kb = lb, ka = min(la, B - lb).  An example with lb > B cannot fit.
+ *   2  only_second     ka = la, kb = min(lb, B - la).  An example with la > B cannot fit.
+ *   3  window_second   the question-answering form; needs 0 < max_len <= INT32_MAX.  ka = la when
+ *                      max_a == 0, else min(la, max_a), cut on trunc_side.  b is never dropped: it is
+ *                      cut into windows of C_r = B - ka_r ids, step_r = C_r - stride apart, by the
+ *                      rule of shred_window_* (w_r = 1 if lb_r <= C_r, else 1 + ceil((lb_r - C_r) /
+ *                      step_r); window j holds the ids [j step_r, min(j step_r + C_r, lb_r)) of b; an
+ *                      empty b has one window).  Every window of example r carries the same kept_a.
+ *                      An example with C_r < stride + 1 cannot fit (ka_r > B included).  With
+ *                      max_a > 0 the call checks B - max_a >= stride + 1 once (-1), and then no
+ *                      example can fail.
+ *
+ * -7: some example cannot be made to fit by the strategy; nothing is written.  The device call finds
+ * it in its row pass, the host call before anything is staged.
+ *
+ * w_r is the number of emitted rows of example r (1 for strategies 0 .. 2), WO[r] the sum of w_r' over
+ * r' < r, Wn = WO[rows].  An example with both rows empty emits only the added ids (with add == 0:
+ * only padding), so every example is represented, as in pad and window.
+ *
+ * Outputs (width = W, pad_id, pad_side as in pad); all but out may be NULL:
+ *   out         [Wn, W] int32, row-major: emitted row w as pad writes an emitted row.
+ *   types       [Wn, W] uint8: the token types above.
+ *   mask        [Wn, W] uint8: 1 where a token sits, 0 where padding sits.
+ *   lengths     Wn int32: e of each emitted row.
+ *   win_row     Wn int32: the example r.  rows > INT32_MAX returns -1 when it is asked for.
+ *   seg_len     [Wn, 2] int32: (ka, kb) of the emitted row.
+ *   seg_src     [Wn, 2] int64: the index in ids_a of the first kept a id and the index in ids_b of the
+ *               first kept b id (for a segment that keeps nothing: the index at which it would begin).
+ *   row_win     rows + 1 int64: WO[0 .. rows]; example r owns the emitted rows [row_win[r], row_win[r+1]).
+ *   widest      NULL, or a host size_t that receives the largest e (0 for rows == 0).
+ *
+ * With bos_n = (bos != NULL): kept_a sits at the emitted positions [bos_n, bos_n + ka), and position c
+ * there holds ids_a[seg_src[w][0] + c - bos_n]; kept_b sits at [bos_n + ka + mid_n, bos_n + ka + mid_n
+ * + kb), and position c there holds ids_b[seg_src[w][1] + c - (bos_n + ka + mid_n)].  The same two
+ * indices into the starts arrays that shred_encode_docs returns for the two texts are those tokens'
+ * byte offsets: the offset mapping of a pair.
+ *
+ * Returns Wn.  Nothing is written but *widest if out is NULL, or width is smaller than *widest, or
+ * cap < Wn * width (cap counts int32 entries): the sizing call, only the length passes run.  With
+ * max_len > 0, width = max_len always suffices.  Errors, with nothing written at all: -1 bad
+ * argument (an unknown strategy; stride or max_a given with strategies 0 .. 2; strategy 3 without a
+ * max_len), HIP error, an e above INT32_MAX, or a Wn * width that does not fit an int64; -6 a bad
+ * row_a or row_b; -7 as above (-6 comes before -7, and -7 before an e above INT32_MAX).  (A HIP error
+ * after the first piece of shred_pair_rows leaves the earlier pieces' output in place.)
+ *
+ * The pair scratch (8 B per example for WO, the scan's temporaries, a pinned result word, events,
+ * and the host call's staging) is allocated on the first pair call and freed with the encoder, so
+ * the other calls' footprints are unchanged.
+ */
+
+/* All buffers on the encoder's device (row_a and row_b are validated there); stream, alignment
+ * (4 bytes; 1 for types and mask; 8 for the int64 outputs) and kernel_ms as shred_pad_device. */
+int64_t shred_pair_device(ShredEncoder* enc, const void* ids_a, size_t n_a, const void* row_a, const void* ids_b,
+                          size_t n_b, const void* row_b, size_t rows, const int32_t* bos, const int32_t* mid,
+                          size_t mid_n, const int32_t* eos, size_t max_len, int trunc_side, int strategy, size_t max_a,
+                          size_t stride, size_t width, int32_t pad_id, int pad_side, void* out, size_t cap, void* types,
+                          void* mask, void* lengths, void* win_row, void* seg_len, void* seg_src, void* row_win,
+                          size_t* widest, void* stream, double* kernel_ms);
+
+/* Host buffers; the offset arrays, the examples that cannot fit, Wn and the widest emitted row are
+ * settled on the host before anything is staged.  Staged like shred_window_rows in pieces of whole
+ * examples: a piece takes examples while its ids of a plus its ids of b, its examples and its output
+ * entries (emitted rows * width, at most 4 per id of the budget) stay within the piece budget of the
+ * batch calls, and one example is taken whole, however long.  A piece writes its own emitted rows of
+ * every output. */
+int64_t shred_pair_rows(ShredEncoder* enc, const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b,
+                        size_t n_b, const int64_t* row_b, size_t rows, const int32_t* bos, const int32_t* mid,
+                        size_t mid_n, const int32_t* eos, size_t max_len, int trunc_side, int strategy, size_t max_a,
+                        size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap,
+                        uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row, int32_t* seg_len,
+                        int64_t* seg_src, int64_t* row_win, size_t* widest);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -1,7 +1,8 @@
 // Rows of token ids to rectangular model inputs on gfx950: padded batches, packed sequences and
 // overlapping windows of long rows (C ABI and definitions: include/shredword_encode.h,
 // shred_pad_* / shred_pack_* / shred_window_*).  The passes use
-// none of the encoder's or the decoder's kernels.
+// none of the encoder's or the decoder's kernels.  The pair form (shred_pair_*) is batch_pair.hip;
+// what the two units share is batch_common.h.
 //
 // Row r keeps keep_r of its len_r ids (from either end) and emits e_r = add + keep_r ids: an
 // optional bos, the kept ids, an optional eos.  E is the exclusive prefix sum of e_r, E[rows] = T.
@@ -74,6 +75,7 @@
 #include <vector>
 
 #include "../host/encoder.h"
+#include "batch_common.h"
 #include "encode_common.h"
 
 namespace shred {
@@ -90,14 +92,6 @@ struct BatchCall {
   uint64_t base;       // pack: stream offset of the call's first row (ids of the pieces before)
   uint64_t row_base;   // pack: index of the call's first row
 };
-
-typedef uint64_t u64;
-
-constexpr int kThreads = 256;
-constexpr int kLane = 4;                   // int32 entries per lane: one 16-byte store
-constexpr int kTile = kThreads * kLane;    // output entries per workgroup (BATCH_TILE)
-constexpr int kStage = 512;                // rows staged in LDS per round (BATCH_STAGE)
-constexpr u64 kNoLimit = ~0ull;
 
 // How a row turns into its emitted row; passed to the kernels and the hipCUB iterators by value.
 struct Rows {
@@ -222,12 +216,6 @@ __global__ __launch_bounds__(kThreads) void k_bat_pad(const int32_t* __restrict_
         if (i < cnt) mask[g + i] = (uint8_t)(mk >> (8 * i));
     }
   }
-}
-
-__global__ __launch_bounds__(kThreads) void k_bat_row_start(const u64* __restrict__ E, u64 rows, u64 base,
-                                                            int64_t* __restrict__ row_start) {
-  const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
-  if (r <= rows) row_start[r] = (int64_t)(base + E[r]);
 }
 
 // Positions [0, limit) of the call's stream (E[rows] = T; positions from T on are padding);
@@ -362,25 +350,6 @@ struct WOInput {
 };
 typedef hipcub::TransformInputIterator<u64, WOInput, hipcub::CountingInputIterator<u64>> WOIter;
 
-// upper_bound by the 64 lanes of one wave (all active): a step probes 64 entries spread over
-// [lo, hi), so a search of 2^24 entries takes 4 rounds of loads instead of 24.
-__device__ __forceinline__ u64 wave_upper_bound(const u64* __restrict__ E, u64 lo, u64 hi, u64 v, int lane) {
-  while (lo < hi) {
-    const u64 gap = (hi - lo) / 64 + 1;
-    const u64 k = lo + (u64)lane * gap;
-    // E does not decrease: the lanes that see an entry <= v are the first `le`
-    const u64 le = (u64)__popcll(__ballot(k < hi && E[k] <= v));
-    if (le == 0) {
-      hi = lo;
-    } else {
-      const u64 next = lo + le * gap;
-      lo += (le - 1) * gap + 1;
-      hi = next < hi ? next : hi;
-    }
-  }
-  return lo;
-}
-
 // total = Wn * W > 0, W >= every window's length; WO: rows + 1 entries, strictly increasing from 0
 // to Wn.  Window w of the call goes to out[w * W ..], lengths[w], win_row[w], win_src[w].
 template <bool kAligned>
@@ -507,16 +476,6 @@ __global__ __launch_bounds__(kThreads) void k_bat_window_meta(Rows rw, u64 rows,
   if (lengths) lengths[r] = 0;
   if (win_row) win_row[r] = (int32_t)(row_base + r);
   if (win_src) win_src[r] = (int64_t)(id_base + a);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Grids are one workgroup per tile / 256 rows.
-bool rows_fit(u64 rows) { return rows / kThreads < 0x7FFFFFFFull; }
-bool tiles_fit(u64 entries) { return entries / kTile < 0x7FFFFFFFull; }
-
-size_t piece_ids() {
-  return std::min(piece_from_env("SHREDWORD_BATCH_PIECE", EncodeDevice::kBatchPiece, 1), size_t(1) << 40);
 }
 
 // The rows [r0, r1) of a piece: whole rows while it holds at most `piece` ids, `piece` rows and

@@ -532,4 +532,60 @@ int64_t shred_window_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const
   return r < 0 ? r : (int64_t)Wn;
 }
 
+namespace {
+// What the two pair calls refuse before any work (0 or -1), and their options.
+int pair_args(const ShredEncoder* enc, const void* ids_a, size_t n_a, const void* row_a, const void* ids_b, size_t n_b,
+              const void* row_b, size_t rows, const int32_t* bos, const int32_t* mid, size_t mid_n, const int32_t* eos,
+              size_t max_len, int trunc_side, int strategy, size_t max_a, size_t stride, int pad_side,
+              const void* win_row, shred::EncodeDevice::PairOpts* o) {
+  if (!enc || (n_a && !ids_a) || (n_b && !ids_b) || !row_a || !row_b || trunc_side < 0 || trunc_side > 1 ||
+      pad_side < 0 || pad_side > 1 || mid_n > 2 || (mid_n && !mid) || strategy < 0 || strategy > 3)
+    return -1;
+  const size_t add = (bos ? 1 : 0) + mid_n + (eos ? 1 : 0);
+  if (max_len && max_len < add) return -1;
+  if (strategy != 3 && (stride || max_a)) return -1;
+  if (strategy == 3) {
+    if (!max_len || max_len > (size_t)INT32_MAX) return -1;
+    const size_t B = max_len - add;
+    if (max_a && (B < max_a || B - max_a <= stride)) return -1;
+  }
+  if (win_row && rows > (size_t)INT32_MAX) return -1;
+  *o = shred::EncodeDevice::PairOpts{bos != nullptr, eos != nullptr, bos ? *bos : 0, eos ? *eos : 0,
+                                     {mid_n > 0 ? mid[0] : 0, mid_n > 1 ? mid[1] : 0}, (uint32_t)mid_n,
+                                     (uint64_t)max_len, trunc_side, strategy, (uint64_t)max_a, (uint64_t)stride};
+  return 0;
+}
+}  // namespace
+
+int64_t shred_pair_device(ShredEncoder* enc, const void* ids_a, size_t n_a, const void* row_a, const void* ids_b,
+                          size_t n_b, const void* row_b, size_t rows, const int32_t* bos, const int32_t* mid,
+                          size_t mid_n, const int32_t* eos, size_t max_len, int trunc_side, int strategy, size_t max_a,
+                          size_t stride, size_t width, int32_t pad_id, int pad_side, void* out, size_t cap, void* types,
+                          void* mask, void* lengths, void* win_row, void* seg_len, void* seg_src, void* row_win,
+                          size_t* widest, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::PairOpts o;
+  if (pair_args(enc, ids_a, n_a, row_a, ids_b, n_b, row_b, rows, bos, mid, mid_n, eos, max_len, trunc_side, strategy,
+                max_a, stride, pad_side, win_row, &o))
+    return -1;
+  return enc->dev->pair((const int32_t*)ids_a, n_a, (const int64_t*)row_a, (const int32_t*)ids_b, n_b,
+                        (const int64_t*)row_b, rows, o, width, pad_id, pad_side, (int32_t*)out, cap, (uint8_t*)types,
+                        (uint8_t*)mask, (int32_t*)lengths, (int32_t*)win_row, (int32_t*)seg_len, (int64_t*)seg_src,
+                        (int64_t*)row_win, widest, stream, kernel_ms);
+}
+
+int64_t shred_pair_rows(ShredEncoder* enc, const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b,
+                        size_t n_b, const int64_t* row_b, size_t rows, const int32_t* bos, const int32_t* mid,
+                        size_t mid_n, const int32_t* eos, size_t max_len, int trunc_side, int strategy, size_t max_a,
+                        size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap,
+                        uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row, int32_t* seg_len,
+                        int64_t* seg_src, int64_t* row_win, size_t* widest) {
+  shred::EncodeDevice::PairOpts o;
+  if (pair_args(enc, ids_a, n_a, row_a, ids_b, n_b, row_b, rows, bos, mid, mid_n, eos, max_len, trunc_side, strategy,
+                max_a, stride, pad_side, win_row, &o))
+    return -1;
+  return enc->dev->pair_host(ids_a, n_a, row_a, ids_b, n_b, row_b, rows, o, width, pad_id, pad_side, out, cap, types,
+                             mask, lengths, win_row, seg_len, seg_src, row_win, widest);
+}
+
 }  // extern "C"

@@ -171,6 +171,29 @@ class EncodeDevice {
                   size_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths, uint8_t* mask,
                   int32_t* win_row, int64_t* win_src, int64_t* row_win);
 
+  // ---- row pairs to one model input (batch_pair.hip; shred_pair_*).  The callers have checked the
+  // arguments' ranges: mid_n <= 2, strategy in 0 .. 3, max_len == 0 or >= the added ids; strategies
+  // 0 .. 2 come with max_a == stride == 0, strategy 3 with 0 < max_len <= INT32_MAX.  pair takes
+  // device buffers, pair_host host buffers (it settles row_a / row_b, the rows that cannot fit, Wn and
+  // the widest row on the host before anything is staged); both return Wn, -1, -6 or -7, with the
+  // longest emitted row in *widest.
+  struct PairOpts {
+    bool has_bos, has_eos;
+    int32_t bos, eos, mid[2];
+    uint32_t mid_n;
+    uint64_t max_len;  // 0: unlimited
+    int trunc_side, strategy;
+    uint64_t max_a, stride;
+  };
+  int64_t pair(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b, size_t n_b,
+               const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id, int pad_side,
+               int32_t* out, size_t cap, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row,
+               int32_t* seg_len, int64_t* seg_src, int64_t* row_win, size_t* widest, void* stream, double* kernel_ms);
+  int64_t pair_host(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b, size_t n_b,
+                    const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id, int pad_side,
+                    int32_t* out, size_t cap, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row,
+                    int32_t* seg_len, int64_t* seg_src, int64_t* row_win, size_t* widest);
+
  private:
   EncodeDevice() = default;
   // Span passes over n text bytes and their T ids (both on the device): starts[k] = start_base +
@@ -208,7 +231,7 @@ class EncodeDevice {
   bool sx_dirty_ = false;          // the scan table on the device is older than the set
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
-  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPasses };
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -214,3 +214,14 @@ lib.shred_window_device.argtypes = _window_rows + [c_void_p, POINTER(c_double)]
 lib.shred_window_device.restype = c_int64
 lib.shred_window_rows.argtypes = _window_rows
 lib.shred_window_rows.restype = c_int64
+# row pairs to one model input: ids_a, n_a, row_a, ids_b, n_b, row_b, rows, bos, mid, mid_n, eos, max_len, trunc_side,
+# strategy, max_a, stride, width, pad_id, pad_side, out, cap, types, mask, lengths, win_row, seg_len, seg_src, row_win,
+# widest
+_pair_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_int32),
+              POINTER(c_int32), c_size_t, POINTER(c_int32), c_size_t, c_int, c_int, c_size_t, c_size_t, c_size_t,
+              c_int32, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+              POINTER(c_size_t)]
+lib.shred_pair_device.argtypes = _pair_rows + [c_void_p, POINTER(c_double)]
+lib.shred_pair_device.restype = c_int64
+lib.shred_pair_rows.argtypes = _pair_rows
+lib.shred_pair_rows.restype = c_int64

@@ -29,6 +29,8 @@ DECODE_CHUNK = 4096
 # pack and window kernels stage in LDS per round (kStage)
 BATCH_TILE = 1024
 BATCH_STAGE = 512
+# batch_pair.hip: the strategies of shred_pair_*, by number
+PAIR_TRUNCATION = ("longest_first", "only_first", "only_second", "window_second")
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -686,6 +688,154 @@ class BPEEncoder:
         a list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): every document is."""
         ids, row = self._encode_rows(text, specials, doc_offsets)
         return self.window_rows(ids, row, **kw)
+
+    # ---- row pairs to one model input (include/shredword_encode.h, shred_pair_*) -------------------
+
+    @classmethod
+    def _pair_args(cls, max_len, truncation, stride, max_first, bos, sep, eos, truncate, pad_id, pad):
+        """-> (bos, mid, mid_n, eos, max_len, trunc_side, strategy, max_a, stride) as the C ABI takes them, then
+        (pad_id, pad_side)."""
+        if pad not in ("left", "right"):
+            raise ValueError('pad must be "left" or "right"')
+        if truncate not in ("left", "right"):
+            raise ValueError('truncate must be "left" or "right"')
+        if truncation not in PAIR_TRUNCATION:
+            raise ValueError(f"truncation must be one of {PAIR_TRUNCATION}")
+        sep = (sep,) if isinstance(sep, (int, np.integer)) else tuple(sep)
+        if len(sep) > 2:
+            raise ValueError("sep holds at most two ids")
+        add = (bos is not None) + len(sep) + (eos is not None)
+        ml = 0 if max_len is None else int(max_len)
+        if ml < 0 or (ml and ml < add):
+            raise ValueError(f"max_len must leave room for the {add} added ids")
+        sd, mf = int(stride), 0 if max_first is None else int(max_first)
+        if sd < 0 or mf < 0:
+            raise ValueError("stride and max_first must not be negative")
+        if truncation == "window_second":
+            if not 0 < ml < 2 ** 31:
+                raise ValueError("window_second needs a max_len, and one that fits an int32")
+            if mf and ml - add - mf < sd + 1:
+                raise ValueError(f"max_len - {add} - max_first must be at least stride + 1: a window must move on by "
+                                 "at least one id")
+        elif sd or mf:
+            raise ValueError("stride and max_first go with truncation=\"window_second\"")
+        ptr = lambda name, v: None if v is None else ctypes.byref(ctypes.c_int32(cls._int32(name, v)))
+        mid = (ctypes.c_int32 * 2)(*[cls._int32("sep", v) for v in sep]) if sep else None
+        return (ptr("bos", bos), mid, len(sep), ptr("eos", eos), ml, int(truncate == "left"),
+                PAIR_TRUNCATION.index(truncation), mf, sd), (cls._int32("pad_id", pad_id), int(pad == "left"))
+
+    @classmethod
+    def _check_pair(cls, r: int) -> int:
+        if r == -7:
+            raise ValueError("a pair cannot be made to fit max_len by this truncation (the segment that is never cut "
+                             "is too long)")
+        if r == -6:
+            raise ValueError("row offsets must be 0 = row[0] <= ... <= row[rows] = len(ids), for both segments")
+        return cls._check_batch(r)
+
+    def pair_rows(self, ids_a, row_a, ids_b, row_b, *, max_len=None, truncation="longest_first", stride=0,
+                  max_first=None, bos=None, sep=(), eos=None, truncate="right", pad_id=0, pad="right", width=None,
+                  mask=False, types=True):
+        """-> (batch, lengths, pair_rows, seg_len, seg_src, row_windows[, types][, mask]): example r is the pair of
+        ids_a[row_a[r]:row_a[r + 1]] and ids_b[row_b[r]:row_b[r + 1]] (both offset arrays in the line_offsets
+        format, rows + 1 entries each), emitted as [bos] + kept_a + sep + kept_b + [eos] (sep: up to two ids).
+        max_len (None: no limit) bounds an emitted row, the added ids included.  truncation: "longest_first"
+        removes ids from the longer segment (from the second on a tie) until the pair fits; "only_first" /
+        "only_second" cut that segment alone (ValueError when the other is too long on its own);
+        "window_second" keeps the first segment (its first max_first ids, None: all) in every emitted row and
+        cuts the second into windows that overlap by `stride` ids, as window_rows does (the question-answering
+        form).  truncate: the side of a cut segment that is dropped.
+        batch: int32 [emitted, width] (width None: the longest emitted row), padded with pad_id on the `pad`
+        side; lengths: int32 [emitted]; pair_rows: int32 [emitted], the example of each emitted row; seg_len:
+        int32 [emitted, 2], (ka, kb); seg_src: int64 [emitted, 2], the index in ids_a / ids_b of the first kept
+        id of each segment (the same index into the starts of encode_docs is that token's byte offset);
+        row_windows: int64 [rows + 1], example r owns the emitted rows [row_windows[r], row_windows[r + 1]);
+        types: uint8 [emitted, width], 1 on kept_b and eos; mask: uint8 [emitted, width], 1 on tokens.
+        Built on the GPU."""
+        head, (pid, ps) = self._pair_args(max_len, truncation, stride, max_first, bos, sep, eos, truncate, pad_id, pad)
+        if row_a is None or row_b is None:
+            raise ValueError("row_a and row_b must hold rows + 1 entries")
+        a, ra, R = self._host_rows(ids_a, row_a)
+        b, rb, Rb = self._host_rows(ids_b, row_b)
+        if R != Rb:
+            raise ValueError("row_a and row_b must hold the same number of rows")
+        args = (self.enc, a.ctypes.data, a.size, ra.ctypes.data, b.ctypes.data, b.size, rb.ctypes.data, R) + head
+        widest = ctypes.c_size_t()
+        Wn = self._check_pair(lib.shred_pair_rows(*args, 0, pid, ps, None, 0, None, None, None, None, None, None, None,
+                                                  ctypes.byref(widest)))
+        W = widest.value if width is None else int(width)
+        if W < widest.value:
+            raise ValueError(f"width {W} is smaller than the longest emitted row ({widest.value} ids)")
+        out = np.empty(max(1, Wn * W), dtype=np.int32)
+        lengths, wrow = (np.empty(max(1, Wn), dtype=np.int32) for _ in range(2))
+        slen = np.empty(max(1, 2 * Wn), dtype=np.int32)
+        ssrc = np.empty(max(1, 2 * Wn), dtype=np.int64)
+        roww = np.empty(R + 1, dtype=np.int64)
+        t = np.empty(max(1, Wn * W), dtype=np.uint8) if types else None
+        m = np.empty(max(1, Wn * W), dtype=np.uint8) if mask else None
+        self._check_pair(lib.shred_pair_rows(*args, W, pid, ps, out.ctypes.data, Wn * W,
+                                             None if t is None else t.ctypes.data, None if m is None else m.ctypes.data,
+                                             lengths.ctypes.data, wrow.ctypes.data, slen.ctypes.data, ssrc.ctypes.data,
+                                             roww.ctypes.data, None))
+        res = (out[:Wn * W].reshape(Wn, W), lengths[:Wn], wrow[:Wn], slen[:2 * Wn].reshape(Wn, 2),
+               ssrc[:2 * Wn].reshape(Wn, 2), roww)
+        res += (t[:Wn * W].reshape(Wn, W),) if types else ()
+        return res + ((m[:Wn * W].reshape(Wn, W),) if mask else ())
+
+    def pair_device(self, ids_a, row_a, ids_b, row_b, *, max_len=None, truncation="longest_first", stride=0,
+                    max_first=None, bos=None, sep=(), eos=None, truncate="right", pad_id=0, pad="right", width=None,
+                    mask=False, types=True, stream=None):
+        """pair_rows on device tensors (ids 1-D int32, offsets 1-D int64, on the encoder's GPU) -> (batch, lengths,
+        pair_rows, seg_len, seg_src, row_windows[, types][, mask], device milliseconds of the pair passes)."""
+        import torch
+        head, (pid, ps) = self._pair_args(max_len, truncation, stride, max_first, bos, sep, eos, truncate, pad_id, pad)
+        if row_a is None or row_b is None:
+            raise ValueError("row_a and row_b must hold rows + 1 entries")
+        R = self._device_rows(ids_a, row_a)
+        if R != self._device_rows(ids_b, row_b):
+            raise ValueError("row_a and row_b must hold the same number of rows")
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids_a.device).cuda_stream)
+        args = (self.enc, ids_a.data_ptr(), ids_a.numel(), row_a.data_ptr(), ids_b.data_ptr(), ids_b.numel(),
+                row_b.data_ptr(), R) + head
+        widest, ms = ctypes.c_size_t(), ctypes.c_double()
+        Wn = self._check_pair(lib.shred_pair_device(*args, 0, pid, ps, None, 0, None, None, None, None, None, None,
+                                                    None, ctypes.byref(widest), st, None))
+        W = widest.value if width is None else int(width)
+        if W < widest.value:
+            raise ValueError(f"width {W} is smaller than the longest emitted row ({widest.value} ids)")
+        new = lambda dt, k: torch.empty(max(1, k), dtype=dt, device=ids_a.device)
+        out, lengths, wrow = new(torch.int32, Wn * W), new(torch.int32, Wn), new(torch.int32, Wn)
+        slen, ssrc, roww = new(torch.int32, 2 * Wn), new(torch.int64, 2 * Wn), new(torch.int64, R + 1)
+        t = new(torch.uint8, Wn * W) if types else None
+        m = new(torch.uint8, Wn * W) if mask else None
+        self._check_pair(lib.shred_pair_device(*args, W, pid, ps, out.data_ptr(), Wn * W,
+                                               None if t is None else t.data_ptr(), None if m is None else m.data_ptr(),
+                                               lengths.data_ptr(), wrow.data_ptr(), slen.data_ptr(), ssrc.data_ptr(),
+                                               roww.data_ptr(), None, st, ctypes.byref(ms)))
+        res = (out[:Wn * W].view(Wn, W), lengths[:Wn], wrow[:Wn], slen[:2 * Wn].view(Wn, 2), ssrc[:2 * Wn].view(Wn, 2),
+               roww)
+        res += (t[:Wn * W].view(Wn, W),) if types else ()
+        return res + ((m[:Wn * W].view(Wn, W),) if mask else ()) + (ms.value,)
+
+    def encode_pairs(self, texts_a, texts_b, *, starts: bool = False, specials: bool = False, **kw):
+        """Two equally long sequences of bytes / str documents -> pair_device(**kw) of their ids: both lists are
+        encoded on the GPU as encode_docs_device encodes them (one row per document) and the ids stay there.
+        Returns pair_device's tuple (torch tensors on the encoder's device, then the device milliseconds); with
+        starts=True two more int64 tensors follow, the byte offset of every token of texts_a in the joined texts_a
+        (join_docs) and the same for texts_b: seg_src indexes them."""
+        import torch
+        if len(texts_a) != len(texts_b):
+            raise ValueError("texts_a and texts_b must hold the same number of documents")
+        sides = []
+        for texts in (texts_a, texts_b):
+            buf, off = join_docs(texts)
+            d_buf = torch.from_numpy(buf.copy()).cuda(self.device)
+            ids, row, st, _ = self.encode_docs_device(d_buf, torch.from_numpy(off).cuda(self.device), starts=starts,
+                                                      specials=specials)
+            sides.append((ids, row, st))
+        (ia, ra, sa), (ib, rb, sb) = sides
+        res = self.pair_device(ia, ra, ib, rb, **kw)
+        return res + ((sa, sb) if starts else ())
 
     def destroy(self):
         if getattr(self, "enc", None):
