@@ -1,6 +1,6 @@
-// What the batch units (batch_device.hip, batch_pair.hip) share: the tile geometry of their
-// output-centric kernels, the search of a prefix sum by one wave, the kernel that writes a prefix
-// sum out as int64, and the limits of their grids and host pieces.
+// What the batch units (batch_device.hip, batch_pair.hip) share on the device: the tile geometry of
+// their output-centric kernels, the search of a prefix sum by one wave, the kernel that writes a
+// prefix sum out as int64, and the limit of their grids.  The host side they share is batch_state.h.
 // Included by .hip files only.
 #pragma once
 
@@ -20,7 +20,6 @@ constexpr int kThreads = 256;
 constexpr int kLane = 4;                   // int32 entries per lane: one 16-byte store
 constexpr int kTile = kThreads * kLane;    // output entries per workgroup (BATCH_TILE)
 constexpr int kStage = 512;                // rows staged in LDS per round (BATCH_STAGE)
-constexpr u64 kNoLimit = ~0ull;
 
 __global__ __launch_bounds__(kThreads) void k_bat_row_start(const u64* __restrict__ E, u64 rows, u64 base,
                                                             int64_t* __restrict__ row_start) {
@@ -49,13 +48,9 @@ __device__ __forceinline__ u64 wave_upper_bound(const u64* __restrict__ E, u64 l
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Grids are one workgroup per tile / 256 rows.
-bool rows_fit(u64 rows) { return rows / kThreads < 0x7FFFFFFFull; }
+// Grids are one workgroup per tile (per 256 rows: batch_rows_fit, host/encoder.h).
+static_assert(kThreads == (int)kBatchRowsPerGroup, "batch_rows_fit assumes the row kernels' workgroup");
 bool tiles_fit(u64 entries) { return entries / kTile < 0x7FFFFFFFull; }
-
-size_t piece_ids() {
-  return std::min(piece_from_env("SHREDWORD_BATCH_PIECE", EncodeDevice::kBatchPiece, 1), size_t(1) << 40);
-}
 
 }  // namespace
 }  // namespace shred

@@ -2,29 +2,29 @@
 // overlapping windows of long rows (C ABI and definitions: include/shredword_encode.h,
 // shred_pad_* / shred_pack_* / shred_window_*).  The passes use
 // none of the encoder's or the decoder's kernels.  The pair form (shred_pair_*) is batch_pair.hip;
-// what the two units share is batch_common.h.
+// what the two units share is batch_common.h (device: tile geometry, the wave search) and
+// batch_state.h (host: the length pass, the device-call driver, the host piece loop).
 //
 // Row r keeps keep_r of its len_r ids (from either end) and emits e_r = add + keep_r ids: an
 // optional bos, the kept ids, an optional eos.  E is the exclusive prefix sum of e_r, E[rows] = T.
 //
 //   k_bat_rows       one thread per row_off entry: range, order and end points, and e_r <= INT32_MAX
 //                    (error words, ordinary stores, no atomics);
-//   hipCUB scan      pack only: inclusive sum over k = 0 .. rows of (k ? e_{k-1} : 0) through a
-//                    transform iterator on row_off: E[0 .. rows];
-//   hipCUB reduce    pad only: the maximum of e_r through the same kind of iterator (the width needed);
+//   hipCUB scan      pack only: E[0 .. rows] (batch_state.h);
+//   hipCUB reduce    pad only: the maximum of e_r (the width needed);
 //   k_bat_pad        output-centric: one workgroup per kTile consecutive entries of the flat [rows, W]
 //                    array, 4 consecutive entries per lane.  The 64-bit (r, c) split of a lane's first
 //                    entry is done once and then walked (++c, a new row's offsets at c == W), so a
 //                    lane's entries may straddle rows.  The lane that owns c == 0 writes lengths[r];
-//                    the mask bytes come from the same walk.  Pad needs no E: entry (r, c) depends
-//                    on row r alone;
+//                    the mask bytes come from the same walk.  Pad needs no E and no staging: entry
+//                    (r, c) depends on row r alone;
 //   k_bat_row_start  pack: row_start[r] = base + E[r];
-//   k_bat_pack       one workgroup per kTile stream positions.  Its first row by a binary search of
-//                    E: the last r with E[r] <= the tile's first position, which skips the rows that
-//                    emit nothing.  Rounds of kStage rows staged in LDS (E relative to the tile, e_r,
-//                    the index in ids of the row's emitted id 0); every lane makes 4 consecutive
-//                    positions: a binary search of the LDS offsets for the row under its first
-//                    position, then a forward walk.  A round resolves the positions below the E of
+//   k_bat_pack       stream-centric: one workgroup per kTile stream positions.  Its first row by a
+//                    binary search of E: the last r with E[r] <= the tile's first position, which skips
+//                    the rows that emit nothing.  Rounds of kStage rows staged in LDS (E relative to the
+//                    tile, e_r, the index in ids of the row's emitted id 0); every lane makes 4
+//                    consecutive positions: a binary search of the LDS offsets for the row under its
+//                    first position, then a forward walk.  A round resolves the positions below the E of
 //                    the first row it did not stage, so a tile with more rows than kStage (rows that
 //                    emit nothing, rows of one id) takes more rounds, and a row longer than a tile
 //                    needs no special case.  Entry `rows` of E is staged as a row that emits nothing:
@@ -66,16 +66,14 @@
 // only element-aligned (tensor views), so the 16-byte (mask: 4-byte) stores have a scalar form.
 #include <hip/hip_runtime.h>
 
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "../host/encoder.h"
 #include "batch_common.h"
+#include "batch_state.h"
 #include "encode_common.h"
 
 namespace shred {
@@ -89,8 +87,9 @@ struct BatchCall {
   uint64_t rows;
   bool ends;           // check row[0] == 0 and row[rows] == n (a piece's local offsets: no)
   EncodeDevice::BatchOpts o;
-  uint64_t base;       // pack: stream offset of the call's first row (ids of the pieces before)
-  uint64_t row_base;   // pack: index of the call's first row
+  uint64_t base;       // pack: stream offset of the call's first row (ids of the pieces before);
+                       // window: index in the call's ids of the piece's first id
+  uint64_t row_base;   // index of the call's first row
 };
 
 // How a row turns into its emitted row; passed to the kernels and the hipCUB iterators by value.
@@ -143,7 +142,16 @@ __global__ __launch_bounds__(kThreads) void k_bat_rows(Rows rw, u64 rows, int en
   if (r && prev >= 0 && (u64)(rw.bos_n + rw.eos_n) + rw.keep((u64)prev, (u64)v) > (u64)INT32_MAX) err[1] = 1;
 }
 
-// Element k of the scan: the length of emitted row k - 1.
+// The row pass of the pad, pack and window calls (0 or -1).
+int row_pass(const Rows& rw, const BatchCall& c, u64* err, hipStream_t st) {
+  if (!c.row) return rw.emit(0) > (u64)INT32_MAX ? -1 : 0;
+  k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(rw, c.rows, c.ends ? 1 : 0,
+                                                                                          err);
+  ENC_OK(hipGetLastError());
+  return 0;
+}
+
+// Element k of the scan: the length of emitted row k - 1; element r of the reduction: that of row r.
 struct EInput {
   Rows rw;
   __host__ __device__ __forceinline__ u64 operator()(u64 k) const { return k ? rw.emit(k - 1) : 0ull; }
@@ -152,8 +160,6 @@ struct WInput {
   Rows rw;
   __host__ __device__ __forceinline__ u64 operator()(u64 r) const { return rw.emit(r); }
 };
-typedef hipcub::TransformInputIterator<u64, EInput, hipcub::CountingInputIterator<u64>> EIter;
-typedef hipcub::TransformInputIterator<u64, WInput, hipcub::CountingInputIterator<u64>> WIter;
 
 // First k in [lo, hi) with E[k] > v, or hi.
 __device__ __forceinline__ u64 upper_bound(const u64* __restrict__ E, u64 lo, u64 hi, u64 v) {
@@ -348,7 +354,6 @@ struct WOInput {
   Windows wn;
   __host__ __device__ __forceinline__ u64 operator()(u64 k) const { return k ? wn.count(k - 1) : 0ull; }
 };
-typedef hipcub::TransformInputIterator<u64, WOInput, hipcub::CountingInputIterator<u64>> WOIter;
 
 // total = Wn * W > 0, W >= every window's length; WO: rows + 1 entries, strictly increasing from 0
 // to Wn.  Window w of the call goes to out[w * W ..], lengths[w], win_row[w], win_src[w].
@@ -478,16 +483,6 @@ __global__ __launch_bounds__(kThreads) void k_bat_window_meta(Rows rw, u64 rows,
   if (win_src) win_src[r] = (int64_t)(id_base + a);
 }
 
-// The rows [r0, r1) of a piece: whole rows while it holds at most `piece` ids, `piece` rows and
-// 4 x piece output entries at per_row entries a row; at least one row, however long.
-size_t piece_end(const int64_t* row, size_t rows, size_t r0, size_t piece, size_t per_row) {
-  size_t r1 = r0 + 1;
-  while (r1 < rows && r1 - r0 < piece && (u64)(row[r1 + 1] - row[r0]) <= (u64)piece &&
-         (r1 + 1 - r0) * per_row <= 4 * piece)
-    ++r1;
-  return r1;
-}
-
 // Pad needs no state: entry (r, c) depends on row r alone.
 int pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
                uint8_t* mask, hipStream_t st) {
@@ -505,61 +500,28 @@ int pad_expand(const BatchCall& c, uint64_t width, int32_t pad_id, int pad_side,
   return 0;
 }
 
-// The batch passes' state, allocated on the first pad / pack call.  Scratch grown to the most rows
-// seen: 8 B per row (E) and what the scan and the reduction ask for.
-struct BatchState : PassState {
-  DeviceBuf<u64> e;            // E[r]: stream offset of emitted row r; E[rows] = T
-  DeviceBuf<uint8_t> tmp;      // hipCUB scan / reduce scratch
-  DeviceWords res;             // [0] bad row_off, [1] an e_r past int32, [2] max e_r
-  PinnedWords host;            // T, then the three words of res
-  EventSet<4> ev;
+// The batch passes' state, allocated on the first pad / pack call: the length pass (sum is E) and
+// the staging of the pad, pack and window host paths.
+struct BatchState : LengthState {
   // host-path staging: ids; row offsets then row_start (2 x hrow.cap()); a piece's int32 outputs:
-  // out, then pos / lengths, then seg (3 x hout.cap()); its mask
+  // out, then pos / lengths, then seg / win_row (3 x hout.cap()); its mask
   DeviceBuf<int32_t> hids;
   DeviceBuf<int64_t> hrow;
   DeviceBuf<int32_t> hout;
   DeviceBuf<uint8_t> hmask;
 
   bool reserve(size_t rows) {
-    if (!res.ensure(4) || !host.ensure(4) || !ev.ensure() || !e.grow(rows + 1)) return false;
     const Rows rw{nullptr, 0, kNoLimit, 0, 0, 0, 0, 0};
-    size_t scan = 0, red = 0;
-    if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
-                                         e.get(), (u64)rows + 1) != hipSuccess)
-      return false;
-    if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
-                                  res.get() + 2, (u64)std::max<size_t>(rows, 1)) != hipSuccess)
-      return false;
-    return tmp.grow(std::max<size_t>(std::max(scan, red), 16));
+    return LengthState::reserve(rows, row_iter(EInput{rw}), row_iter(WInput{rw}));
   }
 
-  // Row checks (when c.row), E into e (when scan) and max e_r over c's rows: 0, -1, -6.
+  // Row checks (when c.row), then E into sum (scan) or the maximum of e_r over c's rows: 0, -1, -6.
   int lengths(const BatchCall& c, bool scan, hipStream_t st, uint64_t* total, uint64_t* widest) {
     const Rows rw = rows_of(c.o, c.row, c.n);
-    ENC_OK(hipMemsetAsync(res.get(), 0, 32, st));
-    if (c.row) {
-      k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(rw, c.rows,
-                                                                                              c.ends ? 1 : 0, res.get());
-      ENC_OK(hipGetLastError());
-    } else if (rw.emit(0) > (u64)INT32_MAX) {
-      return -1;
-    }
-    size_t bytes = tmp.cap();
-    if (scan) {
-      ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, EIter(hipcub::CountingInputIterator<u64>(0), EInput{rw}),
-                                              e.get(), c.rows + 1, st));
-      ENC_OK(hipMemcpyAsync(host.get(), e.get() + c.rows, 8, hipMemcpyDeviceToHost, st));
-    } else if (c.rows) {
-      ENC_OK(hipcub::DeviceReduce::Max(tmp.get(), bytes, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
-                                       res.get() + 2, c.rows, st));
-    }
-    ENC_OK(hipMemcpyAsync(host.get() + 1, res.get(), 24, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (host[1]) return -6;
-    if (host[2]) return -1;
-    *total = scan ? host[0] : 0;
-    *widest = host[3];
-    return 0;
+    const auto scan_in = row_iter(EInput{rw});
+    const auto max_in = row_iter(WInput{rw});
+    return measure(c.rows, [&](u64* err) { return row_pass(rw, c, err, st); }, scan ? &scan_in : nullptr,
+                   scan ? nullptr : &max_in, st, total, widest);
   }
 
   // Stream positions [c.base, c.base + limit) into out / pos / seg (which point at position
@@ -567,7 +529,7 @@ struct BatchState : PassState {
   int pack_expand(const BatchCall& c, uint64_t limit, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg,
                   int64_t* row_start, hipStream_t st) {
     if (row_start) {
-      k_bat_row_start<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(e.get(), c.rows,
+      k_bat_row_start<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(sum.get(), c.rows,
                                                                                                    c.base, row_start);
       ENC_OK(hipGetLastError());
     }
@@ -575,64 +537,48 @@ struct BatchState : PassState {
       const Rows rw = rows_of(c.o, c.row, c.n);
       const u64 tiles = (limit + kTile - 1) / kTile;
       const uint32_t al = (aligned16(out) ? 1u : 0u) | (aligned16(pos) ? 2u : 0u) | (aligned16(seg) ? 4u : 0u);
-      k_bat_pack<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(c.ids, rw, c.rows, e.get(), limit, pad_id,
+      k_bat_pack<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(c.ids, rw, c.rows, sum.get(), limit, pad_id,
                                                                    c.row_base, out, pos, seg, al);
       ENC_OK(hipGetLastError());
     }
     return 0;
   }
+
+  // Staging of a pad or window piece: its ids and offsets, out (output 0) and two per-row int32
+  // arrays (outputs 1 and 3), the mask (output 2).
+  bool stage(const Piece& p, bool mask, Staged* s) {
+    if (!hids.grow(std::max<size_t>(p.len[0], 1)) || !hrow.grow(p.r1 - p.r0 + 1, 2) ||
+        !hout.grow(std::max(p.cells, p.wp), 3) || (mask && !hmask.grow(std::max<size_t>(p.cells, 1))))
+      return false;
+    s->ids[0] = hids.get();
+    s->row[0] = hrow.get();
+    s->out[0] = hout.get();
+    s->out[1] = hout.get() + hout.cap();
+    s->out[2] = hmask.get();
+    s->out[3] = hout.get() + 2 * hout.cap();
+    return true;
+  }
 };
 
-// The window passes' state, allocated on the first window call (the host path stages through
-// BatchState's buffers and hsrc).  Scratch grown to the most rows seen: 8 B per row (WO) and what
-// the scan and the reduction ask for.
-struct WindowState : PassState {
-  DeviceBuf<u64> wo;           // WO[r]: index of row r's first window; WO[rows] = Wn
-  DeviceBuf<uint8_t> tmp;      // hipCUB scan / reduce scratch
-  DeviceWords res;             // k_bat_rows' words ([0] bad row_off, [1] never set: e_r <= max_len), [2] max e
-  PinnedWords host;            // Wn, then the three words of res
-  EventSet<4> ev;
+// The window passes' state, allocated on the first window call: the length pass (sum is WO); the
+// host path stages through BatchState's buffers and hsrc.
+struct WindowState : LengthState {
   DeviceBuf<int64_t> hsrc;     // host path: a piece's win_src
 
   bool reserve(size_t rows) {
-    if (!res.ensure(4) || !host.ensure(4) || !ev.ensure() || !wo.grow(rows + 1)) return false;
     const Rows rw{nullptr, 0, 1, 0, 0, 0, 0, 0};
-    size_t scan = 0, red = 0;
-    if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, WOIter(hipcub::CountingInputIterator<u64>(0), WOInput{{rw, 1}}),
-                                         wo.get(), (u64)rows + 1) != hipSuccess)
-      return false;
-    if (hipcub::DeviceReduce::Max(nullptr, red, WIter(hipcub::CountingInputIterator<u64>(0), WInput{rw}),
-                                  res.get() + 2, (u64)std::max<size_t>(rows, 1)) != hipSuccess)
-      return false;
-    return tmp.grow(std::max<size_t>(std::max(scan, red), 16));
+    return LengthState::reserve(rows, row_iter(WOInput{{rw, 1}}), row_iter(WInput{rw}));
   }
 
-  // Row checks (when c.row), WO into wo and the longest window over c's rows: 0, -1, -6.
+  // Row checks (when c.row), WO into sum and the longest window over c's rows: 0, -1, -6.
   int lengths(const BatchCall& c, const Windows& wn, hipStream_t st, uint64_t* windows, uint64_t* widest) {
-    ENC_OK(hipMemsetAsync(res.get(), 0, 32, st));
-    if (c.row) {
-      k_bat_rows<<<dim3((unsigned)((c.rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(wn.rw, c.rows,
-                                                                                              c.ends ? 1 : 0, res.get());
-      ENC_OK(hipGetLastError());
-    }
-    size_t bytes = tmp.cap();
-    ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, WOIter(hipcub::CountingInputIterator<u64>(0), WOInput{wn}),
-                                            wo.get(), c.rows + 1, st));
-    ENC_OK(hipMemcpyAsync(host.get(), wo.get() + c.rows, 8, hipMemcpyDeviceToHost, st));
-    if (c.rows) {
-      bytes = tmp.cap();
-      ENC_OK(hipcub::DeviceReduce::Max(tmp.get(), bytes, WIter(hipcub::CountingInputIterator<u64>(0), WInput{wn.rw}),
-                                       res.get() + 2, c.rows, st));
-    }
-    ENC_OK(hipMemcpyAsync(host.get() + 1, res.get(), 24, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (host[1]) return -6;
-    *windows = host[0];
-    *widest = host[3];
-    return 0;
+    const auto scan_in = row_iter(WOInput{wn});
+    const auto max_in = row_iter(WInput{wn.rw});
+    return measure(c.rows, [&](u64* err) { return row_pass(wn.rw, c, err, st); }, &scan_in, &max_in, st, windows,
+                   widest);
   }
 
-  // The call's windows [0, windows) from wo into out / lengths / mask / win_row / win_src (which
+  // The call's windows [0, windows) from sum into out / lengths / mask / win_row / win_src (which
   // point at the call's first window); win_row gets c.row_base added and win_src c.base.
   int expand(const BatchCall& c, const Windows& wn, uint64_t windows, uint64_t width, int32_t pad_id, int pad_side,
              int32_t* out, int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, hipStream_t st) {
@@ -648,7 +594,7 @@ struct WindowState : PassState {
     }
     const u64 tiles = (total + kTile - 1) / kTile;
     (aligned16(out) ? k_bat_window<true> : k_bat_window<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
-        c.ids, wn, c.rows, wo.get(), width, total, pad_id, pad_side ? 1u : 0u, c.row_base, c.base, out, lengths, mask,
+        c.ids, wn, c.rows, sum.get(), width, total, pad_id, pad_side ? 1u : 0u, c.row_base, c.base, out, lengths, mask,
         (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? 1u : 0u, win_row, win_src);
     ENC_OK(hipGetLastError());
     return 0;
@@ -657,279 +603,166 @@ struct WindowState : PassState {
 
 }  // namespace
 
-int64_t EncodeDevice::window(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
-                             size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap,
-                             int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, int64_t* row_win,
-                             size_t* widest_out, void* stream, double* kernel_ms) {
-  if (kernel_ms) *kernel_ms = 0;
-  const u64 R = row_off ? rows : 1;
-  if (!rows_fit(R)) return -1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  WindowState& ws = pass_state<WindowState>(pass_[kWindow]);
-  if (!ws.reserve(R)) {
-    std::fprintf(stderr, "[ERROR]\t encoder: window allocation failed (%zu rows)\n", (size_t)R);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  const EventSet<4>& ev = ws.ev;
-  const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
-  const Windows wn = windows_of(o, stride, row_off, n);
-  u64 windows = 0, widest = 0;
-  ENC_OK(hipEventRecord(ev[0], st));
-  const int r = ws.lengths(c, wn, st, &windows, &widest);
-  if (r < 0) return r;
-  ENC_OK(hipEventRecord(ev[1], st));
-  if (windows > (u64)INT64_MAX || (width && windows > (u64)INT64_MAX / width)) return -1;
-  const bool expand = out && width >= widest && cap >= windows * width;
-  if (expand) {
-    if (!tiles_fit(windows * width)) return -1;
-    ENC_OK(hipEventRecord(ev[2], st));
-    if (row_win) {
-      k_bat_row_start<<<dim3((unsigned)((R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(ws.wo.get(), R, 0,
-                                                                                              row_win);
-      ENC_OK(hipGetLastError());
-    }
-    if (ws.expand(c, wn, windows, width, pad_id, pad_side, out, lengths, mask, win_row, win_src, st) < 0) return -1;
-    ENC_OK(hipEventRecord(ev[3], st));
-  }
-  ENC_OK(hipStreamSynchronize(st));
-  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
-  if (widest_out) *widest_out = (size_t)widest;
-  return (int64_t)windows;
-}
-
 int64_t EncodeDevice::pad(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                           size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap, int32_t* lengths,
                           uint8_t* mask, void* stream, double* kernel_ms) {
   if (kernel_ms) *kernel_ms = 0;
   const u64 R = row_off ? rows : 1;
-  if (!rows_fit(R) || (width && R > (u64)INT64_MAX / width)) return -1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
-  if (!bs.reserve(R)) {
-    std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  const EventSet<4>& ev = bs.ev;
+  if (width && R > (u64)INT64_MAX / width) return -1;
   const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
-  u64 total = 0, widest = 0;
-  ENC_OK(hipEventRecord(ev[0], st));
-  const int r = bs.lengths(c, false, st, &total, &widest);
-  if (r < 0) return r;
-  ENC_OK(hipEventRecord(ev[1], st));
-  const bool expand = out && width >= widest && cap >= R * width;
-  if (expand) {
-    if (!tiles_fit(R * width)) return -1;
-    ENC_OK(hipEventRecord(ev[2], st));
-    if (pad_expand(c, width, pad_id, pad_side, out, lengths, mask, st) < 0) return -1;
-    ENC_OK(hipEventRecord(ev[3], st));
-  }
-  ENC_OK(hipStreamSynchronize(st));
-  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
-  return (int64_t)widest;
+  return device_call<BatchState>(
+      pass_[kBatch], device_, stream ? stream : stream_, "batch", R, kernel_ms,
+      [&](BatchState& bs, hipStream_t st, Plan* p) {
+        u64 total = 0, widest = 0;
+        const int r = bs.lengths(c, false, st, &total, &widest);
+        *p = Plan{(int64_t)widest, out && width >= widest && cap >= R * width, R * width};
+        return r;
+      },
+      [&](BatchState&, hipStream_t st) { return pad_expand(c, width, pad_id, pad_side, out, lengths, mask, st); });
 }
 
 int64_t EncodeDevice::pack(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                            size_t seq_len, int32_t pad_id, bool drop_last, int32_t* out, size_t cap, int32_t* pos,
                            int32_t* seg, int64_t* row_start, void* stream, double* kernel_ms) {
-  if (kernel_ms) *kernel_ms = 0;
-  const u64 R = row_off ? rows : 1;
-  if (!rows_fit(R)) return -1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
-  if (!bs.reserve(R)) {
-    std::fprintf(stderr, "[ERROR]\t encoder: batch allocation failed (%zu rows)\n", (size_t)R);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  const EventSet<4>& ev = bs.ev;
+  const u64 R = row_off ? rows : 1, L = seq_len;
   const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
-  u64 total = 0, widest = 0;
-  ENC_OK(hipEventRecord(ev[0], st));
-  const int r = bs.lengths(c, true, st, &total, &widest);
-  if (r < 0) return r;
-  ENC_OK(hipEventRecord(ev[1], st));
-  const u64 L = seq_len;
-  const u64 S = drop_last ? total / L : total / L + (total % L ? 1 : 0);
-  if (S > (u64)INT64_MAX / L) return -1;
-  const bool expand = out && cap >= S * L;
-  if (expand) {
-    if (!tiles_fit(S * L)) return -1;
-    ENC_OK(hipEventRecord(ev[2], st));
-    if (bs.pack_expand(c, S * L, pad_id, out, pos, seg, row_start, st) < 0) return -1;
-    ENC_OK(hipEventRecord(ev[3], st));
-  }
-  ENC_OK(hipStreamSynchronize(st));
-  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
-  return (int64_t)S;
+  u64 S = 0;
+  return device_call<BatchState>(
+      pass_[kBatch], device_, stream ? stream : stream_, "batch", R, kernel_ms,
+      [&](BatchState& bs, hipStream_t st, Plan* p) {
+        u64 total = 0, widest = 0;
+        const int r = bs.lengths(c, true, st, &total, &widest);
+        if (r < 0) return r;
+        S = drop_last ? total / L : total / L + (total % L ? 1 : 0);
+        if (S > (u64)INT64_MAX / L) return -1;
+        *p = Plan{(int64_t)S, out && cap >= S * L, S * L};
+        return 0;
+      },
+      [&](BatchState& bs, hipStream_t st) { return bs.pack_expand(c, S * L, pad_id, out, pos, seg, row_start, st); });
 }
 
-// Host rows in pieces of whole rows (piece_end).  A pad piece is a pad of its own rows into rows
+int64_t EncodeDevice::window(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
+                             size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out, size_t cap,
+                             int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, int64_t* row_win,
+                             size_t* widest_out, void* stream, double* kernel_ms) {
+  const u64 R = row_off ? rows : 1;
+  const BatchCall c{ids, n, row_off, R, true, o, 0, 0};
+  const Windows wn = windows_of(o, stride, row_off, n);
+  u64 windows = 0, widest = 0;
+  const int64_t r = device_call<WindowState>(
+      pass_[kWindow], device_, stream ? stream : stream_, "window", R, kernel_ms,
+      [&](WindowState& ws, hipStream_t st, Plan* p) {
+        const int r = ws.lengths(c, wn, st, &windows, &widest);
+        if (r < 0) return r;
+        if (windows > (u64)INT64_MAX || (width && windows > (u64)INT64_MAX / width)) return -1;
+        *p = Plan{(int64_t)windows, out && width >= widest && cap >= windows * width, windows * width};
+        return 0;
+      },
+      [&](WindowState& ws, hipStream_t st) {
+        if (row_win) {
+          k_bat_row_start<<<dim3((unsigned)((R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(ws.sum.get(), R, 0,
+                                                                                                  row_win);
+          ENC_OK(hipGetLastError());
+        }
+        return ws.expand(c, wn, windows, width, pad_id, pad_side, out, lengths, mask, win_row, win_src, st);
+      });
+  if (r >= 0 && widest_out) *widest_out = (size_t)widest;
+  return r;
+}
+
+// Host rows in pieces of whole rows (host_pieces).  A pad piece is a pad of its own rows into rows
 // [r0, r1) of out; the caller has validated row_off and width on the host, so no length pass runs.
 int EncodeDevice::pad_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                            size_t width, int32_t pad_id, int pad_side, int32_t* out, int32_t* lengths,
                            uint8_t* mask) {
-  const size_t R = row_off ? rows : 1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  const size_t piece = piece_ids();
   BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
   hipStream_t st = (hipStream_t)stream_;
-  std::vector<int64_t> local;
-  for (size_t r0 = 0; r0 < R;) {
-    const size_t r1 = row_off ? piece_end(row_off, R, r0, piece, width) : 1;
-    const size_t m = r1 - r0;
-    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
-    const size_t cells = m * width;
-    if (!tiles_fit(cells) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2) ||
-        !bs.hout.grow(std::max(cells, m), 3) || (mask && !bs.hmask.grow(std::max<size_t>(cells, 1)))) {
-      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
-      return -1;
-    }
-    int32_t *const dids = bs.hids.get(), *const dout = bs.hout.get(), *const dlen = dout + bs.hout.cap();
-    if (len) ENC_OK(hipMemcpyAsync(dids, ids + a, len * 4, hipMemcpyHostToDevice, st));
-    if (row_off) {
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    const BatchCall c{dids, len, row_off ? bs.hrow.get() : nullptr, m, false, o, 0, r0};
-    if (pad_expand(c, width, pad_id, pad_side, dout, lengths ? dlen : nullptr, mask ? bs.hmask.get() : nullptr, st) < 0)
-      return -1;
-    if (cells) ENC_OK(hipMemcpyAsync(out + r0 * width, dout, cells * 4, hipMemcpyDeviceToHost, st));
-    if (lengths) ENC_OK(hipMemcpyAsync(lengths + r0, dlen, m * 4, hipMemcpyDeviceToHost, st));
-    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + r0 * width, bs.hmask.get(), cells, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    r0 = r1;
-  }
-  return 0;
+  const HostCall call{"batch", row_off ? rows : 1, width, 1, {{ids, n, row_off}}, false, nullptr,
+                      3,       {{out, 4, 0, 1}, {lengths, 4, 1, 0}, {mask, 1, 0, 1}}};
+  return host_pieces(
+      device_, st, call, [](size_t) { return (u64)1; },
+      [&](const Piece& p, Staged* s) { return bs.stage(p, mask != nullptr, s); },
+      [&](const Piece& p, const Staged& s) {
+        const BatchCall c{s.ids[0], p.len[0], row_off ? s.row[0] : nullptr, p.r1 - p.r0, false, o, 0, p.r0};
+        return pad_expand(c, width, pad_id, pad_side, s.get<int32_t>(0), s.get<int32_t>(1), s.get<uint8_t>(2), st);
+      });
 }
 
-// A pack piece writes its slice of the flat stream at the offset of its first row (BatchCall::base),
-// cut at out_len = S * seq_len; only the last piece runs on to out_len, which writes the pad tail.
+// A pack piece runs its own length pass (the caller has validated row_off) and writes its slice of
+// the flat stream at the offset of its first row (BatchCall::base), cut at out_len = S * seq_len;
+// only the last piece runs on to out_len, which writes the pad tail.  The stream is not a rectangle
+// of emitted rows, so the piece's outputs are sized and copied back here.
 int EncodeDevice::pack_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                             uint64_t out_len, int32_t pad_id, int32_t* out, int32_t* pos, int32_t* seg,
                             int64_t* row_start) {
   const size_t R = row_off ? rows : 1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  const size_t piece = piece_ids();
   BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
   hipStream_t st = (hipStream_t)stream_;
-  std::vector<int64_t> local;
+  const HostCall call{"batch", R, 0, 1, {{ids, n, row_off}}, false, nullptr, 0, {}};
   u64 done = 0;
   if (row_start) row_start[0] = 0;
-  for (size_t r0 = 0; r0 < R;) {
-    const size_t r1 = row_off ? piece_end(row_off, R, r0, piece, 0) : 1;
-    const size_t m = r1 - r0;
-    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
-    if (!bs.reserve(m) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2)) {
-      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu ids, %zu rows)\n", len, m);
-      return -1;
-    }
-    if (len) ENC_OK(hipMemcpyAsync(bs.hids.get(), ids + a, len * 4, hipMemcpyHostToDevice, st));
-    if (row_off) {
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    const BatchCall c{bs.hids.get(), len, row_off ? bs.hrow.get() : nullptr, m, false, o, done, r0};
-    u64 total = 0, widest = 0;
-    if (bs.lengths(c, true, st, &total, &widest) < 0) return -1;  // (the caller has validated row_off)
-    const u64 end = r1 == R ? out_len : std::min(done + total, out_len);
-    const u64 limit = end > done ? end - done : 0;
-    if (!tiles_fit(limit) || !bs.hout.grow(std::max<size_t>((size_t)limit, 1), 3)) {
-      std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu entries)\n", (size_t)limit);
-      return -1;
-    }
-    int32_t *const dout = bs.hout.get(), *const dpos = dout + bs.hout.cap(), *const dseg = dpos + bs.hout.cap();
-    int64_t* dstart = bs.hrow.get() + bs.hrow.cap();
-    if (bs.pack_expand(c, limit, pad_id, dout, pos ? dpos : nullptr, seg ? dseg : nullptr,
-                       row_start ? dstart : nullptr, st) < 0)
-      return -1;
-    if (limit) {
-      ENC_OK(hipMemcpyAsync(out + done, dout, limit * 4, hipMemcpyDeviceToHost, st));
-      if (pos) ENC_OK(hipMemcpyAsync(pos + done, dpos, limit * 4, hipMemcpyDeviceToHost, st));
-      if (seg) ENC_OK(hipMemcpyAsync(seg + done, dseg, limit * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (row_start) ENC_OK(hipMemcpyAsync(row_start + r0 + 1, dstart + 1, m * 8, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    done += total;
-    r0 = r1;
-  }
-  return 0;
+  return host_pieces(
+      device_, st, call, [](size_t) { return (u64)0; },
+      [&](const Piece& p, Staged* s) {
+        const size_t m = p.r1 - p.r0;
+        if (!bs.reserve(m) || !bs.hids.grow(std::max<size_t>(p.len[0], 1)) || !bs.hrow.grow(m + 1, 2)) return false;
+        s->ids[0] = bs.hids.get();
+        s->row[0] = bs.hrow.get();
+        return true;
+      },
+      [&](const Piece& p, const Staged& s) {
+        const size_t m = p.r1 - p.r0;
+        const BatchCall c{s.ids[0], p.len[0], row_off ? s.row[0] : nullptr, m, false, o, done, p.r0};
+        u64 total = 0, widest = 0;
+        if (bs.lengths(c, true, st, &total, &widest) < 0) return -1;
+        const u64 end = p.r1 == R ? out_len : std::min(done + total, out_len);
+        const u64 limit = end > done ? end - done : 0;
+        if (!tiles_fit(limit) || !bs.hout.grow(std::max<size_t>((size_t)limit, 1), 3)) {
+          std::fprintf(stderr, "[ERROR]\t encoder: batch staging allocation failed (%zu entries)\n", (size_t)limit);
+          return -1;
+        }
+        int32_t *const dout = bs.hout.get(), *const dpos = dout + bs.hout.cap(), *const dseg = dpos + bs.hout.cap();
+        int64_t* dstart = bs.hrow.get() + bs.hrow.cap();
+        if (bs.pack_expand(c, limit, pad_id, dout, pos ? dpos : nullptr, seg ? dseg : nullptr,
+                           row_start ? dstart : nullptr, st) < 0)
+          return -1;
+        if (limit) {
+          ENC_OK(hipMemcpyAsync(out + done, dout, limit * 4, hipMemcpyDeviceToHost, st));
+          if (pos) ENC_OK(hipMemcpyAsync(pos + done, dpos, limit * 4, hipMemcpyDeviceToHost, st));
+          if (seg) ENC_OK(hipMemcpyAsync(seg + done, dseg, limit * 4, hipMemcpyDeviceToHost, st));
+        }
+        if (row_start) ENC_OK(hipMemcpyAsync(row_start + p.r0 + 1, dstart + 1, m * 8, hipMemcpyDeviceToHost, st));
+        done += total;
+        return 0;
+      });
 }
 
 // A window piece is the windows of its own rows, written to windows [w0, w1) of the outputs.  The
 // caller has validated row_off, width and cap on the host, so no length pass runs: the piece's WO
-// is made here and uploaded, and row_win is written from it.  A piece takes whole rows while it
-// holds at most `piece` ids, `piece` rows and 4 x piece output entries; at least one row.
+// is made on the host and uploaded, and row_win is written from it.
 int EncodeDevice::window_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const BatchOpts& o,
                               size_t stride, size_t width, int32_t pad_id, int pad_side, int32_t* out,
                               int32_t* lengths, uint8_t* mask, int32_t* win_row, int64_t* win_src, int64_t* row_win) {
-  const size_t R = row_off ? rows : 1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  const size_t piece = piece_ids();
   BatchState& bs = pass_state<BatchState>(pass_[kBatch]);
   WindowState& ws = pass_state<WindowState>(pass_[kWindow]);
   hipStream_t st = (hipStream_t)stream_;
-  const u64 C = o.max_len - ((o.has_bos ? 1 : 0) + (o.has_eos ? 1 : 0)), step = C - stride;
-  const auto count = [&](size_t r) {
-    return window_count(row_off ? (u64)(row_off[r + 1] - row_off[r]) : (u64)n, C, step);
-  };
-  std::vector<int64_t> local;
-  std::vector<u64> wo;
-  u64 w0 = 0;
-  if (row_win) row_win[0] = 0;
-  for (size_t r0 = 0; r0 < R;) {
-    wo.assign(1, 0);
-    size_t r1 = r0;
-    do {
-      wo.push_back(wo.back() + count(r1));
-      ++r1;
-    } while (r1 < R && r1 - r0 < piece && (u64)(row_off[r1 + 1] - row_off[r0]) <= (u64)piece &&
-             (wo.back() + count(r1)) * width <= 4 * (u64)piece);
-    const size_t m = r1 - r0, wp = (size_t)wo.back();
-    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a;
-    const size_t cells = wp * width;
-    if (!tiles_fit(cells) || !bs.hids.grow(std::max<size_t>(len, 1)) || !bs.hrow.grow(m + 1, 2) || !ws.wo.grow(m + 1) ||
-        !bs.hout.grow(std::max(cells, wp), 3) || (mask && !bs.hmask.grow(std::max<size_t>(cells, 1))) ||
-        (win_src && !ws.hsrc.grow(wp))) {
-      std::fprintf(stderr, "[ERROR]\t encoder: window staging allocation failed (%zu ids, %zu rows, %zu windows)\n", len,
-                   m, wp);
-      return -1;
-    }
-    int32_t *const dids = bs.hids.get(), *const dout = bs.hout.get(), *const dlen = dout + bs.hout.cap(),
-                   *const drow = dlen + bs.hout.cap();
-    if (len) ENC_OK(hipMemcpyAsync(dids, ids + a, len * 4, hipMemcpyHostToDevice, st));
-    if (row_off) {
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r0 + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(bs.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    ENC_OK(hipMemcpyAsync(ws.wo.get(), wo.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    const BatchCall c{dids, len, row_off ? bs.hrow.get() : nullptr, m, false, o, a, r0};
-    const Windows wn = windows_of(o, stride, c.row, len);
-    if (ws.expand(c, wn, wp, width, pad_id, pad_side, dout, lengths ? dlen : nullptr, mask ? bs.hmask.get() : nullptr,
-                  win_row ? drow : nullptr, win_src ? ws.hsrc.get() : nullptr, st) < 0)
-      return -1;
-    if (cells) ENC_OK(hipMemcpyAsync(out + w0 * width, dout, cells * 4, hipMemcpyDeviceToHost, st));
-    if (lengths) ENC_OK(hipMemcpyAsync(lengths + w0, dlen, wp * 4, hipMemcpyDeviceToHost, st));
-    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + w0 * width, bs.hmask.get(), cells, hipMemcpyDeviceToHost, st));
-    if (win_row) ENC_OK(hipMemcpyAsync(win_row + w0, drow, wp * 4, hipMemcpyDeviceToHost, st));
-    if (win_src) ENC_OK(hipMemcpyAsync(win_src + w0, ws.hsrc.get(), wp * 8, hipMemcpyDeviceToHost, st));
-    if (row_win)
-      for (size_t i = 1; i <= m; ++i) row_win[r0 + i] = (int64_t)(w0 + wo[i]);
-    ENC_OK(hipStreamSynchronize(st));
-    w0 += wp;
-    r0 = r1;
-  }
-  return 0;
+  const Windows host = windows_of(o, stride, row_off, n);
+  const HostCall call{"window", row_off ? rows : 1, width, 1, {{ids, n, row_off}}, true, row_win, 5,
+                      {{out, 4, 0, 1}, {lengths, 4, 1, 0}, {mask, 1, 0, 1}, {win_row, 4, 1, 0}, {win_src, 8, 1, 0}}};
+  return host_pieces(
+      device_, st, call, [&](size_t r) { return host.count(r); },
+      [&](const Piece& p, Staged* s) {
+        if (!bs.stage(p, mask != nullptr, s) || !ws.sum.grow(p.r1 - p.r0 + 1) || (win_src && !ws.hsrc.grow(p.wp)))
+          return false;
+        s->wo = ws.sum.get();
+        s->out[4] = ws.hsrc.get();
+        return true;
+      },
+      [&](const Piece& p, const Staged& s) {
+        const BatchCall c{s.ids[0], p.len[0], row_off ? s.row[0] : nullptr, p.r1 - p.r0, false, o, p.a[0], p.r0};
+        return ws.expand(c, windows_of(o, stride, c.row, c.n), p.wp, width, pad_id, pad_side, s.get<int32_t>(0),
+                         s.get<int32_t>(1), s.get<uint8_t>(2), s.get<int32_t>(3), s.get<int64_t>(4), st);
+      });
 }
 
 }  // namespace shred

@@ -1,7 +1,8 @@
 // Row pairs to one model input on gfx950: [bos] + kept_a + mid + kept_b + [eos], truncated against
 // one budget or with the second row cut into windows (C ABI and definitions:
-// include/shredword_encode.h, shred_pair_*).  The tile geometry and the helpers are those of
-// batch_device.hip (batch_common.h); the kernels are this unit's own.
+// include/shredword_encode.h, shred_pair_*).  The rule that turns an example into its emitted rows is
+// host/pair_rule.h; the tile geometry and the wave search are batch_common.h's, the kernels this
+// unit's own, and the length pass, the device call and the host pieces are batch_state.h's.
 //
 // Example r has la_r ids of ids_a and lb_r ids of ids_b.  The strategy turns (la_r, lb_r) into ka_r
 // kept ids of a and, for strategies 0 .. 2, kb_r kept ids of b (one emitted row), for strategy 3 a
@@ -11,10 +12,8 @@
 //   k_pair_rows      one thread per entry of the two offset arrays: range, order and end points of
 //                    both, and for example r - 1: whether the strategy can make it fit and whether
 //                    its e fits an int32 (error words, ordinary stores, no atomics);
-//   hipCUB scan      inclusive sum over k = 0 .. rows of (k ? w_{k-1} : 0) through a transform
-//                    iterator on the two offset arrays: WO[0 .. rows];
-//   hipCUB reduce    the maximum over r of the example's longest emitted row (its first), through
-//                    the same kind of iterator;
+//   hipCUB scan      WO[0 .. rows] from w_r, through a transform iterator on the two offset arrays;
+//   hipCUB reduce    the maximum over r of the example's longest emitted row (its first);
 //   k_bat_row_start  row_win[r] = WO[r];
 //   k_bat_pair       output-centric like k_bat_window: one workgroup per kTile consecutive entries
 //                    of the flat [Wn, W] array, 4 consecutive entries per lane, the (emitted row,
@@ -43,112 +42,19 @@
 // only element-aligned (tensor views), so the 16-byte (types, mask: 4-byte) stores have a scalar form.
 #include <hip/hip_runtime.h>
 
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "../host/encoder.h"
+#include "../host/pair_rule.h"
 #include "batch_common.h"
+#include "batch_state.h"
 #include "encode_common.h"
 
 namespace shred {
 namespace {
-
-// How an example turns into its emitted rows; passed to the kernels and the hipCUB iterators by
-// value, and used by the host path on host offset arrays.
-struct Pairs {
-  const int64_t* ra;   // rows + 1 entries each
-  const int64_t* rb;
-  u64 na, nb;
-  u64 B;               // kept ids per emitted row: max_len - add, or kNoLimit
-  u64 max_a, stride;   // strategy 3 (max_a 0: all of a)
-  uint32_t strategy, left, bos_n, mid_n, eos_n;
-  int32_t bos, mid0, mid1, eos;
-
-  __host__ __device__ __forceinline__ u64 add() const { return (u64)(bos_n + mid_n + eos_n); }
-  __host__ __device__ __forceinline__ void bounds(u64 r, u64* a0, u64* a1, u64* b0, u64* b1) const {
-    *a0 = (u64)ra[r];
-    *a1 = (u64)ra[r + 1];
-    *b0 = (u64)rb[r];
-    *b1 = (u64)rb[r + 1];
-  }
-  // ka and cb: kb for strategies 0 .. 2, the window capacity C for strategy 3.  False: the example
-  // cannot be made to fit (nothing is set).
-  __host__ __device__ __forceinline__ bool fit(u64 la, u64 lb, u64* ka, u64* cb) const {
-    if (strategy == 0) {
-      if (lb <= B && la <= B - lb) {  // la + lb <= B
-        *ka = la;
-        *cb = lb;
-      } else if ((la < lb ? la : lb) <= B / 2) {  // the shorter stays whole
-        *ka = la <= lb ? la : B - lb;
-        *cb = la <= lb ? B - la : lb;
-      } else {
-        *ka = B - B / 2;
-        *cb = B / 2;
-      }
-      return true;
-    }
-    if (strategy == 1) {
-      if (lb > B) return false;
-      *ka = la < B - lb ? la : B - lb;
-      *cb = lb;
-      return true;
-    }
-    if (strategy == 2) {
-      if (la > B) return false;
-      *ka = la;
-      *cb = lb < B - la ? lb : B - la;
-      return true;
-    }
-    const u64 k = max_a && max_a < la ? max_a : la;
-    if (k > B || B - k <= stride) return false;
-    *ka = k;
-    *cb = B - k;
-    return true;
-  }
-  // w_r (1 for an example that cannot fit: the call fails before the value is used).
-  __host__ __device__ __forceinline__ u64 count(u64 r) const {
-    if (strategy != 3) return 1;
-    u64 a0, a1, b0, b1, ka, C;
-    bounds(r, &a0, &a1, &b0, &b1);
-    return fit(a1 - a0, b1 - b0, &ka, &C) ? window_count(b1 - b0, C, C - stride) : 1;
-  }
-  // ka and the kb of the example's first (its longest) emitted row.
-  __host__ __device__ __forceinline__ bool first(u64 la, u64 lb, u64* ka, u64* kb) const {
-    if (!fit(la, lb, ka, kb)) return false;
-    if (strategy == 3 && lb < *kb) *kb = lb;
-    return true;
-  }
-  // The largest e of example r (0 for one that cannot fit).
-  __host__ __device__ __forceinline__ u64 emit(u64 r) const {
-    u64 a0, a1, b0, b1, ka, kb;
-    bounds(r, &a0, &a1, &b0, &b1);
-    return first(a1 - a0, b1 - b0, &ka, &kb) ? add() + ka + kb : 0;
-  }
-  // Emitted id j of a row of e = add + ka + kb ids, and its token type.
-  __device__ __forceinline__ int32_t id(const int32_t* __restrict__ ids_a, const int32_t* __restrict__ ids_b, u64 ka,
-                                        u64 kb, u64 asrc, u64 bsrc, u64 j, uint32_t* type) const {
-    *type = 0;
-    if (j < (u64)bos_n) return bos;
-    j -= (u64)bos_n;
-    if (j < ka) return ids_a[asrc + j];
-    j -= ka;
-    if (j < (u64)mid_n) return j ? mid1 : mid0;
-    j -= (u64)mid_n;
-    *type = 1;
-    return j < kb ? ids_b[bsrc + j] : eos;
-  }
-};
-
-Pairs pairs_of(const EncodeDevice::PairOpts& o, const int64_t* ra, u64 na, const int64_t* rb, u64 nb) {
-  const uint32_t b = o.has_bos ? 1u : 0u, e = o.has_eos ? 1u : 0u;
-  return Pairs{ra, rb, na, nb, o.max_len ? o.max_len - (b + o.mid_n + e) : kNoLimit, o.max_a, o.stride,
-               (uint32_t)o.strategy, o.trunc_side ? 1u : 0u, b, o.mid_n, e, o.bos, o.mid[0], o.mid[1], o.eos};
-}
 
 // err: [0] a bad offset array, [1] an e past int32, [2] an example that cannot fit.
 __global__ __launch_bounds__(kThreads) void k_pair_rows(Pairs pr, u64 rows, u64* __restrict__ err) {
@@ -166,13 +72,13 @@ __global__ __launch_bounds__(kThreads) void k_pair_rows(Pairs pr, u64 rows, u64*
     u64 ka, kb;
     if (!pr.first((u64)(va - pa), (u64)(vb - pb), &ka, &kb)) {
       err[2] = 1;
-    } else if (ka > (u64)INT32_MAX || kb > (u64)INT32_MAX || pr.add() + ka + kb > (u64)INT32_MAX) {
+    } else if (pr.too_long(ka, kb)) {
       err[1] = 1;
     }
   }
 }
 
-// Element k of the scan: the emitted rows of example k - 1.
+// Element k of the scan: the emitted rows of example k - 1; element r of the reduction: its longest.
 struct PWOInput {
   Pairs pr;
   __host__ __device__ __forceinline__ u64 operator()(u64 k) const { return k ? pr.count(k - 1) : 0ull; }
@@ -181,8 +87,6 @@ struct PEInput {
   Pairs pr;
   __host__ __device__ __forceinline__ u64 operator()(u64 r) const { return pr.emit(r); }
 };
-typedef hipcub::TransformInputIterator<u64, PWOInput, hipcub::CountingInputIterator<u64>> PWOIter;
-typedef hipcub::TransformInputIterator<u64, PEInput, hipcub::CountingInputIterator<u64>> PEIter;
 
 // total = Wn * W > 0, W >= every emitted row's length; WO: rows + 1 entries, strictly increasing
 // from 0 to Wn; every example fits (k_pair_rows, or the host).  Emitted row w of the call goes to
@@ -366,14 +270,9 @@ struct PairOut {
   int64_t* seg_src;
 };
 
-// The pair passes' state, allocated on the first pair call.  Scratch grown to the most examples
-// seen: 8 B per example (WO) and what the scan and the reduction ask for; the host path's staging.
-struct PairState : PassState {
-  DeviceBuf<u64> wo;           // WO[r]: index of example r's first emitted row; WO[rows] = Wn
-  DeviceBuf<uint8_t> tmp;      // hipCUB scan / reduce scratch
-  DeviceWords res;             // k_pair_rows' three words, [3] max e
-  PinnedWords host;            // Wn, then the four words of res
-  EventSet<4> ev;
+// The pair passes' state, allocated on the first pair call: the length pass (sum is WO) and the
+// host path's staging.
+struct PairState : LengthState {
   // host-path staging: a piece's ids of a and of b; its two local offset arrays (2 x hrow.cap());
   // out; lengths, win_row and the two columns' worth of seg_len (4 x hmeta.cap()); seg_src
   // (2 x hsrc.cap()); types and mask (2 x hbytes.cap())
@@ -384,42 +283,22 @@ struct PairState : PassState {
   DeviceBuf<uint8_t> hbytes;
 
   bool reserve(size_t rows) {
-    if (!res.ensure(4) || !host.ensure(5) || !ev.ensure() || !wo.grow(rows + 1)) return false;
     const Pairs pr{nullptr, nullptr, 0, 0, kNoLimit, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    size_t scan = 0, red = 0;
-    if (hipcub::DeviceScan::InclusiveSum(nullptr, scan, PWOIter(hipcub::CountingInputIterator<u64>(0), PWOInput{pr}),
-                                         wo.get(), (u64)rows + 1) != hipSuccess)
-      return false;
-    if (hipcub::DeviceReduce::Max(nullptr, red, PEIter(hipcub::CountingInputIterator<u64>(0), PEInput{pr}),
-                                  res.get() + 3, (u64)std::max<size_t>(rows, 1)) != hipSuccess)
-      return false;
-    return tmp.grow(std::max<size_t>(std::max(scan, red), 16));
+    return LengthState::reserve(rows, row_iter(PWOInput{pr}), row_iter(PEInput{pr}));
   }
 
-  // The row pass, WO into wo and the longest emitted row over the call's examples: 0, -1, -6, -7.
+  // The row pass, WO into sum and the longest emitted row over the call's examples: 0, -1, -6, -7.
   int lengths(const Pairs& pr, u64 rows, hipStream_t st, uint64_t* emitted, uint64_t* widest) {
-    ENC_OK(hipMemsetAsync(res.get(), 0, 32, st));
-    k_pair_rows<<<dim3((unsigned)((rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(pr, rows, res.get());
-    ENC_OK(hipGetLastError());
-    // (the scan and the reduction read entries 0 .. rows of the offset arrays and nothing through
-    // them, so they may run on arrays that the row pass finds bad)
-    size_t bytes = tmp.cap();
-    ENC_OK(hipcub::DeviceScan::InclusiveSum(tmp.get(), bytes, PWOIter(hipcub::CountingInputIterator<u64>(0), PWOInput{pr}),
-                                            wo.get(), rows + 1, st));
-    ENC_OK(hipMemcpyAsync(host.get(), wo.get() + rows, 8, hipMemcpyDeviceToHost, st));
-    if (rows) {
-      bytes = tmp.cap();
-      ENC_OK(hipcub::DeviceReduce::Max(tmp.get(), bytes, PEIter(hipcub::CountingInputIterator<u64>(0), PEInput{pr}),
-                                       res.get() + 3, rows, st));
-    }
-    ENC_OK(hipMemcpyAsync(host.get() + 1, res.get(), 32, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    if (host[1]) return -6;
-    if (host[3]) return -7;
-    if (host[2]) return -1;
-    *emitted = host[0];
-    *widest = host[4];
-    return 0;
+    const auto scan_in = row_iter(PWOInput{pr});
+    const auto max_in = row_iter(PEInput{pr});
+    return measure(
+        rows,
+        [&](u64* err) {
+          k_pair_rows<<<dim3((unsigned)((rows + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(pr, rows, err);
+          ENC_OK(hipGetLastError());
+          return 0;
+        },
+        &scan_in, &max_in, st, emitted, widest);
   }
 
   // The emitted rows [0, emitted) of the examples of pr from wo into o; win_row gets row_base added,
@@ -440,7 +319,7 @@ struct PairState : PassState {
     const uint32_t al = ((reinterpret_cast<uintptr_t>(o.types) & 3) == 0 ? 1u : 0u) |
                         ((reinterpret_cast<uintptr_t>(o.mask) & 3) == 0 ? 2u : 0u);
     (aligned16(o.out) ? k_bat_pair<true> : k_bat_pair<false>)<<<dim3((unsigned)tiles), dim3(kThreads), 0, st>>>(
-        ids_a, ids_b, pr, rows, wo.get(), width, total, pad_id, pad_side ? 1u : 0u, row_base, a_base, b_base, o.out,
+        ids_a, ids_b, pr, rows, sum.get(), width, total, pad_id, pad_side ? 1u : 0u, row_base, a_base, b_base, o.out,
         o.types, o.mask, al, o.lengths, o.win_row, o.seg_len, o.seg_src);
     ENC_OK(hipGetLastError());
     return 0;
@@ -454,139 +333,67 @@ int64_t EncodeDevice::pair(const int32_t* ids_a, size_t n_a, const int64_t* row_
                            int pad_side, int32_t* out, size_t cap, uint8_t* types, uint8_t* mask, int32_t* lengths,
                            int32_t* win_row, int32_t* seg_len, int64_t* seg_src, int64_t* row_win, size_t* widest_out,
                            void* stream, double* kernel_ms) {
-  if (kernel_ms) *kernel_ms = 0;
   const u64 R = rows;
-  if (!rows_fit(R)) return -1;
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  PairState& ps = pass_state<PairState>(pass_[kPair]);
-  if (!ps.reserve(R)) {
-    std::fprintf(stderr, "[ERROR]\t encoder: pair allocation failed (%zu examples)\n", (size_t)R);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)stream_;
-  const EventSet<4>& ev = ps.ev;
   const Pairs pr = pairs_of(o, row_a, n_a, row_b, n_b);
   u64 emitted = 0, widest = 0;
-  ENC_OK(hipEventRecord(ev[0], st));
-  const int r = ps.lengths(pr, R, st, &emitted, &widest);
-  if (r < 0) return r;
-  ENC_OK(hipEventRecord(ev[1], st));
-  if (emitted > (u64)INT64_MAX || (width && emitted > (u64)INT64_MAX / width)) return -1;
-  const bool expand = out && width >= widest && cap >= emitted * width;
-  if (expand) {
-    if (!tiles_fit(emitted * width)) return -1;
-    ENC_OK(hipEventRecord(ev[2], st));
-    if (row_win) {
-      k_bat_row_start<<<dim3((unsigned)((R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(ps.wo.get(), R, 0,
-                                                                                              row_win);
-      ENC_OK(hipGetLastError());
-    }
-    const PairOut po{out, types, mask, lengths, win_row, seg_len, seg_src};
-    if (ps.expand(ids_a, ids_b, pr, R, emitted, width, pad_id, pad_side, 0, 0, 0, po, st) < 0) return -1;
-    ENC_OK(hipEventRecord(ev[3], st));
-  }
-  ENC_OK(hipStreamSynchronize(st));
-  if (kernel_ms) ENC_OK(ev.sum_ms(expand ? 2 : 1, kernel_ms));
-  if (widest_out) *widest_out = (size_t)widest;
-  return (int64_t)emitted;
+  const int64_t r = device_call<PairState>(
+      pass_[kPair], device_, stream ? stream : stream_, "pair", R, kernel_ms,
+      [&](PairState& ps, hipStream_t st, Plan* p) {
+        const int r = ps.lengths(pr, R, st, &emitted, &widest);
+        if (r < 0) return r;
+        if (emitted > (u64)INT64_MAX || (width && emitted > (u64)INT64_MAX / width)) return -1;
+        *p = Plan{(int64_t)emitted, out && width >= widest && cap >= emitted * width, emitted * width};
+        return 0;
+      },
+      [&](PairState& ps, hipStream_t st) {
+        if (row_win) {
+          k_bat_row_start<<<dim3((unsigned)((R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(ps.sum.get(), R, 0,
+                                                                                                  row_win);
+          ENC_OK(hipGetLastError());
+        }
+        const PairOut po{out, types, mask, lengths, win_row, seg_len, seg_src};
+        return ps.expand(ids_a, ids_b, pr, R, emitted, width, pad_id, pad_side, 0, 0, 0, po, st);
+      });
+  if (r >= 0 && widest_out) *widest_out = (size_t)widest;
+  return r;
 }
 
-// Host examples.  The two offset arrays, the examples that cannot fit, Wn and the widest emitted row
-// are settled here on the host, so no length pass runs on the device.  A piece is the emitted rows
-// of its own examples, written to rows [w0, w1) of the outputs: it takes whole examples while its
-// ids of a plus its ids of b, its examples and its output entries (emitted rows * width, at most 4
-// per id of the budget) stay within the piece budget, and at least one example, however long.  The
-// piece's WO is made here and uploaded, and row_win is written from it.
-int64_t EncodeDevice::pair_host(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b,
-                                size_t n_b, const int64_t* row_b, size_t rows, const PairOpts& o, size_t width,
-                                int32_t pad_id, int pad_side, int32_t* out, size_t cap, uint8_t* types, uint8_t* mask,
-                                int32_t* lengths, int32_t* win_row, int32_t* seg_len, int64_t* seg_src,
-                                int64_t* row_win, size_t* widest_out) {
-  const size_t R = rows;
-  if (!rows_fit(R)) return -1;
-  for (int side = 0; side < 2; ++side) {
-    const int64_t* row = side ? row_b : row_a;
-    const size_t n = side ? n_b : n_a;
-    if (row[0] != 0 || row[R] < 0 || (u64)row[R] != n) return -6;
-    for (size_t r = 0; r < R; ++r)
-      if (row[r] > row[r + 1]) return -6;
-  }
-  const Pairs pr = pairs_of(o, row_a, n_a, row_b, n_b);
-  u64 Wn = 0, widest = 0;
-  bool too_long = false;
-  for (size_t r = 0; r < R; ++r) {
-    u64 ka, kb;
-    if (!pr.first((u64)(row_a[r + 1] - row_a[r]), (u64)(row_b[r + 1] - row_b[r]), &ka, &kb)) return -7;
-    if (ka > (u64)INT32_MAX || kb > (u64)INT32_MAX || pr.add() + ka + kb > (u64)INT32_MAX) too_long = true;
-    widest = std::max(widest, pr.add() + ka + kb);
-    Wn += pr.count(r);
-  }
-  if (too_long || Wn > (u64)INT64_MAX || (width && Wn > (u64)INT64_MAX / width)) return -1;
-  if (widest_out) *widest_out = (size_t)widest;
-  if (!out || width < widest || cap < Wn * width) return (int64_t)Wn;
-
-  DeviceGuard guard;
-  ENC_OK(hipSetDevice(device_));
-  const size_t piece = piece_ids();
+// Host examples, whose offset arrays, fit, Wn, width and cap the caller has settled on the host, so
+// no length pass runs on the device.  A piece is the emitted rows of its own examples, written to
+// rows [w0, w1) of the outputs; its ids are those of a plus those of b.  The piece's WO is made on
+// the host and uploaded, and row_win is written from it.
+int EncodeDevice::pair_host(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b, size_t n_b,
+                            const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id,
+                            int pad_side, int32_t* out, uint8_t* types, uint8_t* mask, int32_t* lengths,
+                            int32_t* win_row, int32_t* seg_len, int64_t* seg_src, int64_t* row_win) {
   PairState& ps = pass_state<PairState>(pass_[kPair]);
   hipStream_t st = (hipStream_t)stream_;
-  std::vector<int64_t> la, lb;
-  std::vector<u64> wo;
-  u64 w0 = 0;
-  if (row_win) row_win[0] = 0;
-  for (size_t r0 = 0; r0 < R;) {
-    wo.assign(1, 0);
-    size_t r1 = r0;
-    do {
-      wo.push_back(wo.back() + pr.count(r1));
-      ++r1;
-    } while (r1 < R && r1 - r0 < piece &&
-             (u64)(row_a[r1 + 1] - row_a[r0]) + (u64)(row_b[r1 + 1] - row_b[r0]) <= (u64)piece &&
-             (wo.back() + pr.count(r1)) * width <= 4 * (u64)piece);
-    const size_t m = r1 - r0, wp = (size_t)wo.back();
-    const size_t a = (size_t)row_a[r0], alen = (size_t)row_a[r1] - a, b = (size_t)row_b[r0], blen = (size_t)row_b[r1] - b;
-    const size_t cells = wp * width;
-    if (!tiles_fit(cells) || !ps.ha.grow(std::max<size_t>(alen, 1)) || !ps.hb.grow(std::max<size_t>(blen, 1)) ||
-        !ps.hrow.grow(m + 1, 2) || !ps.wo.grow(m + 1) || !ps.hout.grow(std::max<size_t>(cells, 1)) ||
-        !ps.hmeta.grow(wp, 4) || (seg_src && !ps.hsrc.grow(wp, 2)) ||
-        ((types || mask) && !ps.hbytes.grow(std::max<size_t>(cells, 1), 2))) {
-      std::fprintf(stderr, "[ERROR]\t encoder: pair staging allocation failed (%zu + %zu ids, %zu examples, %zu rows)\n",
-                   alen, blen, m, wp);
-      return -1;
-    }
-    int64_t *const dra = ps.hrow.get(), *const drb = dra + ps.hrow.cap();
-    int32_t *const dlen = ps.hmeta.get(), *const drow = dlen + ps.hmeta.cap(), *const dseg = drow + ps.hmeta.cap();
-    uint8_t *const dtypes = ps.hbytes.get(), *const dmask = dtypes + ps.hbytes.cap();
-    if (alen) ENC_OK(hipMemcpyAsync(ps.ha.get(), ids_a + a, alen * 4, hipMemcpyHostToDevice, st));
-    if (blen) ENC_OK(hipMemcpyAsync(ps.hb.get(), ids_b + b, blen * 4, hipMemcpyHostToDevice, st));
-    la.resize(m + 1);
-    lb.resize(m + 1);
-    for (size_t i = 0; i <= m; ++i) {
-      la[i] = row_a[r0 + i] - (int64_t)a;
-      lb[i] = row_b[r0 + i] - (int64_t)b;
-    }
-    ENC_OK(hipMemcpyAsync(dra, la.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    ENC_OK(hipMemcpyAsync(drb, lb.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    ENC_OK(hipMemcpyAsync(ps.wo.get(), wo.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    const Pairs local = pairs_of(o, dra, alen, drb, blen);
-    const PairOut po{ps.hout.get(), types ? dtypes : nullptr, mask ? dmask : nullptr, lengths ? dlen : nullptr,
-                     win_row ? drow : nullptr, seg_len ? dseg : nullptr, seg_src ? ps.hsrc.get() : nullptr};
-    if (ps.expand(ps.ha.get(), ps.hb.get(), local, m, wp, width, pad_id, pad_side, r0, a, b, po, st) < 0) return -1;
-    if (cells) ENC_OK(hipMemcpyAsync(out + w0 * width, po.out, cells * 4, hipMemcpyDeviceToHost, st));
-    if (types && cells) ENC_OK(hipMemcpyAsync(types + w0 * width, dtypes, cells, hipMemcpyDeviceToHost, st));
-    if (mask && cells) ENC_OK(hipMemcpyAsync(mask + w0 * width, dmask, cells, hipMemcpyDeviceToHost, st));
-    if (lengths) ENC_OK(hipMemcpyAsync(lengths + w0, dlen, wp * 4, hipMemcpyDeviceToHost, st));
-    if (win_row) ENC_OK(hipMemcpyAsync(win_row + w0, drow, wp * 4, hipMemcpyDeviceToHost, st));
-    if (seg_len) ENC_OK(hipMemcpyAsync(seg_len + 2 * w0, dseg, wp * 8, hipMemcpyDeviceToHost, st));
-    if (seg_src) ENC_OK(hipMemcpyAsync(seg_src + 2 * w0, ps.hsrc.get(), wp * 16, hipMemcpyDeviceToHost, st));
-    if (row_win)
-      for (size_t i = 1; i <= m; ++i) row_win[r0 + i] = (int64_t)(w0 + wo[i]);
-    ENC_OK(hipStreamSynchronize(st));
-    w0 += wp;
-    r0 = r1;
-  }
-  return (int64_t)Wn;
+  const Pairs host = pairs_of(o, row_a, n_a, row_b, n_b);
+  const HostCall call{"pair", rows, width, 2, {{ids_a, n_a, row_a}, {ids_b, n_b, row_b}}, true, row_win, 7,
+                      {{out, 4, 0, 1}, {types, 1, 0, 1}, {mask, 1, 0, 1}, {lengths, 4, 1, 0}, {win_row, 4, 1, 0},
+                       {seg_len, 4, 2, 0}, {seg_src, 8, 2, 0}}};
+  return host_pieces(
+      device_, st, call, [&](size_t r) { return host.count(r); },
+      [&](const Piece& p, Staged* s) {
+        const size_t m = p.r1 - p.r0;
+        if (!ps.ha.grow(std::max<size_t>(p.len[0], 1)) || !ps.hb.grow(std::max<size_t>(p.len[1], 1)) ||
+            !ps.hrow.grow(m + 1, 2) || !ps.sum.grow(m + 1) || !ps.hout.grow(std::max<size_t>(p.cells, 1)) ||
+            !ps.hmeta.grow(p.wp, 4) || (seg_src && !ps.hsrc.grow(p.wp, 2)) ||
+            ((types || mask) && !ps.hbytes.grow(std::max<size_t>(p.cells, 1), 2)))
+          return false;
+        *s = Staged{{ps.ha.get(), ps.hb.get()},
+                    {ps.hrow.get(), ps.hrow.get() + ps.hrow.cap()},
+                    ps.sum.get(),
+                    {ps.hout.get(), ps.hbytes.get(), ps.hbytes.get() + ps.hbytes.cap(), ps.hmeta.get(),
+                     ps.hmeta.get() + ps.hmeta.cap(), ps.hmeta.get() + 2 * ps.hmeta.cap(), ps.hsrc.get()}};
+        return true;
+      },
+      [&](const Piece& p, const Staged& s) {
+        const PairOut po{s.get<int32_t>(0), s.get<uint8_t>(1), s.get<uint8_t>(2), s.get<int32_t>(3),
+                         s.get<int32_t>(4), s.get<int32_t>(5), s.get<int64_t>(6)};
+        return ps.expand(s.ids[0], s.ids[1], pairs_of(o, s.row[0], p.len[0], s.row[1], p.len[1]), p.r1 - p.r0, p.wp,
+                         width, pad_id, pad_side, p.r0, p.a[0], p.a[1], po, st);
+      });
 }
 
 }  // namespace shred

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "pair_rule.h"
 
 namespace shred {
 
@@ -402,18 +403,22 @@ int batch_args(const ShredEncoder* enc, const void* ids, size_t n, const void* r
   return 0;
 }
 
+// An offset array of host rows: rows + 1 entries that start at 0, end at n and do not decrease.
+bool offsets_ok(const int64_t* row_off, size_t rows, size_t n) {
+  if (row_off[0] != 0 || row_off[rows] < 0 || (uint64_t)row_off[rows] != n) return false;
+  for (size_t r = 0; r < rows; ++r)
+    if (row_off[r] > row_off[r + 1]) return false;
+  return true;
+}
+
 // The length pass of host rows: 0 with T = sum e_r and the largest e_r, -6 for a bad row_off, -1
 // for an e_r past int32.
 int batch_host_lengths(size_t n, const int64_t* row_off, size_t rows, const shred::EncodeDevice::BatchOpts& o,
                        uint64_t* total, uint64_t* widest) {
   const uint64_t add = (o.has_bos ? 1 : 0) + (o.has_eos ? 1 : 0);
-  const uint64_t keep_max = o.max_len ? o.max_len - add : ~0ull;
+  const uint64_t keep_max = o.max_len ? o.max_len - add : shred::kNoLimit;
   *total = *widest = 0;
-  if (row_off) {
-    if (row_off[0] != 0 || row_off[rows] < 0 || (uint64_t)row_off[rows] != n) return -6;
-    for (size_t r = 0; r < rows; ++r)
-      if (row_off[r] > row_off[r + 1]) return -6;
-  }
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
   const size_t R = row_off ? rows : 1;
   for (size_t r = 0; r < R; ++r) {
     const uint64_t len = row_off ? (uint64_t)(row_off[r + 1] - row_off[r]) : (uint64_t)n;
@@ -555,6 +560,22 @@ int pair_args(const ShredEncoder* enc, const void* ids_a, size_t n_a, const void
                                      (uint64_t)max_len, trunc_side, strategy, (uint64_t)max_a, (uint64_t)stride};
   return 0;
 }
+
+// The length pass of host examples: 0 with Wn and the longest emitted row, -6 for a bad row_a or
+// row_b, -7 for an example that cannot fit, -1 for an e past int32.
+int pair_host_lengths(const shred::Pairs& pr, size_t rows, uint64_t* Wn, uint64_t* widest) {
+  *Wn = *widest = 0;
+  if (!offsets_ok(pr.ra, rows, pr.na) || !offsets_ok(pr.rb, rows, pr.nb)) return -6;
+  bool too_long = false;
+  for (size_t r = 0; r < rows; ++r) {
+    uint64_t ka, kb;
+    if (!pr.first((uint64_t)(pr.ra[r + 1] - pr.ra[r]), (uint64_t)(pr.rb[r + 1] - pr.rb[r]), &ka, &kb)) return -7;
+    too_long |= pr.too_long(ka, kb);
+    *widest = std::max(*widest, pr.add() + ka + kb);
+    *Wn += pr.count(r);
+  }
+  return too_long ? -1 : 0;
+}
 }  // namespace
 
 int64_t shred_pair_device(ShredEncoder* enc, const void* ids_a, size_t n_a, const void* row_a, const void* ids_b,
@@ -584,8 +605,15 @@ int64_t shred_pair_rows(ShredEncoder* enc, const int32_t* ids_a, size_t n_a, con
   if (pair_args(enc, ids_a, n_a, row_a, ids_b, n_b, row_b, rows, bos, mid, mid_n, eos, max_len, trunc_side, strategy,
                 max_a, stride, pad_side, win_row, &o))
     return -1;
-  return enc->dev->pair_host(ids_a, n_a, row_a, ids_b, n_b, row_b, rows, o, width, pad_id, pad_side, out, cap, types,
-                             mask, lengths, win_row, seg_len, seg_src, row_win, widest);
+  if (!shred::batch_rows_fit(rows)) return -1;
+  uint64_t Wn = 0, first = 0;
+  if (const int r = pair_host_lengths(shred::pairs_of(o, row_a, n_a, row_b, n_b), rows, &Wn, &first)) return r;
+  if (Wn > (uint64_t)INT64_MAX || (width && Wn > (uint64_t)INT64_MAX / width)) return -1;
+  if (widest) *widest = (size_t)first;
+  if (!out || width < first || cap < Wn * width) return (int64_t)Wn;
+  const int r = enc->dev->pair_host(ids_a, n_a, row_a, ids_b, n_b, row_b, rows, o, width, pad_id, pad_side, out, types,
+                                    mask, lengths, win_row, seg_len, seg_src, row_win);
+  return r < 0 ? r : (int64_t)Wn;
 }
 
 }  // extern "C"

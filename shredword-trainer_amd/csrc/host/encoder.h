@@ -39,6 +39,12 @@ constexpr uint64_t window_count(uint64_t len, uint64_t C, uint64_t step) {
   return len <= C ? 1 : 1 + (len - C + step - 1) / step;
 }
 
+// The batch calls (shred_pad_* .. shred_pair_*): "no limit" on the ids a row keeps, and the most
+// rows a call takes (its row kernels run one workgroup per kBatchRowsPerGroup rows).
+constexpr uint64_t kNoLimit = ~0ull;
+constexpr uint64_t kBatchRowsPerGroup = 256;
+constexpr bool batch_rows_fit(uint64_t rows) { return rows / kBatchRowsPerGroup < 0x7FFFFFFFull; }
+
 // What one family of passes owns on the device; the units derive theirs from the resources of
 // hip/encode_common.h.
 struct PassState {
@@ -174,9 +180,9 @@ class EncodeDevice {
   // ---- row pairs to one model input (batch_pair.hip; shred_pair_*).  The callers have checked the
   // arguments' ranges: mid_n <= 2, strategy in 0 .. 3, max_len == 0 or >= the added ids; strategies
   // 0 .. 2 come with max_a == stride == 0, strategy 3 with 0 < max_len <= INT32_MAX.  pair takes
-  // device buffers, pair_host host buffers (it settles row_a / row_b, the rows that cannot fit, Wn and
-  // the widest row on the host before anything is staged); both return Wn, -1, -6 or -7, with the
-  // longest emitted row in *widest.
+  // device buffers and returns Wn, -1, -6 or -7, with the longest emitted row in *widest; pair_host
+  // takes host buffers whose row_a / row_b, fit (host/pair_rule.h), width and cap the caller has
+  // checked on the host and returns 0 or -1.
   struct PairOpts {
     bool has_bos, has_eos;
     int32_t bos, eos, mid[2];
@@ -189,10 +195,10 @@ class EncodeDevice {
                const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id, int pad_side,
                int32_t* out, size_t cap, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row,
                int32_t* seg_len, int64_t* seg_src, int64_t* row_win, size_t* widest, void* stream, double* kernel_ms);
-  int64_t pair_host(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b, size_t n_b,
-                    const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id, int pad_side,
-                    int32_t* out, size_t cap, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row,
-                    int32_t* seg_len, int64_t* seg_src, int64_t* row_win, size_t* widest);
+  int pair_host(const int32_t* ids_a, size_t n_a, const int64_t* row_a, const int32_t* ids_b, size_t n_b,
+                const int64_t* row_b, size_t rows, const PairOpts& o, size_t width, int32_t pad_id, int pad_side,
+                int32_t* out, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row, int32_t* seg_len,
+                int64_t* seg_src, int64_t* row_win);
 
  private:
   EncodeDevice() = default;

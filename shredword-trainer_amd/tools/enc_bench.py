@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | special | docs | long] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -13,7 +13,10 @@ tensors, timed with device events in the same process after a warm-up; with a tr
 window_device (max_len 1024, stride 128, with the mask) on the corpus's ids and line offsets: device ms
 and effective GB/s by the traffic model of batch_device.hip, pad_device at the same width on the same
 rows (rows cut to 1024 ids: the same output size when no line is longer than a window), and a torch
-gather (an index of window starts plus columns, a masked take) on the same tensors; with a trailing `special`,
+gather (an index of window starts plus columns, a masked take) on the same tensors; with a trailing `pair`,
+pair_device (window_second, max_len 512, stride 128, bos, one sep, eos, with types and mask) on 65,536 seeded
+examples of 8..32 and 200..1500 random ids (the corpus is not used): device ms and effective GB/s by the traffic
+model of batch_pair.hip, checked against a torch gather of the same rows; with a trailing `special`,
 "<|endoftext|>" is put in front of the first '\\n' after every 2048th byte of the corpus, and that
 text is timed through encode_spans_device without and with specials=True (the encode, span and
 special passes of one call each); with a trailing `docs`, the corpus is one document per line (doc_offsets
@@ -66,8 +69,8 @@ else:
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
-    long_leg = args[-1] == "long"
-    if spans or decode or special or docs or window or long_leg:
+    long_leg, pair = args[-1] == "long", args[-1] == "pair"
+    if spans or decode or special or docs or window or long_leg or pair:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -343,4 +346,50 @@ else:
         nbytes = R * W * (4 + 4 * fill + 1) + 16 * R
         print("pad at the same width: rows", R, "fill", fill, "ms", ms[len(ms) // 2], "GB/s",
               nbytes / ms[len(ms) // 2] / 1e6, "min", ms[0], "max", ms[-1], flush=True)
+    if pair:
+        del out
+        reps = max(reps, 5)
+        R, M, S, BOS, SEP, EOS = 65536, 512, 128, 1, 2, 3
+        g = torch.Generator().manual_seed(5)
+        offs = lambda lens: torch.cat([lens.new_zeros(1), lens.cumsum(0)])
+        ra, rb = offs(torch.randint(8, 33, (R,), generator=g)), offs(torch.randint(200, 1501, (R,), generator=g))
+        ids_a, ids_b = (torch.randint(10, 50_000, (int(r[-1]),), generator=g, dtype=torch.int32).cuda() for r in (ra, rb))
+        ra, rb = ra.cuda(), rb.cuda()
+
+        def torch_pair():
+            la, lb = ra[1:] - ra[:-1], rb[1:] - rb[:-1]
+            C = M - 3 - la
+            step = C - S
+            w = torch.where(lb <= C, torch.ones_like(lb), 1 + (lb - C + step - 1) // step)
+            wo = offs(w)
+            Wn = int(wo[-1].item())
+            prow = torch.repeat_interleave(torch.arange(R, device="cuda"), w, output_size=Wn)
+            bsrc = rb[:-1][prow] + (torch.arange(Wn, device="cuda") - wo[:-1][prow]) * step[prow]
+            ka, asrc = la[prow], ra[:-1][prow]
+            kb = torch.minimum(rb[1:][prow] - bsrc, C[prow])
+            e = 3 + ka + kb
+            col = torch.arange(M, device="cuda")[None, :]
+            ja, jb = col - 1, col - 2 - ka[:, None]
+            out = torch.where(col < e[:, None], EOS, -1).to(torch.int32)  # the eos is what no other rule overwrites
+            out = torch.where((jb >= 0) & (jb < kb[:, None]), ids_b[(bsrc[:, None] + jb).clamp(0, ids_b.numel() - 1)], out)
+            out = torch.where(jb == -1, SEP, out)
+            out = torch.where((ja >= 0) & (ja < ka[:, None]), ids_a[(asrc[:, None] + ja).clamp(0, ids_a.numel() - 1)], out)
+            out[:, 0] = BOS
+            return (out, e.to(torch.int32), prow.to(torch.int32), torch.stack([ka, kb], 1).to(torch.int32),
+                    torch.stack([asrc, bsrc], 1), wo, ((jb >= 0) & (col < e[:, None])).to(torch.uint8),
+                    (col < e[:, None]).to(torch.uint8))
+
+        kw = dict(max_len=M, truncation="window_second", stride=S, bos=BOS, sep=(SEP,), eos=EOS, width=M, pad_id=-1,
+                  types=True, mask=True)
+        ours = enc.pair_device(ids_a, ra, ids_b, rb, **kw)  # first call: allocates the pair scratch
+        assert all(torch.equal(a, b) for a, b in zip(ours[:8], torch_pair()))
+        Wn = ours[0].shape[0]
+        for _ in range(5):
+            enc.pair_device(ids_a, ra, ids_b, rb, **kw)
+        ms = sorted(enc.pair_device(ids_a, ra, ids_b, rb, **kw)[8] for _ in range(reps))
+        fill = ours[1].sum().item() / (Wn * M)
+        nbytes = Wn * M * (4 + 4 * fill + 2) + 32 * Wn + 64 * R
+        print("pair: examples", R, "ids", ids_a.numel(), "+", ids_b.numel(), "emitted rows", Wn, "width", M, "stride", S,
+              "fill", fill, "ms", ms[len(ms) // 2], "GB/s", nbytes / ms[len(ms) // 2] / 1e6, "of 8 TB/s",
+              nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0], "max", ms[-1], flush=True)
     enc.destroy()

@@ -507,3 +507,92 @@ def test_encode_pairs_end_to_end(enc):
                     assert text[starts[side][k]:starts[side][k] + tok_len[tok]] == enc.decode([tok])
     with pytest.raises(ValueError):
         enc.encode_pairs(qs, ctx[:-1])
+
+
+# ---- 9. the identities the shared expansion rests on ---------------------------------------------
+
+def _short_rows(rng):
+    """BATCH_STAGE + 5 rows of 0 to 3 ids, with runs of empty rows."""
+    lens = rng.integers(0, 4, size=_stage() + 5)
+    lens[10:45] = 0
+    lens[300:302] = 0
+    return lens
+
+
+def _offset(n, dt, fill):
+    """A device buffer of n + 1 + 8 elements, to be written from element 1 on."""
+    import torch
+    return torch.full((n + 1 + 8,), fill, dtype=dt, device="cuda")
+
+
+def _inside(buf, Wn, W, fill):
+    """The [Wn, W] array written from element 1 of an _offset buffer; nothing else was touched."""
+    g = buf.cpu().numpy()
+    assert g[0] == fill and (g[1 + Wn * W:] == fill).all()
+    return g[1:1 + Wn * W].reshape(Wn, W)
+
+
+def test_window_is_a_pair_with_an_empty_first_row(enc):
+    """window_device == pair_device(truncation="window_second") on examples whose first rows are empty."""
+    import torch
+    from shredword.cbase import lib
+    rng = np.random.default_rng(21)
+    lens = np.concatenate([_short_rows(rng), [3 * _tile() + 1]])
+    row = _rows_of(lens)
+    R, added, M, S, W = lens.size, 2, 9, 2, 11
+    ids = torch.from_numpy(rng.integers(0, 50_000, size=int(row[-1])).astype(np.int32)).cuda()
+    row = torch.from_numpy(row).cuda()
+    ids_a, row_a = torch.empty(0, dtype=torch.int32, device="cuda"), torch.zeros(R + 1, dtype=torch.int64, device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    bos, eos = ctypes.c_int32(1), ctypes.c_int32(2)
+    for side, pad in enumerate(("right", "left")):
+        kw = dict(max_len=M, stride=S, bos=1, eos=2, pad=pad, pad_id=-1, width=W, mask=True)
+        win = [t.cpu().numpy() for t in enc.window_device(ids, row, **kw)[:6]]
+        par = [t.cpu().numpy() for t in enc.pair_device(ids_a, row_a, ids, row, truncation="window_second", sep=(), **kw)[:8]]
+        batch, lengths, wrow, wsrc, roww, mask = win
+        Wn = batch.shape[0]
+        assert Wn > R + 3 * _tile() // M and lengths.min() == added and lengths.max() == M
+        for name, a, b in (("batch", batch, par[0]), ("lengths", lengths, par[1]), ("rows", wrow, par[2]),
+                           ("row_windows", roww, par[5]), ("mask", mask, par[7])):
+            assert a.dtype == b.dtype and np.array_equal(a, b), (name, pad)
+        assert np.array_equal(par[4][:, 1], wsrc) and (par[3][:, 0] == 0).all()
+        assert np.array_equal(par[3][:, 1], lengths - added)
+        types = mask.copy()
+        types[np.arange(Wn), W - lengths if side else 0] = 0  # the bos column
+        assert np.array_equal(par[6], types), pad
+        # both into views offset by one element (the scalar stores), through the raw ABI
+        wb, wm = _offset(Wn * W, torch.int32, SENT), _offset(Wn * W, torch.uint8, 0xA5)
+        pb, pt, pm = _offset(Wn * W, torch.int32, SENT), _offset(Wn * W, torch.uint8, 0xA5), _offset(Wn * W, torch.uint8, 0xA5)
+        assert wb[1:].data_ptr() % 16 == 4 and pb[1:].data_ptr() % 16 == 4
+        assert all(t[1:].data_ptr() % 4 == 1 for t in (wm, pt, pm))
+        r = lib.shred_window_device(enc.enc, ids.data_ptr(), ids.numel(), row.data_ptr(), R, ctypes.byref(bos),
+                                    ctypes.byref(eos), M, S, W, -1, side, wb[1:].data_ptr(), Wn * W, None, wm[1:].data_ptr(),
+                                    None, None, None, None, st, None)
+        assert r == Wn
+        r = lib.shred_pair_device(enc.enc, ids_a.data_ptr(), 0, row_a.data_ptr(), ids.data_ptr(), ids.numel(),
+                                  row.data_ptr(), R, ctypes.byref(bos), None, 0, ctypes.byref(eos), M, 0, 3, 0, S, W, -1, side,
+                                  pb[1:].data_ptr(), Wn * W, pt[1:].data_ptr(), pm[1:].data_ptr(), None, None, None, None,
+                                  None, None, st, None)
+        assert r == Wn
+        assert np.array_equal(_inside(wb, Wn, W, SENT), batch) and np.array_equal(_inside(pb, Wn, W, SENT), batch)
+        assert np.array_equal(_inside(wm, Wn, W, 0xA5), mask) and np.array_equal(_inside(pm, Wn, W, 0xA5), mask)
+        assert np.array_equal(_inside(pt, Wn, W, 0xA5), types)
+
+
+def test_pad_is_a_window_of_rows_that_fit(enc):
+    """pad_device(max_len=M) == window_device(max_len=M, stride=0) on rows none longer than M - added."""
+    import torch
+    rng = np.random.default_rng(22)
+    lens = _short_rows(rng)
+    row = _rows_of(lens)
+    ids = torch.from_numpy(rng.integers(0, 50_000, size=int(row[-1])).astype(np.int32)).cuda()
+    row = torch.from_numpy(row).cuda()
+    for pad in ("right", "left"):
+        kw = dict(max_len=6, bos=1, eos=2, pad=pad, pad_id=-1, mask=True)
+        assert lens.max() <= 6 - 2
+        p = [t.cpu().numpy() for t in enc.pad_device(ids, row, **kw)[:3]]
+        w = [t.cpu().numpy() for t in enc.window_device(ids, row, stride=0, **kw)[:6]]
+        assert p[0].shape == (lens.size, 5)
+        for name, a, b in (("batch", p[0], w[0]), ("lengths", p[1], w[1]), ("mask", p[2], w[5])):
+            assert a.dtype == b.dtype and np.array_equal(a, b), (name, pad)
+        assert np.array_equal(w[2], np.arange(lens.size))
