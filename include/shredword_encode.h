@@ -581,6 +581,111 @@ int64_t shred_pair_rows(ShredEncoder* enc, const int32_t* ids_a, size_t n_a, con
                         uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row, int32_t* seg_len,
                         int64_t* seg_src, int64_t* row_win, size_t* widest);
 
+/* ---- masked-LM inputs on the GPU: per token or per whole word -------------------------------------
+ *
+ * The masked-language-model objective (BERT / RoBERTa pre-training, ELECTRA generators) selects some
+ * tokens, replaces most of them, and asks the model for the originals.  These calls work on the flat
+ * (ids, row_off) pair, before pad, pack, window or pair, and so compose with all four: the caller pads
+ * the masked ids as usual and pads the labels with pad_id = bos = eos (= mid) = ignore_id, which the
+ * batch calls allow because they never look ids up.  Truncation and windowing then agree between the
+ * two, because both use the same row_off.
+ *
+ * Inputs:
+ *   ids         n int32.
+ *   row_off     the usual rows + 1 int64, or NULL with rows == 0 for one row; validated as elsewhere (-6).
+ *   starts      with whole_word != 0: n int64, as shred_encode_spans / shred_encode_docs return them
+ *               (NULL with n > 0 then returns -1).  Not read otherwise, and may be NULL.
+ *   opts        the scalar options, ShredMlmOpts below:
+ *     index_base        uint64 added to every index below.  The host call's pieces use it; a caller
+ *                       sharding a stream over calls may use it too.
+ *     p, seed           selection probability in [0, 1] and a 64-bit seed.
+ *     p_mask, p_random  of the selected tokens: the share replaced by mask_id, and the share replaced
+ *                       by a random id.  The rest keep their id.  Both lie in [0, 1] and their sum is
+ *                       at most 1.
+ *     mask_id           any int32.
+ *     rand_vocab        random replacements are uniform in [0, rand_vocab).  Required in
+ *                       [1, INT32_MAX] when p_random > 0.
+ *     protect, protect_n  host pointer to at most SHRED_MLM_MAX_PROTECT int32 ids that are never
+ *                       selected (unk, a pad id already present, and so on).
+ *     protect_specials  non-zero: the K registered specials (ids in [256 + M, 256 + M + K)) are never
+ *                       selected either.
+ *     whole_word        non-zero: tokens are selected by whole words.
+ *     ignore_id         label of every token not selected.  Callers pass -100.
+ *
+ * Definitions, with mix = fmix64 exactly as in the dropout section and G = 0x9E3779B97F4A7C15:
+ *   d(x, c) = mix(mix(seed + G * (x + 1)) ^ c), with the constants SEL = 1 << 40 and
+ *             ACT = (1 << 40) + 1.  They are above every merge rank, so the same seed used for
+ *             dropout and for masking gives unrelated draws.
+ *   T(q)    = (uint64_t)(q * 4294967296.0), computed in double.  T(p_mask) + T(p_random) > 2^32
+ *             returns -1.
+ *   Unit of token k: without whole_word, h(k) = index_base + k.  With it, h(k) = index_base + k',
+ *             where k' is the largest k' <= k at which a word begins.  A word begins by the rule of
+ *             the sections above, with one addition.  Token k begins a word iff
+ *               k == 0, or k is the first token of its row, or
+ *               ids[k] or ids[k-1] is a registered special, or
+ *               starts[k] != starts[k-1] + len(ids[k-1]), where len is that of the token-lengths
+ *               table (1 for ids below 256, for negative ids and for ids past the table), or
+ *               ids[k] or ids[k-1] is protected (the protect list, and the specials under
+ *               protect_specials).  This is the addition: a protected id is a unit of its own.
+ *   Token k is selected iff ids[k] is not protected and (d(h(k), SEL) >> 32) < T(p).  All
+ *             unprotected tokens of a word therefore fall together.
+ *   For a selected token, let a = d(index_base + k, ACT) and v = a >> 32.
+ *             If v < T(p_mask):                    out[k] = mask_id.
+ *             Else if v < T(p_mask) + T(p_random): out[k] = (int32)(((a & 0xFFFFFFFF) * rand_vocab) >> 32).
+ *             Else                                 out[k] = ids[k].
+ *             labels[k] = ids[k].  The action is drawn per token, also inside a whole word.
+ *   A token not selected has out[k] = ids[k] and labels[k] = ignore_id.
+ *
+ * A decision depends on (seed, index, ids, starts) alone: the same arguments give the same result on
+ * host and device calls alike and for every staging, and a new seed (per epoch, say) a new masking.
+ *
+ * Returns the number of selected tokens.  Errors, with nothing written: -1 bad argument (a
+ * probability outside [0, 1] or NaN, T(p_mask) + T(p_random) > 2^32, protect_n above the limit,
+ * rand_vocab out of range with p_random > 0, whole_word without starts, labels aliasing ids or out)
+ * or HIP error; -4 whole-word mode with a byte map holding an id >= 256 (lengths undefined, as for
+ * spans); -6 bad row_off.  (A HIP error after the first piece of shred_mlm_rows leaves the earlier
+ * pieces' output in place.)
+ *
+ * out may be the same buffer as ids (in place).  labels must not alias either.  p == 0 is legal: a
+ * copy, all labels ignore_id, returns 0.
+ *
+ * The masking scratch (two result words, events, the host call's staging, and in whole-word mode 9 B
+ * per id for the word begins and k') is allocated on the first masking call and freed with the
+ * encoder, so the other calls' footprints are unchanged.  Whole-word mode reads the token-lengths
+ * table of the span passes on the device and uploads it if no spans call has.
+ */
+#define SHRED_MLM_MAX_PROTECT 16
+
+typedef struct ShredMlmOpts {
+  uint64_t index_base;
+  double p;
+  uint64_t seed;
+  double p_mask, p_random;
+  int32_t mask_id;
+  int32_t ignore_id;
+  int64_t rand_vocab;
+  const int32_t* protect;
+  size_t protect_n;
+  int protect_specials;
+  int whole_word;
+} ShredMlmOpts;
+
+/* All buffers on the encoder's device (row_off is validated there, and a bad one keeps the later
+ * passes from writing); queued on `stream` (NULL = the encoder's own) and synchronised before
+ * return.  ids, out and labels need only their element's alignment, so tensor views fit.  kernel_ms
+ * (may be NULL) receives the device time of the passes. */
+int64_t shred_mlm_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const ShredMlmOpts* opts, const void* starts, void* out, void* labels, void* stream,
+                         double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget
+ * of the batch calls, so device memory does not grow with n (one row is taken whole, however long).
+ * Each piece runs the device passes with index_base + the index of its first id; because words never
+ * cross rows and positions are global, the result is the same for every piece size.  row_off is
+ * validated on the host before anything is staged. */
+int64_t shred_mlm_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const ShredMlmOpts* opts, const int64_t* starts, int32_t* out, int32_t* labels);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -21,7 +21,8 @@ constexpr int kLane = 4;                   // int32 entries per lane: one 16-byt
 constexpr int kTile = kThreads * kLane;    // output entries per workgroup (BATCH_TILE)
 constexpr int kStage = 512;                // rows staged in LDS per round (BATCH_STAGE)
 
-__global__ __launch_bounds__(kThreads) void k_bat_row_start(const u64* __restrict__ E, u64 rows, u64 base,
+// (not every unit writes a prefix sum out)
+[[maybe_unused]] __global__ __launch_bounds__(kThreads) void k_bat_row_start(const u64* __restrict__ E, u64 rows, u64 base,
                                                             int64_t* __restrict__ row_start) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r <= rows) row_start[r] = (int64_t)(base + E[r]);

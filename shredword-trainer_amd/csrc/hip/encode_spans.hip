@@ -208,12 +208,17 @@ struct SpanState : PassState {
 
   void specials_changed() override { lens.reset(); }
 
-  bool reserve(size_t n, size_t T, const std::vector<int32_t>& host_lens) {
+  bool upload_lens(const std::vector<int32_t>& host_lens) {
     if (!lens.get() && (!lens.grow(host_lens.size()) || hipMemcpy(lens.get(), host_lens.data(), host_lens.size() * 4,
                                                                    hipMemcpyHostToDevice) != hipSuccess)) {
       lens.reset();
       return false;
     }
+    return true;
+  }
+
+  bool reserve(size_t n, size_t T, const std::vector<int32_t>& host_lens) {
+    if (!upload_lens(host_lens)) return false;
     const size_t nb = (n + kChunk - 1) / kChunk;
     if (!host.ensure(4) || !ev.ensure() || !cnt.grow(nb, 4) || !prefix.grow(T)) return false;
     size_t a = 0, b = 0;
@@ -226,6 +231,11 @@ struct SpanState : PassState {
 };
 
 }  // namespace
+
+const int32_t* EncodeDevice::span_lens(const std::vector<int32_t>& lens) {
+  SpanState& sp = pass_state<SpanState>(pass_[kSpans]);
+  return sp.upload_lens(lens) ? sp.lens.get() : nullptr;
+}
 
 int EncodeDevice::span_passes(const uint8_t* text, size_t n, const int32_t* ids, size_t T, int64_t* starts,
                               int64_t* line, size_t line_cap, uint64_t start_base, uint64_t id_base,

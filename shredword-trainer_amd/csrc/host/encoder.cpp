@@ -616,4 +616,49 @@ int64_t shred_pair_rows(ShredEncoder* enc, const int32_t* ids_a, size_t n_a, con
   return r < 0 ? r : (int64_t)Wn;
 }
 
+namespace {
+// T(q) of the masking section, or ~0 for a q outside [0, 1] (NaN included).
+uint64_t mlm_threshold(double q) { return q >= 0 && q <= 1 ? (uint64_t)(q * 4294967296.0) : ~0ull; }
+
+// What the two masking calls refuse before any work (0, -1 or -4), and their options.
+int mlm_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+             const ShredMlmOpts* o, const void* starts, const void* out, const void* labels,
+             shred::EncodeDevice::MaskOpts* m) {
+  if (!enc || !o || (n && (!ids || !out || !labels)) || (!row_off && rows)) return -1;
+  if (n && (labels == ids || labels == out)) return -1;
+  const uint64_t t_sel = mlm_threshold(o->p), t_mask = mlm_threshold(o->p_mask), t_rand = mlm_threshold(o->p_random);
+  if (t_sel == ~0ull || t_mask == ~0ull || t_rand == ~0ull || t_mask + t_rand > (1ull << 32)) return -1;
+  if (o->protect_n > SHRED_MLM_MAX_PROTECT || (o->protect_n && !o->protect)) return -1;
+  if (o->p_random > 0 && (o->rand_vocab < 1 || o->rand_vocab > (int64_t)INT32_MAX)) return -1;
+  if (o->whole_word && n && !starts) return -1;
+  if (o->whole_word && !enc->spans_ok) return -4;
+  const int32_t sp_lo = (int32_t)(256 + enc->first.size());
+  *m = shred::EncodeDevice::MaskOpts{o->index_base, o->seed, t_sel, t_mask, t_mask + t_rand,
+                                     o->p_random > 0 ? (uint64_t)o->rand_vocab : 0, o->mask_id, o->ignore_id,
+                                     sp_lo, (int32_t)(sp_lo + enc->num_specials), o->protect_specials != 0,
+                                     o->whole_word != 0, (uint32_t)o->protect_n, {}};
+  for (size_t i = 0; i < o->protect_n; ++i) m->protect[i] = o->protect[i];
+  return 0;
+}
+}  // namespace
+
+int64_t shred_mlm_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const ShredMlmOpts* opts, const void* starts, void* out, void* labels, void* stream,
+                         double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::MaskOpts o;
+  if (const int r = mlm_args(enc, ids, n, row_off, rows, opts, starts, out, labels, &o)) return r;
+  return enc->dev->mask((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, (const int64_t*)starts, enc->lens,
+                        (int32_t*)out, (int32_t*)labels, stream, kernel_ms);
+}
+
+int64_t shred_mlm_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const ShredMlmOpts* opts, const int64_t* starts, int32_t* out, int32_t* labels) {
+  shred::EncodeDevice::MaskOpts o;
+  if (const int r = mlm_args(enc, ids, n, row_off, rows, opts, starts, out, labels, &o)) return r;
+  if (!shred::batch_rows_fit(rows)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  return enc->dev->mask_host(ids, n, row_off, rows, o, starts, enc->lens, out, labels);
+}
+
 }  // extern "C"

@@ -200,8 +200,33 @@ class EncodeDevice {
                 int32_t* out, uint8_t* types, uint8_t* mask, int32_t* lengths, int32_t* win_row, int32_t* seg_len,
                 int64_t* seg_src, int64_t* row_win);
 
+  // ---- masked-LM inputs (batch_mask.hip; shred_mlm_*).  The callers have checked the arguments'
+  // ranges and turned the probabilities into thresholds.  mask takes device buffers (starts: nullptr
+  // unless o.whole_word) and returns the selected count, -1 or -6; mask_host takes host buffers whose
+  // row_off the caller has checked on the host and returns the selected count or -1.  lens: as
+  // encode_spans takes it (whole-word mode reads the span passes' copy on the device).
+  static constexpr int kMaskMaxProtect = 16;  // SHRED_MLM_MAX_PROTECT
+  struct MaskOpts {
+    uint64_t index_base, seed;
+    uint64_t t_sel, t_mask, t_act;  // T(p), T(p_mask), T(p_mask) + T(p_random) <= 2^32
+    uint64_t rand_vocab;
+    int32_t mask_id, ignore_id;
+    int32_t sp_lo, sp_hi;           // the registered specials are the ids [sp_lo, sp_hi)
+    bool protect_specials, whole_word;
+    uint32_t protect_n;
+    int32_t protect[kMaskMaxProtect];
+  };
+  int64_t mask(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MaskOpts& o,
+               const int64_t* starts, const std::vector<int32_t>& lens, int32_t* out, int32_t* labels, void* stream,
+               double* kernel_ms);
+  int64_t mask_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MaskOpts& o,
+                    const int64_t* starts, const std::vector<int32_t>& lens, int32_t* out, int32_t* labels);
+
  private:
   EncodeDevice() = default;
+  // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
+  // not there (the first use, or after set_specials); nullptr when that fails.
+  const int32_t* span_lens(const std::vector<int32_t>& lens);
   // Span passes over n text bytes and their T ids (both on the device): starts[k] = start_base +
   // byte offset, line[q + 1] = id_base + id offset of the line after the q-th '\n' (line[0] is
   // not written; line_cap entries).  *newlines / *last_byte: the text's '\n' count and last byte.
@@ -237,7 +262,8 @@ class EncodeDevice {
   bool sx_dirty_ = false;          // the scan table on the device is older than the set
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
-  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kPasses };
+  enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
+              kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -225,3 +225,16 @@ lib.shred_pair_device.argtypes = _pair_rows + [c_void_p, POINTER(c_double)]
 lib.shred_pair_device.restype = c_int64
 lib.shred_pair_rows.argtypes = _pair_rows
 lib.shred_pair_rows.restype = c_int64
+# masked-LM inputs: ids, n, row_off, rows, opts, starts, out, labels
+class ShredMlmOpts(ctypes.Structure):
+    _fields_ = [("index_base", c_uint64), ("p", c_double), ("seed", c_uint64), ("p_mask", c_double),
+                ("p_random", c_double), ("mask_id", c_int32), ("ignore_id", c_int32), ("rand_vocab", c_int64),
+                ("protect", POINTER(c_int32)), ("protect_n", c_size_t), ("protect_specials", c_int),
+                ("whole_word", c_int)]
+
+
+_mlm_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredMlmOpts), c_void_p, c_void_p, c_void_p]
+lib.shred_mlm_device.argtypes = _mlm_rows + [c_void_p, POINTER(c_double)]
+lib.shred_mlm_device.restype = c_int64
+lib.shred_mlm_rows.argtypes = _mlm_rows
+lib.shred_mlm_rows.restype = c_int64

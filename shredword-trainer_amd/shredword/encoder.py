@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from .cbase import lib
+from .cbase import ShredMlmOpts, lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
@@ -31,6 +31,7 @@ BATCH_TILE = 1024
 BATCH_STAGE = 512
 # batch_pair.hip: the strategies of shred_pair_*, by number
 PAIR_TRUNCATION = ("longest_first", "only_first", "only_second", "window_second")
+MLM_MAX_PROTECT = 16   # SHRED_MLM_MAX_PROTECT
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -836,6 +837,131 @@ class BPEEncoder:
         (ia, ra, sa), (ib, rb, sb) = sides
         res = self.pair_device(ia, ra, ib, rb, **kw)
         return res + ((sa, sb) if starts else ())
+
+    # ---- masked-LM inputs (include/shredword_encode.h, shred_mlm_*) ---------------------------------
+
+    def _mlm_opts(self, mask_id, p, seed, mask_prob, random_prob, random_vocab, protect, protect_specials, whole_word,
+                  ignore_id, index_base):
+        """-> (ShredMlmOpts as the C ABI takes it, the array its protect pointer keeps alive)."""
+        p, pm, pr = float(p), float(mask_prob), float(random_prob)
+        for name, q in (("p", p), ("mask_prob", pm), ("random_prob", pr)):
+            if not 0.0 <= q <= 1.0:
+                raise ValueError(f"{name} must be a probability in [0, 1]")
+        if int(pm * 4294967296.0) + int(pr * 4294967296.0) > 2 ** 32:
+            raise ValueError("mask_prob + random_prob must be at most 1")
+        rv = 256 + self.num_merges if random_vocab is None else int(random_vocab)
+        if pr > 0 and not 1 <= rv < 2 ** 31:
+            raise ValueError("random_vocab must be in [1, INT32_MAX] when random_prob > 0")
+        prot = np.array([self._int32("protect", v) for v in protect], dtype=np.int32)
+        if prot.size > MLM_MAX_PROTECT:
+            raise ValueError(f"protect holds at most {MLM_MAX_PROTECT} ids")
+        base = int(index_base)
+        if not 0 <= base < 2 ** 64:
+            raise ValueError("index_base must fit a uint64")
+        opts = ShredMlmOpts(base, p, int(seed) & (2 ** 64 - 1), pm, pr, self._int32("mask_id", mask_id),
+                            self._int32("ignore_id", ignore_id), rv if pr > 0 else 0,
+                            prot.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if prot.size else None, prot.size,
+                            int(bool(protect_specials)), int(bool(whole_word)))
+        return opts, prot
+
+    def _check_mlm(self, r: int) -> int:
+        if r == -4:
+            raise ValueError("the byte map holds an id >= 256: token lengths are undefined")
+        return self._check_batch(r)
+
+    def mlm_rows(self, ids, row_offsets=None, *, mask_id, p=0.15, seed=0, mask_prob=0.8, random_prob=0.1,
+                 random_vocab=None, protect=(), protect_specials=True, whole_word=False, starts=None, ignore_id=-100,
+                 index_base=0):
+        """-> (masked_ids, labels, selected): masked-language-model inputs of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row), before pad / pack / window / pair.  Every
+        token is selected with probability p; of the selected, the share mask_prob becomes mask_id, the
+        share random_prob a uniform id in [0, random_vocab) (None: 256 + num_merges) and the rest keep
+        their id; labels holds the original id of a selected token and ignore_id elsewhere.  protect: up
+        to 16 ids that are never selected; protect_specials: nor are the registered special tokens.
+        whole_word: the tokens of a word are selected together (starts: the byte offsets encode_spans /
+        encode_docs return for the ids; a row's first token, a special and a protected id begin a word).
+        A decision is a function of (seed, index_base + the token's index) alone: the same arguments
+        always give the same result, on host and device calls alike, and a new seed (one per epoch, say)
+        a new masking.  Pad the labels with pad_id = bos = eos = ignore_id.  Built on the GPU."""
+        opts, _keep = self._mlm_opts(mask_id, p, seed, mask_prob, random_prob, random_vocab, protect,
+                                     protect_specials, whole_word, ignore_id, index_base)
+        a, row, R = self._host_rows(ids, row_offsets)
+        st = None
+        if whole_word:
+            if starts is None:
+                raise ValueError("whole_word needs starts, one byte offset per id")
+            st = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+            if st.size != a.size:
+                raise ValueError("whole_word needs starts, one byte offset per id")
+        out, labels = np.empty(max(1, a.size), dtype=np.int32), np.empty(max(1, a.size), dtype=np.int32)
+        r = self._check_mlm(lib.shred_mlm_rows(self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data,
+                                               0 if row is None else R, ctypes.byref(opts),
+                                               None if st is None else st.ctypes.data, out.ctypes.data,
+                                               labels.ctypes.data))
+        return out[:a.size], labels[:a.size], r
+
+    def mlm_device(self, ids, row_offsets=None, *, mask_id, p=0.15, seed=0, mask_prob=0.8, random_prob=0.1,
+                   random_vocab=None, protect=(), protect_specials=True, whole_word=False, starts=None, ignore_id=-100,
+                   index_base=0, out=None, stream=None):
+        """mlm_rows on device tensors (ids 1-D int32, row_offsets and starts 1-D int64, on the encoder's GPU;
+        views that are only element-aligned fit) -> (masked_ids, labels, selected, device milliseconds of the
+        masking passes).  out: None, or an int32 tensor for the masked ids; out=ids masks in place."""
+        import torch
+        opts, _keep = self._mlm_opts(mask_id, p, seed, mask_prob, random_prob, random_vocab, protect,
+                                     protect_specials, whole_word, ignore_id, index_base)
+        R = self._device_rows(ids, row_offsets)
+        n = ids.numel()
+        for name, t, dt in (("starts", starts if whole_word else None, torch.int64), ("out", out, torch.int32)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                    or not t.is_contiguous() or t.device != ids.device or t.numel() != n:
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} tensor of len(ids) entries on the ids' device")
+        if whole_word and starts is None:
+            raise ValueError("whole_word needs starts, one byte offset per id")
+        if out is None:
+            out = torch.empty(max(1, n), dtype=torch.int32, device=ids.device)[:n]
+        labels = torch.empty(max(1, n), dtype=torch.int32, device=ids.device)[:n]
+        ms = ctypes.c_double()
+        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        r = self._check_mlm(lib.shred_mlm_device(
+            self.enc, ids.data_ptr(), n, None if row_offsets is None else row_offsets.data_ptr(),
+            0 if row_offsets is None else R, ctypes.byref(opts), starts.data_ptr() if whole_word else None,
+            out.data_ptr(), labels.data_ptr(), st, ctypes.byref(ms)))
+        return out, labels, r, ms.value
+
+    def encode_mlm(self, text, *, mask_id, p=0.15, seed=0, mask_prob=0.8, random_prob=0.1, random_vocab=None,
+                   protect=(), protect_specials=True, whole_word=False, ignore_id=-100, index_base=0,
+                   doc_offsets=None, specials: bool = False, **pad_kw):
+        """Text to masked-LM model inputs on the GPU: encode_docs_device (one row per document of a list /
+        tuple, or per doc_offsets entry of one text; None: one document), mlm_device, then pad_device twice
+        with **pad_kw (bos, eos, max_len, truncate, pad_id, pad, width): the masked ids with the caller's
+        bos / eos / pad_id, the labels with ignore_id in their place.  -> (batch, labels, lengths,
+        attention_mask, selected): int32 [rows, width] twice, int32 [rows], uint8 [rows, width] tensors on
+        the encoder's device, and the number of selected tokens (before any truncation)."""
+        import torch
+        if isinstance(text, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(text)
+        else:
+            buf = self._host_text(text)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        pad_kw.pop("mask", None)
+        d_buf = torch.from_numpy(np.array(buf)).cuda(self.device)
+        d_off = None if off is None else torch.from_numpy(np.array(off)).cuda(self.device)
+        ids, row, st, _ = self.encode_docs_device(d_buf, d_off, starts=whole_word, specials=specials)
+        masked, labels, selected, _ = self.mlm_device(
+            ids, row, mask_id=mask_id, p=p, seed=seed, mask_prob=mask_prob, random_prob=random_prob,
+            random_vocab=random_vocab, protect=protect, protect_specials=protect_specials, whole_word=whole_word,
+            starts=st, ignore_id=ignore_id, index_base=index_base)
+        batch, lengths, attn, _ = self.pad_device(masked, row, mask=True, **pad_kw)
+        lab_kw = dict(pad_kw, pad_id=ignore_id, width=batch.shape[1])
+        for k in ("bos", "eos"):
+            if lab_kw.get(k) is not None:
+                lab_kw[k] = ignore_id
+        lab_batch = self.pad_device(labels, row, **lab_kw)[0]
+        return batch, lab_batch, lengths, attn, selected
 
     def destroy(self):
         if getattr(self, "enc", None):

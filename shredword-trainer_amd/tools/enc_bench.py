@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -28,7 +28,12 @@ per line, as one document and as 16 documents), and beside a copy of 1 GiB, whic
 a trailing `long`, the long-word mode (long_words=True): encode_device on the corpus as it is (no long word: the
 cost of the find pass, against the first line's time with the mode off), on the corpus with the delimiters of a
 4 KB stretch taken out after every 64 KB (one long word per 64 KB), and on single words of 4 KB, 64 KB and 1 MB
-cut from the corpus without its delimiters, with the rounds each word took."""
+cut from the corpus without its delimiters, with the rounds each word took; with a trailing `mlm`, mlm_device on
+2^26 seeded ids of the vocabulary in rows of 200..500 (the corpus is not used), per token and per whole word (starts
+from the token lengths, a delimiter before 30 % of the tokens), p = 0.15 with four protected ids: device ms (median of
+7 after two warm-up calls) and GB/s by the traffic model of batch_mask.hip, beside the torch composition on the same
+tensors in the same process (rand for selection and action, an isin protect mask, where for ids and labels; whole
+words: begins from starts, a cumsum for the word of every token and one draw per word gathered back)."""
 import os
 import subprocess
 import sys
@@ -69,8 +74,8 @@ else:
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
-    long_leg, pair = args[-1] == "long", args[-1] == "pair"
-    if spans or decode or special or docs or window or long_leg or pair:
+    long_leg, pair, mlm = args[-1] == "long", args[-1] == "pair", args[-1] == "mlm"
+    if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
     reps = int(args[1]) if len(args) > 1 else 5
@@ -392,4 +397,70 @@ else:
         print("pair: examples", R, "ids", ids_a.numel(), "+", ids_b.numel(), "emitted rows", Wn, "width", M, "stride", S,
               "fill", fill, "ms", ms[len(ms) // 2], "GB/s", nbytes / ms[len(ms) // 2] / 1e6, "of 8 TB/s",
               nbytes / ms[len(ms) // 2] / 1e6 / 8000, "min", ms[0], "max", ms[-1], flush=True)
+    if mlm:
+        del out
+        reps = max(reps, 7)
+        n, P, MASK, IGN = 1 << 26, 0.15, 4, -100
+        V = 256 + enc.num_merges
+        g = torch.Generator().manual_seed(7)
+        rl = torch.randint(200, 501, (n // 350 + 1,), generator=g)
+        row = torch.cat([rl.new_zeros(1), rl.cumsum(0)])
+        row = torch.cat([row[row < n], row.new_tensor([n])]).cuda()
+        ids = torch.randint(5, V, (n,), generator=g, dtype=torch.int32).cuda()
+        lens_t = torch.from_numpy(enc.token_lengths).cuda()
+        tl = lens_t[ids.long()].long()
+        gap = (torch.rand(n, generator=g) < 0.3).cuda().long()  # a delimiter before the token: words of 3.3 tokens
+        gap[0] = 0
+        starts = (tl.cumsum(0) - tl + gap.cumsum(0)).contiguous()
+        del tl, gap
+        prot = torch.tensor([0, 1, 2, 3], dtype=torch.int32, device="cuda")
+
+        def events(fn):
+            """median / min / max device ms of fn() over reps runs, after two warm-up runs"""
+            for _ in range(2):
+                fn()
+            ms = []
+            for _ in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            ms.sort()
+            return ms[len(ms) // 2], ms[0], ms[-1]
+
+        def torch_apply(sel):
+            """the collator's tail: labels, then 80 % mask, 10 % random, 10 % kept"""
+            labels = torch.where(sel, ids, IGN)
+            act = torch.rand(n, device="cuda")
+            rnd = torch.randint(0, V, (n,), dtype=torch.int32, device="cuda")
+            return torch.where(sel & (act < 0.8), MASK, torch.where(sel & (act < 0.9), rnd, ids)), labels
+
+        def torch_token():
+            return torch_apply((torch.rand(n, device="cuda") < P) & ~torch.isin(ids, prot))
+
+        def torch_whole():
+            """word begins from starts, the rows and the protected ids; one draw per word, gathered per token"""
+            guarded = torch.isin(ids, prot)
+            begin = torch.ones(n, dtype=torch.bool, device="cuda")
+            begin[1:] = (starts[1:] != starts[:-1] + lens_t[ids[:-1].long()]) | guarded[1:] | guarded[:-1]
+            begin[row[:-1]] = True
+            word = begin.cumsum(0) - 1
+            return torch_apply((torch.rand(int(word[-1].item()) + 1, device="cuda")[word] < P) & ~guarded)
+
+        kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
+        for name, whole, per_id, ref in (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole)):
+            run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
+            run()  # first call: allocates the masking scratch
+            run()
+            res = [run() for _ in range(reps)]
+            ms = sorted(r[3] for r in res)
+            med = ms[len(ms) // 2]
+            t, c = events(ref), events(run)
+            picked = int((ref()[1] != IGN).sum().item())
+            print("mlm", name + ": ids", n, "rows", row.numel() - 1, "selected", res[0][2], "share", res[0][2] / n,
+                  "| ms", med, "GB/s at", per_id, "B per id", per_id * n / med / 1e6, "min", ms[0], "max", ms[-1],
+                  "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1], "max", t[2],
+                  "selected share", picked / n, "| torch / ours", t[0] / med, flush=True)
     enc.destroy()
