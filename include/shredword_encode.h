@@ -145,6 +145,9 @@ int64_t shred_encode(ShredEncoder* enc, const uint8_t* text, size_t n, int32_t* 
 
 /* The same on device buffers (text: n bytes, out: cap >= n int32, both on the encoder's device),
  * queued on `stream` (a hipStream_t, NULL = the encoder's own) and synchronised before return.
+ * The encoder's own stream is non-blocking: it is not ordered with the legacy default stream (the
+ * handle 0, which therefore cannot be named here), so in every *_device call a caller with work
+ * pending on that stream synchronises it first; the Python layer does (BPEEncoder._stream).
  * Same return values; kernel_ms (may be NULL) receives the device time of the encode passes. */
 int64_t shred_encode_device(ShredEncoder* enc, const void* text, size_t n, void* out, size_t cap,
                             void* stream, double* kernel_ms);

@@ -184,6 +184,21 @@ class BPEEncoder:
         return r
 
     @staticmethod
+    def _stream(stream, device):
+        """The hipStream_t of a device call as the C ABI takes it: `stream` (a handle), or for None the
+        caller's current torch stream on `device`.  The handle 0, torch's default stream, reads as "no
+        stream given" in the C ABI, which then queues on the encoder's own non-blocking stream; that
+        stream is not ordered with the legacy default stream.  So work already queued there (the
+        producer of the call's inputs, say) is waited for here, and the call, which synchronises its
+        stream before it returns, is ordered behind it."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        if not stream:
+            torch.cuda.default_stream(device).synchronize()
+        return ctypes.c_void_p(stream)
+
+    @staticmethod
     def _host_text(text) -> np.ndarray:
         if isinstance(text, str):
             text = text.encode("utf-8")
@@ -214,9 +229,9 @@ class BPEEncoder:
         elif out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.device != text.device:
             raise ValueError("out must be a contiguous int32 tensor on the text's device")
         ms = ctypes.c_double()
-        st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
+        st = self._stream(stream, text.device)
         r = self._check(lib.shred_encode_device(self.enc, text.data_ptr(), n, out.data_ptr(), out.numel(),
-                                                ctypes.c_void_p(st), ctypes.byref(ms)))
+                                                st, ctypes.byref(ms)))
         return out[:r], ms.value
 
     def _spans_host(self, text, want_starts, want_lines, specials=False):
@@ -266,12 +281,12 @@ class BPEEncoder:
             if lines else None
         ms = (ctypes.c_double * 3)()
         nl = ctypes.c_size_t()
-        st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
+        st = self._stream(stream, text.device)
         call = lib.shred_encode_special_device if specials else lib.shred_encode_spans_device
         r = self._check(call(
             self.enc, text.data_ptr(), n, out.data_ptr(), out.numel(),
             None if st_t is None else st_t.data_ptr(), None if ln_t is None else ln_t.data_ptr(),
-            0 if ln_t is None else ln_t.numel(), ctypes.byref(nl), ctypes.c_void_p(st), ms))
+            0 if ln_t is None else ln_t.numel(), ctypes.byref(nl), st, ms))
         return (out[:r], None if st_t is None else st_t[:r], None if ln_t is None else ln_t[:nl.value + 1],
                 (ms[0], ms[1], ms[2]) if specials else (ms[0], ms[1]))
 
@@ -330,11 +345,11 @@ class BPEEncoder:
         st_t = torch.empty(max(1, n), dtype=torch.int64, device=text.device) if starts else None
         row = torch.empty((docs if doc_offsets is not None else 1) + 1, dtype=torch.int64, device=text.device)
         ms = (ctypes.c_double * 4)()
-        st = stream if stream is not None else torch.cuda.current_stream(text.device).cuda_stream
+        st = self._stream(stream, text.device)
         r = self._check_docs(lib.shred_encode_docs_device(
             self.enc, text.data_ptr(), n, None if doc_offsets is None else doc_offsets.data_ptr(), docs,
             int(bool(specials)), out.data_ptr(), out.numel(), None if st_t is None else st_t.data_ptr(),
-            row.data_ptr(), ctypes.c_void_p(st), ms))
+            row.data_ptr(), st, ms))
         return out[:r], row, None if st_t is None else st_t[:r], (ms[0], ms[1], ms[2], ms[3])
 
     def decode(self, ids) -> bytes:
@@ -410,7 +425,7 @@ class BPEEncoder:
             raise ValueError("row_offsets must hold rows + 1 entries")
         s, u, ul = self._decode_args(sep, unk)
         rows = 0 if row_offsets is None else row_offsets.numel() - 1
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        st = self._stream(stream, ids.device)
         args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(), rows)
         ms0, ms1 = ctypes.c_double(), ctypes.c_double()
         need = lib.shred_decode_device(*args, None, 0, None, s, u, ul, st, ctypes.byref(ms0))
@@ -540,7 +555,7 @@ class BPEEncoder:
             raise ValueError('pad must be "left" or "right"')
         b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
         R = self._device_rows(ids, row_offsets)
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        st = self._stream(stream, ids.device)
         args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
                 0 if row_offsets is None else R, b, e, ml, ts)
         ps = int(pad == "left")
@@ -570,7 +585,7 @@ class BPEEncoder:
         L = int(seq_len)
         b, e, ml, ts, pid = self._batch_args(bos, eos, max_len, truncate, pad_id)
         R = self._device_rows(ids, row_offsets)
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        st = self._stream(stream, ids.device)
         args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
                 0 if row_offsets is None else R, b, e, ml, ts, L, pid, int(bool(drop_last)))
         ms = ctypes.c_double()
@@ -643,7 +658,7 @@ class BPEEncoder:
         import torch
         b, e, ml, sd, pid, ps = self._window_args(bos, eos, max_len, stride, pad_id, pad)
         R = self._device_rows(ids, row_offsets)
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        st = self._stream(stream, ids.device)
         args = (self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
                 0 if row_offsets is None else R, b, e, ml, sd)
         widest, ms = ctypes.c_size_t(), ctypes.c_double()
@@ -795,7 +810,7 @@ class BPEEncoder:
         R = self._device_rows(ids_a, row_a)
         if R != self._device_rows(ids_b, row_b):
             raise ValueError("row_a and row_b must hold the same number of rows")
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids_a.device).cuda_stream)
+        st = self._stream(stream, ids_a.device)
         args = (self.enc, ids_a.data_ptr(), ids_a.numel(), row_a.data_ptr(), ids_b.data_ptr(), ids_b.numel(),
                 row_b.data_ptr(), R) + head
         widest, ms = ctypes.c_size_t(), ctypes.c_double()
@@ -923,7 +938,7 @@ class BPEEncoder:
             out = torch.empty(max(1, n), dtype=torch.int32, device=ids.device)[:n]
         labels = torch.empty(max(1, n), dtype=torch.int32, device=ids.device)[:n]
         ms = ctypes.c_double()
-        st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(ids.device).cuda_stream)
+        st = self._stream(stream, ids.device)
         r = self._check_mlm(lib.shred_mlm_device(
             self.enc, ids.data_ptr(), n, None if row_offsets is None else row_offsets.data_ptr(),
             0 if row_offsets is None else R, ctypes.byref(opts), starts.data_ptr() if whole_word else None,
