@@ -11,8 +11,8 @@
 //   k_collect      K4  touched delta slots -> host records       (FreqChangeMap, bpe.cpp:9-50)
 //   k_unmerge      rollback of a chain's unconfirmed merges
 //
-// Device's other methods: pair_count.hip (K1, K6, probes), resident_loop.hip (k_resident);
-// hip_common.h holds what the units share.
+// Device's other methods: pair_count.hip (K1, K6, probes).  The resident loop (resident_loop.hip)
+// and the indexed loop (word_loop.hip) are classes Device drives; hip_common.h holds what the units share.
 //
 // Deltas are staged in per-workgroup LDS hash tables and spilled to HBM tables
 // with 64-bit atomics (sum) and atomicMin (first touch), so the reduction is order-free and the
@@ -919,6 +919,7 @@ Device::Device(int device_ordinal) : ordinal_(device_ordinal) {
   hipStream_t s;
   HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   stream_ = s;
+  res_.set_stream(stream_);
   HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   aux_stream_ = s;
   for (auto& e : ev_) {
@@ -956,8 +957,6 @@ Device::Device(int device_ordinal) : ordinal_(device_ordinal) {
   if (const char* e = std::getenv("SHREDWORD_RESIDENT")) resident_on_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("SHREDWORD_INDEX")) index_on_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("SHREDWORD_HYBRID")) hybrid_ = std::atoi(e) != 0;
-  if (const char* e = std::getenv("SHREDWORD_RESIDENT_ARRIVE_POLLS")) res_arrive_polls_ = (uint32_t)std::strtoul(e, nullptr, 10);
-  if (const char* e = std::getenv("SHREDWORD_RESIDENT_REGION_KEYS")) res_region_keys_ = (uint32_t)std::strtoul(e, nullptr, 10);
   if (const char* e = std::getenv("SHREDWORD_SWITCH_OCC")) switch_occ_ = std::strtoull(e, nullptr, 10);
   int nb = 0;  // resident workgroups of k_merge per CU
   HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_merge<true>), kThreads, 0));
@@ -1037,16 +1036,12 @@ void Device::free_all() {
 
 Device::~Device() {
   (void)hipSetDevice(ordinal_);
-  if (res_running_ && res_posted_.empty()) park();
+  if (res_.running() && !res_.in_flight()) park();
   delete wl_;  // ends its launch first
   wl_ = nullptr;
   (void)hipStreamSynchronize(S(stream_));
   drain_retired();  // aborted resident launches: their late workgroups leave first
-  free_resident();
-  if (res_mbox_) (void)hipHostFree(res_mbox_);
-  if (res_status_) (void)hipHostFree(res_status_);
-  for (auto e : res_ev_)
-    if (e) (void)hipEventDestroy((hipEvent_t)e);
+  res_.free_plan();
   (void)hipStreamSynchronize(S(stream_));
   (void)hipStreamSynchronize(S(aux_stream_));
   free_all();
@@ -1147,7 +1142,8 @@ void Device::upload(const TiledStream& ts, Layout layout, const std::vector<uint
   tph[4] = now_seconds();
   reset_tokens();
   tph[5] = now_seconds();
-  plan_resident(ts);
+  if (layout_ == Layout::kTypes) res_.plan(ts, tok_, tile_off_, tile_len_, weight_, cu_count_, &bytes_alloc_);
+  else res_.free_plan();
   tph[6] = now_seconds();
   if (report)
     std::fprintf(stderr, "[LOAD] device upload: tables + copies %.1f ms, host-visible slots %.1f ms, tile index %.1f ms, "
@@ -1159,6 +1155,21 @@ void Device::upload(const TiledStream& ts, Layout layout, const std::vector<uint
 void Device::set_index(bool on) {
   park();
   index_on_ = on;
+}
+
+// Both persistent loops end; the tiles in HBM are current.
+void Device::park() {
+  index_sync();
+  if (!res_.running()) return;
+  HIP_OK(hipSetDevice(ordinal_));
+  double ms = 0;
+  const uint64_t merges = res_.stop(&ms);
+  if (timing_ && merges) {  // one launch: its wall time is the merge loop's device time
+    times_.merge_ms += ms;
+    times_.merge_launches += merges;
+    times_.res_ms += ms;
+  }
+  rebuild_signatures();  // the tiles are back in HBM: their pair signatures for k_merge / k_unmerge
 }
 
 // The indexed loop's launch ends and the tile stream catches up with its words (the tile
@@ -1333,11 +1344,93 @@ int Device::device_select(const std::vector<PairCount>& pairs, int32_t X0, int n
 
 bool Device::index_id_room(int32_t max_id) const { return wl_ && (uint32_t)max_id + 2 <= wl_->id_room(); }
 
+// merge_chain's resident branch: one merge (ab[0], ab[1]) -> X0 posted to the launch.
+void Device::post_resident_merge(const int32_t* ab, int32_t X0) {
+  if (res_.in_flight() >= (size_t)kResSlots) fatal("merge_chain: every resident slot has a merge in flight");
+  const int slot = res_.running() && res_.aborted() ? -1 : res_.pick_slot();
+  if (slot < 0) {  // the launch aborted (not co-resident): this merge and those in flight go elsewhere
+    resident_abort_fallback();
+    merge_chain(ab, 1, X0);
+    return;
+  }
+  bool grow = false;
+  for (const MergeSlot& s2 : slot_) grow |= !s2.dsum || (uint32_t)X0 + 2 > s2.cap;
+  if (grow) {  // the delta tables grow: only between launches
+    if (res_.in_flight()) fatal("merge_chain: delta tables too small with a resident merge in flight");
+    park();
+    for (MergeSlot& s2 : slot_) ensure_slots(s2, (uint32_t)X0 + 2);
+    uint32_t cap = 0;
+    for (const MergeSlot& s2 : slot_) cap = std::max(cap, s2.cap);
+    for (MergeSlot& s2 : slot_) ensure_slots(s2, cap);
+  }
+  max_id_seen_ = std::max(max_id_seen_, X0);
+  visited_tiles_ += res_.post_merge(slot, ab[0], ab[1], X0, skip_ ? &index_ : nullptr);
+}
+
+// collect's resident branch: what merge X, seen complete, means for the tile index, the
+// statistics and the hybrid switch.
+size_t Device::collect_resident(int32_t X, const DeltaRecord** recs) {
+  ResidentLoop::Collected c;
+  if (!res_.collect(X, &c)) {
+    resident_abort_fallback();
+    return collect(X, recs);
+  }
+  const uint64_t* hs = c.hs;
+  if (c.n_tiles == kAllTiles) index_.set_all(X);
+  else index_.set_tiles_bits(X, c.tiles, c.n_tiles);
+  if (res_.stamps() && merge_log_)  // diagnostic: host post / flag-seen clock beside the device's dispatch / flag
+    std::fprintf(merge_log_, "S %d %u %.2f %.2f %.2f %llu %llu %zu %u\n", X, c.nparts, 1e6 * c.t_post, 1e6 * c.t_wait,
+                 1e6 * c.t_flag, (unsigned long long)hs[8], (unsigned long long)(hs[8] + hs[2]), c.n, c.n_tiles);
+  if (timing_) {
+    times_.merge_bytes += 4.0 * (double)live_tokens_est_;
+    times_.res_bytes += 4.0 * (double)live_tokens_est_;
+    times_.res_k3_bytes += 8.0 * (double)hs[1];  // hs[1]: tokens the merge's matched tiles hold after it
+    times_.res_merges += 1;
+  }
+  if (hybrid_ && !idx_phase_ && index_on_ && wl_ && wl_->ready()) {
+    // entries merged per merge is far from monotone (a frequent pair of a few common words sits
+    // between pairs spread over many words): switch once a whole window of merges stayed small
+    sw_win_[sw_n_++ % kSwitchWindow] = hs[0];
+    uint64_t mx = 0;
+    for (uint64_t v : sw_win_) mx = std::max(mx, v);
+    if (sw_n_ >= kSwitchWindow && mx < switch_occ_) switch_pending_ = true;
+  }
+  live_tokens_est_ -= hs[0];
+  records_total_ += c.n;
+  records_max_ = std::max<uint64_t>(records_max_, c.n);
+  *recs = c.recs;
+  return c.n;
+}
+
+// The resident launch aborted before dispatching anything (some workgroups never became
+// resident: another kernel or process holds CUs).  Resident is off for this device from here on;
+// the merges posted to it run again, in order, on the indexed loop (or the launch path).  The
+// launch's missing workgroups may start only once those CUs free up, and they hold its stream
+// until then, so all further work moves to a fresh stream.
+void Device::resident_abort_fallback() {
+  const std::vector<ResidentLoop::Post> inflight = res_.abandon();
+  res_.disable();
+  ++res_aborts_;
+  retired_streams_.push_back(stream_);
+  hipStream_t s;
+  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  stream_ = s;
+  res_.set_stream(stream_);
+  if (wl_) wl_->set_stream(stream_);
+  if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
+    std::fprintf(stderr, "[RESIDENT] launch aborted (not every workgroup resident): %zu merges move to the %s\n",
+                 inflight.size(), wl_ && wl_->ready() ? "indexed loop" : "launch path");
+  for (const ResidentLoop::Post& rp : inflight) {
+    const int32_t ab[2] = {rp.a, rp.b};
+    merge_chain(ab, 1, rp.X);
+  }
+}
+
 void Device::merge_chain(const int32_t* ab, int n, int32_t X0) {
   HIP_OK(hipSetDevice(ordinal_));
   if (n < 1 || n > kChainMax) fatal("merge_chain: bad chain length");
-  if (switch_pending_ && n == 1 && run_count_ == 0 && res_posted_.empty()) hybrid_switch(X0);
-  if (n == 1 && index_eligible() && run_count_ == 0 && res_posted_.empty()) {  // the indexed loop
+  if (switch_pending_ && n == 1 && run_count_ == 0 && !res_.in_flight()) hybrid_switch(X0);
+  if (n == 1 && index_eligible() && run_count_ == 0 && !res_.in_flight()) {  // the indexed loop
     if (words_stale_) index_refresh();
     if (!wl_->in_flight()) wl_->reserve(X0);
     max_id_seen_ = std::max(max_id_seen_, X0);
@@ -1660,7 +1753,7 @@ size_t Device::collect(int32_t X, const DeltaRecord** recs) {
     records_max_ = std::max<uint64_t>(records_max_, n);
     return n;
   }
-  if (!res_posted_.empty()) return collect_resident(X, recs);
+  if (res_.in_flight()) return collect_resident(X, recs);
   if (run_count_ == 0) fatal("collect: no launch in flight");
   ChainRun& run = run_at(0);
   const int j = X - run.X0;
@@ -1688,8 +1781,8 @@ void Device::rollback(int32_t X) {
     ++rollbacks_;
     return;
   }
-  if (!res_posted_.empty()) {  // resident: each wrong guess is expanded back where it matched
-    undo_resident_from(X);
+  if (res_.in_flight()) {  // resident: each wrong guess is expanded back where it matched
+    rollbacks_ += res_.rollback(X);
     return;
   }
   park();
@@ -1798,7 +1891,7 @@ void Device::reserve_ids(int32_t max_id) {
   bool grow = false;
   for (const MergeSlot& s : slot_) grow |= !s.dsum || need > s.cap;
   if (!grow) return;
-  if (!res_posted_.empty() || run_count_ > 0) return;  // later: merge_chain grows on demand
+  if (res_.in_flight() || run_count_ > 0) return;  // later: merge_chain grows on demand
   park();
   for (MergeSlot& s : slot_) ensure_slots(s, need);
   // the slots share keys_per_merge_: size them alike

@@ -1,13 +1,13 @@
-// MI355X (gfx950) whole-chip resident merge loop: k_resident and the part of the Device class
-// (device.h) that plans, launches and talks to it.  bpe_device.hip chooses between this loop, the
-// indexed loop (word_loop.hip) and the launch path; hip_common.h holds what the units share.
+// MI355X (gfx950) whole-chip resident merge loop: k_resident and ResidentLoop (resident_loop.h),
+// the host class that plans, launches and talks to it.  Device (bpe_device.hip) chooses between this
+// loop, the indexed loop (word_loop.hip) and the launch path, and decides what a collected merge or
+// an aborted launch means; hip_common.h holds what the units share.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstring>
 
-#include "../host/device.h"
-#include "../host/dist.h"
+#include "../host/resident_loop.h"
 #include "hip_common.h"
 
 namespace shred {
@@ -45,7 +45,6 @@ constexpr uint32_t kResRing = 16;
 constexpr uint32_t kResGatherWg = 1, kResFirstWorker = 2;
 constexpr int kResGatherBatch = 16;  // records per gatherer thread per round trip
 constexpr int kResThreadsHbm = 512;  // k_resident block size when the tokens stay in HBM
-constexpr uint32_t kAllTiles = 0xFFFFFFFFu;  // hcount[2]: merge X matched (nearly) every tile
 static_assert(kResDeltaW < (1 << 12) && kResMaxTiles * kWaveTok < (1u << 22), "region header fields (k_resident)");
 constexpr uint32_t kOpUnmerge = 4;
 // k_resident: not every workgroup became resident within the leader's bound (another kernel or
@@ -107,7 +106,7 @@ struct ResParams {
   uint32_t region_keys;      // a participant with more LDS delta keys adds them to the global tables
   uint32_t mt_dense;         // more matched tiles than this: the host index marks X in every tile
   uint32_t mt_words;         // the matched tiles go to the host as a bitmap of this many u32 words
-  ResSlot sl[Device::kResSlots];  // merge X uses sl[X % kResSlots]
+  ResSlot sl[ResidentLoop::kSlots];  // merge X uses sl[X % kSlots]
   uint32_t* dbg;      // diagnostic (SHREDWORD_RESIDENT_DEBUG): per workgroup [phase, last seq, pi, T]
   u64* stamps;        // diagnostic: per participant [go seen, work done, loop cycles, -] (s_memrealtime)
 };
@@ -131,7 +130,7 @@ __device__ __forceinline__ void q_pack(uint32_t cnt, uint32_t pi, uint32_t op, u
 }
 
 // sm = the tile signature's bit count - 1 (kResSigBits, or a half / quarter of it when the table
-// needs a smaller LDS plan: Device::plan_resident)
+// needs a smaller LDS plan: ResidentLoop::plan)
 __device__ __forceinline__ void res_sig_bits(int32_t x, int32_t y, uint32_t* h1, uint32_t* h2, uint32_t sm) {
   uint32_t k = (uint32_t)x * 0x9E3779B1u ^ ((uint32_t)y + 0x7F4A7C15u) * 0x85EBCA77u;
   k ^= k >> 15;
@@ -988,23 +987,37 @@ __global__ __launch_bounds__(kLdsTok ? 256 : kResThreadsHbm) void k_resident(Res
 
 // ==========================================================================================
 // k_resident host side: plan (which workgroup holds which tiles in LDS), launch, post, collect,
-// roll back, park.  See the kernel's comment for the protocol.
-void Device::free_resident() {
-  drain_retired();
-  for (void* p : {(void*)res_wg_tiles_, (void*)res_wg_rank_, (void*)res_tile_lofs_, (void*)res_cmd_, (void*)res_q_,
-                  (void*)res_dbg_, (void*)res_stamps_, (void*)res_arrive_})
-    if (p) HIP_OK(hipFree(p));
-  res_wg_tiles_ = res_wg_rank_ = res_tile_lofs_ = res_cmd_ = res_arrive_ = nullptr;
-  res_q_ = nullptr;
-  res_dbg_ = nullptr;
-  res_stamps_ = nullptr;
-  resident_ok_ = false;
+// roll back, stop.  See the kernel's comment for the protocol.
+ResidentLoop::ResidentLoop(int ordinal, const MergeSlot* slots, uint32_t& seq, const uint32_t& keys_per_merge)
+    : ordinal_(ordinal), slot_(slots), seq_(seq), keys_per_merge_(keys_per_merge) {
+  if (const char* e = std::getenv("SHREDWORD_RESIDENT_ARRIVE_POLLS")) arrive_polls_ = (uint32_t)std::strtoul(e, nullptr, 10);
+  if (const char* e = std::getenv("SHREDWORD_RESIDENT_REGION_KEYS")) region_keys_ = (uint32_t)std::strtoul(e, nullptr, 10);
 }
 
-void Device::plan_resident(const TiledStream& ts) {
-  free_resident();
-  if (layout_ != Layout::kTypes || ntiles_ == 0) return;
-  const uint32_t G = (uint32_t)std::min(cu_count_, kMaxMergeGroups);
+ResidentLoop::~ResidentLoop() {
+  free_plan();
+  if (mbox_) (void)hipHostFree(mbox_);
+  if (status_) (void)hipHostFree(status_);
+  for (auto e : ev_)
+    if (e) (void)hipEventDestroy((hipEvent_t)e);
+}
+
+void ResidentLoop::free_plan() {
+  for (void* p : {(void*)wg_tiles_, (void*)wg_rank_, (void*)tile_lofs_, (void*)cmd_, (void*)q_, (void*)dbg_,
+                  (void*)stamps_, (void*)arrive_})
+    if (p) HIP_OK(hipFree(p));
+  wg_tiles_ = wg_rank_ = tile_lofs_ = cmd_ = arrive_ = dbg_ = nullptr;
+  q_ = stamps_ = nullptr;
+  ok_ = false;
+}
+
+void ResidentLoop::plan(const TiledStream& ts, int32_t* tok, const uint64_t* tile_off, uint32_t* tile_len,
+                        const uint64_t* weight, int cu_count, size_t* bytes) {
+  free_plan();
+  tok_ = tok, tile_off_ = tile_off, tile_len_ = tile_len, weight_ = weight;
+  ntiles_ = ts.num_tiles();
+  if (ntiles_ == 0) return;
+  const uint32_t G = (uint32_t)std::min(cu_count, kMaxMergeGroups);
   if (G < kResFirstWorker + 1) return;
   const uint32_t W = G - kResFirstWorker;  // workers 2 .. G-1 (0 dispatches, 1 gathers)
   int max_lds = 0;
@@ -1066,7 +1079,6 @@ void Device::plan_resident(const TiledStream& ts) {
     wg_tiles.assign(G + 1, 0);
     wg_rank.assign(G + 1, 0);
     lofs.assign(T, 0);
-    res_owner_.assign(T, 0);
     double pre = 0;
     uint32_t w = kResFirstWorker;
     for (size_t t = 0; t < T; ++t) {
@@ -1074,17 +1086,16 @@ void Device::plan_resident(const TiledStream& ts) {
       uint32_t want = kResFirstWorker + (uint32_t)std::min<double>(W - 1, std::floor((pre + c / 2) * W / total));
       if (want < w) want = w;
       while (w < want) wg_tiles[++w] = (uint32_t)t;
-      res_owner_[t] = w;
       pre += c;
     }
     while (w < G) wg_tiles[++w] = (uint32_t)T;
     tok_words = 0;
     nr_max = 0;
     uint32_t nt_max = 0;
-    res_wg_ntiles_.assign(G, 0);
+    wg_ntiles_.assign(G, 0);
     for (uint32_t g = 0; g < G; ++g) {
       const uint32_t a = wg_tiles[g], b = wg_tiles[g + 1];
-      res_wg_ntiles_[g] = b - a;
+      wg_ntiles_[g] = b - a;
       nt_max = std::max(nt_max, b - a);
       uint32_t o = 0;
       for (uint32_t t = a; t < b; ++t) {
@@ -1107,95 +1118,90 @@ void Device::plan_resident(const TiledStream& ts) {
     fit = (long)shm <= bud;
   }
   if (!fit) return;
-  res_lds_tok_ = lds_tok;
-  res_sig_words_ = sw;
-  res_w_global_ = w_global;
-  res_grid_ = G;
-  res_tok_words_ = tok_words;
-  res_w_words_ = nr_max;
-  res_shm_ = shm;
-  res_all_.clear();
-  for (uint32_t g = kResFirstWorker; g < G; ++g) res_all_.push_back(g);
-  res_wg_first_ = wg_tiles;
-  res_wg_tiles_ = dalloc<uint32_t>(G + 1, &bytes_alloc_);
-  res_wg_rank_ = dalloc<uint32_t>(G + 1, &bytes_alloc_);
-  res_tile_lofs_ = dalloc<uint32_t>(T, &bytes_alloc_);
-  res_cmd_ = dalloc<uint32_t>(kResRing * 8, &bytes_alloc_);
-  res_q_ = dalloc<uint64_t>((size_t)G * kResRing * 2, &bytes_alloc_);
-  res_arrive_ = dalloc<uint32_t>(16, &bytes_alloc_);
-  HIP_OK(hipMemcpy(res_wg_tiles_, wg_tiles.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(res_wg_rank_, wg_rank.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(res_tile_lofs_, lofs.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_OK(hipMemset(res_cmd_, 0, kResRing * 8 * sizeof(uint32_t)));
+  lds_tok_ = lds_tok;
+  sig_words_ = sw;
+  w_global_ = w_global;
+  grid_ = G;
+  tok_words_ = tok_words;
+  w_words_ = nr_max;
+  shm_ = shm;
+  all_.clear();
+  for (uint32_t g = kResFirstWorker; g < G; ++g) all_.push_back(g);
+  wg_first_ = wg_tiles;
+  wg_tiles_ = dalloc<uint32_t>(G + 1, bytes);
+  wg_rank_ = dalloc<uint32_t>(G + 1, bytes);
+  tile_lofs_ = dalloc<uint32_t>(T, bytes);
+  cmd_ = dalloc<uint32_t>(kResRing * 8, bytes);
+  q_ = dalloc<uint64_t>((size_t)G * kResRing * 2, bytes);
+  arrive_ = dalloc<uint32_t>(16, bytes);
+  HIP_OK(hipMemcpy(wg_tiles_, wg_tiles.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(wg_rank_, wg_rank.data(), (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(tile_lofs_, lofs.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(cmd_, 0, kResRing * 8 * sizeof(uint32_t)));
   if (std::getenv("SHREDWORD_RESIDENT_DEBUG")) {
-    res_dbg_ = dalloc<uint32_t>((size_t)G * 4, &bytes_alloc_);
-    HIP_OK(hipMemset(res_dbg_, 0, (size_t)G * 16));
+    dbg_ = dalloc<uint32_t>((size_t)G * 4, bytes);
+    HIP_OK(hipMemset(dbg_, 0, (size_t)G * 16));
   }
-  if (const char* e = std::getenv("SHREDWORD_RESIDENT_STAMPS")) {
-    res_stamps_ = dalloc<uint64_t>((size_t)G * 8, &bytes_alloc_);
-    HIP_OK(hipMemset(res_stamps_, 0, (size_t)G * 64));
-    res_stamp_detail_ = std::atoi(e) >= 2;
+  if (std::getenv("SHREDWORD_RESIDENT_STAMPS")) {
+    stamps_ = dalloc<uint64_t>((size_t)G * 8, bytes);
+    HIP_OK(hipMemset(stamps_, 0, (size_t)G * 64));
   }
-  if (!res_mbox_) {
+  if (!mbox_) {
     const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
-    HIP_OK(hipHostMalloc(&res_mbox_, sizeof(ResMbox), pin));
-    std::memset(res_mbox_, 0, sizeof(ResMbox));
-    HIP_OK(hipHostGetDevicePointer(&res_mbox_dev_, res_mbox_, 0));
-    HIP_OK(hipHostMalloc((void**)&res_status_, 64, pin));
-    std::memset(res_status_, 0, 64);
-    HIP_OK(hipHostGetDevicePointer(&res_status_dev_, res_status_, 0));
-    for (auto& e : res_ev_) {
+    HIP_OK(hipHostMalloc(&mbox_, sizeof(ResMbox), pin));
+    std::memset(mbox_, 0, sizeof(ResMbox));
+    HIP_OK(hipHostGetDevicePointer(&mbox_dev_, mbox_, 0));
+    HIP_OK(hipHostMalloc((void**)&status_, 64, pin));
+    std::memset(status_, 0, 64);
+    HIP_OK(hipHostGetDevicePointer(&status_dev_, status_, 0));
+    for (auto& e : ev_) {
       hipEvent_t ev;
       HIP_OK(hipEventCreate(&ev));
       e = ev;
     }
   }
-  const void* kfn = res_lds_tok_ ? reinterpret_cast<const void*>(&k_resident<true, true>)
-                                 : reinterpret_cast<const void*>(&k_resident<true, false>);
+  const void* kfn = lds_tok_ ? reinterpret_cast<const void*>(&k_resident<true, true>)
+                             : reinterpret_cast<const void*>(&k_resident<true, false>);
   HIP_OK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   int per_cu = 0;  // the persistent grid must be co-resident: at least one workgroup per CU
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, res_lds_tok_ ? 256 : kResThreadsHbm, shm));
-  if (per_cu < 1 || (long)per_cu * cu_count_ < (long)G) return;
-  resident_ok_ = true;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, lds_tok_ ? 256 : kResThreadsHbm, shm));
+  if (per_cu < 1 || (long)per_cu * cu_count < (long)G) return;
+  ok_ = true;
   if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
     std::fprintf(stderr, "[RESIDENT] plan: grid %u, %zu B of LDS per workgroup, %d per CU; tokens in %s, weights in %s, "
-                 "%u-bit tile signatures\n", G, (size_t)shm, per_cu, res_lds_tok_ ? "LDS" : "HBM",
-                 res_w_global_ ? "HBM" : "LDS", 32u * res_sig_words_);
+                 "%u-bit tile signatures\n", G, (size_t)shm, per_cu, lds_tok_ ? "LDS" : "HBM",
+                 w_global_ ? "HBM" : "LDS", 32u * sig_words_);
 }
 
-void Device::set_resident(bool on) {
-  park();
-  resident_on_ = on;
-}
-
-void Device::start_resident() {
+void ResidentLoop::start() {
   ResParams rp;
   rp.tok = tok_;
   rp.tile_off = tile_off_;
   rp.tile_len = tile_len_;
   rp.weight = weight_;
-  rp.wg_tiles = res_wg_tiles_;
-  rp.wg_rank = res_wg_rank_;
-  rp.tile_lofs = res_tile_lofs_;
-  rp.tok_words = res_tok_words_;
-  rp.w_words = res_w_words_;
-  rp.sig_words = res_sig_words_;
-  rp.w_global = res_w_global_ ? 1u : 0u;
-  rp.mbox = (const ResMbox*)res_mbox_dev_;
-  rp.cmd = res_cmd_;
-  rp.q = reinterpret_cast<u64*>(res_q_);
-  rp.status = (uint32_t*)res_status_dev_;
-  rp.arrive = res_arrive_;
-  rp.arrive_polls = res_arrive_polls_;
+  rp.wg_tiles = wg_tiles_;
+  rp.wg_rank = wg_rank_;
+  rp.tile_lofs = tile_lofs_;
+  rp.tok_words = tok_words_;
+  rp.w_words = w_words_;
+  rp.sig_words = sig_words_;
+  rp.w_global = w_global_ ? 1u : 0u;
+  rp.mbox = (const ResMbox*)mbox_dev_;
+  rp.cmd = cmd_;
+  rp.q = reinterpret_cast<u64*>(q_);
+  rp.status = (uint32_t*)status_dev_;
+  rp.arrive = arrive_;
+  rp.arrive_polls = arrive_polls_;
   rp.seq0 = seq_ + 1;
   rp.leader_polls = 1u << 23;  // ~10 s without a command: the launch ends itself (the host relaunches)
   rp.keys_per_merge = keys_per_merge_;
-  rp.slot_cap = min_slot_cap();
-  rp.region_keys = res_region_keys_;
+  rp.slot_cap = UINT32_MAX;
+  for (int k = 0; k < kSlots; ++k) rp.slot_cap = std::min(rp.slot_cap, slot_[k].cap);
+  rp.region_keys = region_keys_;
   rp.mt_dense = (uint32_t)(ntiles_ / 2);
   rp.mt_words = (uint32_t)((ntiles_ + 31) / 32);
-  for (int k = 0; k < kResSlots; ++k) {
-    MergeSlot& sl = slot_[k];
+  for (int k = 0; k < kSlots; ++k) {
+    const MergeSlot& sl = slot_[k];
     ResSlot& r = rp.sl[k];
     r.dsum = U(sl.dsum);
     r.dft = U(sl.dft);
@@ -1212,84 +1218,68 @@ void Device::start_resident() {
     // region headers carry the merge id k_resident polls for: none may hold a stale one
     if (sl.rhdr) HIP_OK(hipMemsetAsync(sl.rhdr, 0, (size_t)kMaxMergeGroups * kRegHdr * sizeof(uint32_t), S(stream_)));
   }
-  for (int32_t& x : res_abandoned_) x = -1;
-  rp.dbg = res_dbg_;
-  rp.stamps = U(res_stamps_);
-  res_status_[0] = 0;
-  res_status_[2] = 0;
-  HIP_OK(hipMemsetAsync(res_q_, 0, (size_t)res_grid_ * kResRing * 2 * sizeof(uint64_t), S(stream_)));
-  HIP_OK(hipMemsetAsync(res_arrive_, 0, sizeof(uint32_t), S(stream_)));
-  HIP_OK(hipEventRecord((hipEvent_t)res_ev_[0], S(stream_)));
+  for (int32_t& x : abandoned_) x = -1;
+  rp.dbg = dbg_;
+  rp.stamps = U(stamps_);
+  status_[0] = 0;
+  status_[2] = 0;
+  HIP_OK(hipMemsetAsync(q_, 0, (size_t)grid_ * kResRing * 2 * sizeof(uint64_t), S(stream_)));
+  HIP_OK(hipMemsetAsync(arrive_, 0, sizeof(uint32_t), S(stream_)));
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[0], S(stream_)));
   // a plain launch: one workgroup per CU by its LDS footprint, checked against the occupancy
-  // query at plan time (plan_resident), so every workgroup is resident together
-  if (res_lds_tok_) k_resident<true, true><<<res_grid_, 256, res_shm_, S(stream_)>>>(rp);
-  else k_resident<true, false><<<res_grid_, kResThreadsHbm, res_shm_, S(stream_)>>>(rp);
+  // query at plan time (plan), so every workgroup is resident together
+  if (lds_tok_) k_resident<true, true><<<grid_, 256, shm_, S(stream_)>>>(rp);
+  else k_resident<true, false><<<grid_, kResThreadsHbm, shm_, S(stream_)>>>(rp);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord((hipEvent_t)res_ev_[1], S(stream_)));
-  res_running_ = true;
-  res_merges_ = 0;
-  ++res_launches_;
+  HIP_OK(hipEventRecord((hipEvent_t)ev_[1], S(stream_)));
+  running_ = true;
+  merges_ = 0;
+  ++launches_;
 }
 
-bool Device::resident_aborted() const { return __atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpAbort; }
+bool ResidentLoop::aborted() const { return __atomic_load_n(&status_[0], __ATOMIC_ACQUIRE) == kOpAbort; }
 
-// merge_chain's resident branch: one merge (ab[0], ab[1]) -> X0 posted to the launch.
-void Device::post_resident_merge(const int32_t* ab, int32_t X0) {
-  if (res_posted_.size() >= (size_t)kResSlots) fatal("merge_chain: every resident slot has a merge in flight");
-  const int slot = res_running_ && resident_aborted() ? -1 : pick_resident_slot();
-  if (slot < 0) {  // the launch aborted (not co-resident): this merge and those in flight go elsewhere
-    resident_abort_fallback();
-    merge_chain(ab, 1, X0);
-    return;
-  }
-  bool grow = false;
-  for (const MergeSlot& s2 : slot_) grow |= !s2.dsum || (uint32_t)X0 + 2 > s2.cap;
-  if (grow) {  // the delta tables grow: only between launches
-    if (!res_posted_.empty()) fatal("merge_chain: delta tables too small with a resident merge in flight");
-    park();
-    for (MergeSlot& s2 : slot_) ensure_slots(s2, (uint32_t)X0 + 2);
-    uint32_t cap = 0;
-    for (const MergeSlot& s2 : slot_) cap = std::max(cap, s2.cap);
-    for (MergeSlot& s2 : slot_) ensure_slots(s2, cap);
-  }
-  max_id_seen_ = std::max(max_id_seen_, X0);
-  const uint32_t seq = post_resident(kOpMerge, ab[0], ab[1], X0, slot);
-  res_posted_.push_back({X0, ab[0], ab[1], seq, slot, (uint32_t)res_post_parts_[slot].size(), now_seconds()});
+uint32_t ResidentLoop::post_merge(int slot, int32_t a, int32_t b, int32_t X, const TileIndex* index) {
+  const uint32_t seq = post(kOpMerge, a, b, X, slot, index);
+  posted_.push_back({X, a, b, seq, slot, (uint32_t)post_parts_[slot].size(), now_seconds()});
+  uint32_t visited = 0;
+  for (uint32_t o : post_parts_[slot]) visited += wg_ntiles_[o];
+  return visited;
 }
 
-// rollback's resident branch: each wrong guess >= X is expanded back where it matched.
-void Device::undo_resident_from(int32_t X) {
-  while (!res_posted_.empty() && res_posted_.back().X >= X) {
-    const ResPost rp = res_posted_.back();
-    res_posted_.pop_back();
+// Each wrong guess >= X is expanded back where it matched.
+int ResidentLoop::rollback(int32_t X) {
+  int n = 0;
+  for (; !posted_.empty() && posted_.back().X >= X; ++n) {
+    const Post rp = posted_.back();
+    posted_.pop_back();
     // no wait: every workgroup takes its commands in order, so the undo follows the guess; the
-    // slot stays out of use until the guess's completion is seen (pick_resident_slot)
-    post_resident(kOpUnmerge, rp.a, rp.b, rp.X, rp.slot);
-    res_abandoned_[rp.slot] = rp.X;
-    ++rollbacks_;
+    // slot stays out of use until the guess's completion is seen (pick_slot)
+    post(kOpUnmerge, rp.a, rp.b, rp.X, rp.slot);
+    abandoned_[rp.slot] = rp.X;
   }
+  return n;
 }
 
 // Posts one command to the resident launch (relaunching it first if it ended on its time-out).
 // Merge and unmerge commands name their participants; a merge's are kept by slot for its undo.
-uint32_t Device::post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int slot) {
-  if (res_running_ && __atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpTimeout) {
-    if (!res_posted_.empty()) fatal("k_resident ended on its time-out with merges in flight");
+uint32_t ResidentLoop::post(uint32_t op, int32_t a, int32_t b, int32_t X, int slot, const TileIndex* index) {
+  if (running_ && __atomic_load_n(&status_[0], __ATOMIC_ACQUIRE) == kOpTimeout) {
+    if (!posted_.empty()) fatal("k_resident ended on its time-out with merges in flight");
     HIP_OK(hipStreamSynchronize(S(stream_)));
-    res_running_ = false;
+    running_ = false;
   }
-  if (!res_running_ && op != kOpStop) start_resident();
+  if (!running_ && op != kOpStop) start();
   uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t np = res_grid_;
+  uint32_t np = grid_;
   if (op == kOpMerge) {
-    std::vector<uint32_t>& pp = res_post_parts_[slot];
-    if (skip_) index_.owners(a, b, res_wg_first_, &pp);
-    if (!skip_ || pp.empty()) pp = res_all_;
-    for (uint32_t o : pp) visited_tiles_ += res_wg_ntiles_[o];
+    std::vector<uint32_t>& pp = post_parts_[slot];
+    if (index) index->owners(a, b, wg_first_, &pp);
+    if (!index || pp.empty()) pp = all_;
     slot_[slot].host_count[1] = 0xFFFFFFFFu;  // the merge raises X here
   }
   if (op == kOpMerge || op == kOpUnmerge) {
-    const std::vector<uint32_t>& pp = res_post_parts_[slot];
+    const std::vector<uint32_t>& pp = post_parts_[slot];
     for (uint32_t o : pp) mask[o >> 5] |= 1u << (o & 31);
     np = (uint32_t)pp.size();
     if (op == kOpMerge) {  // the gatherer completes every merge
@@ -1298,7 +1288,7 @@ uint32_t Device::post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int
     }
   }
   const uint32_t seq = ++seq_;
-  uint64_t* g = static_cast<ResMbox*>(res_mbox_)->cmd[seq % kResRing].g;
+  uint64_t* g = static_cast<ResMbox*>(mbox_)->cmd[seq % kResRing].g;
   auto put = [&](int k, uint32_t v) { __atomic_store_n(&g[k], (uint64_t)seq | ((uint64_t)v << 32), __ATOMIC_RELAXED); };
   put(kCmdOp, op);
   put(kCmdA, (uint32_t)a);
@@ -1313,40 +1303,40 @@ uint32_t Device::post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int
 // A slot for the next resident merge: none with a posted merge, and none whose undone guess has
 // not completed yet (its completion still writes the slot and raises the slot's flag with the
 // same merge id the next merge may carry).
-int Device::pick_resident_slot() {
+int ResidentLoop::pick_slot() {
   for (;;) {
     int wait_slot = -1;
-    for (int k = 0; k < kResSlots; ++k) {
-      const int s = (res_next_slot_ + k) % kResSlots;
+    for (int k = 0; k < kSlots; ++k) {
+      const int s = (next_slot_ + k) % kSlots;
       bool used = false;
-      for (const ResPost& rp : res_posted_) used |= rp.slot == s;
+      for (const Post& rp : posted_) used |= rp.slot == s;
       if (used) continue;
-      if (res_abandoned_[s] >= 0) {
-        if (__atomic_load_n(slot_[s].host_count + 1, __ATOMIC_ACQUIRE) != (uint32_t)res_abandoned_[s]) {
+      if (abandoned_[s] >= 0) {
+        if (__atomic_load_n(slot_[s].host_count + 1, __ATOMIC_ACQUIRE) != (uint32_t)abandoned_[s]) {
           if (wait_slot < 0) wait_slot = s;
           continue;
         }
-        res_abandoned_[s] = -1;
+        abandoned_[s] = -1;
       }
-      res_next_slot_ = (s + 1) % kResSlots;
+      next_slot_ = (s + 1) % kSlots;
       return s;
     }
     if (wait_slot < 0) fatal("k_resident: no free merge slot");
-    if (!wait_resident(slot_[wait_slot], res_abandoned_[wait_slot])) return -1;  // the launch aborted
+    if (!wait(slot_[wait_slot], abandoned_[wait_slot])) return -1;  // the launch aborted
   }
 }
 
-bool Device::wait_resident(const MergeSlot& sl, int32_t X) {
+bool ResidentLoop::wait(const MergeSlot& sl, int32_t X) {
   volatile uint32_t* flag = sl.host_count + 1;
   const double t0 = now_seconds();
   unsigned spins = 0;
   while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != (uint32_t)X) {
     __builtin_ia32_pause();
     if (++spins % 4096 != 0) continue;
-    if (resident_aborted()) return false;
-    if (__atomic_load_n(&res_status_[0], __ATOMIC_ACQUIRE) == kOpTimeout)
+    if (aborted()) return false;
+    if (__atomic_load_n(&status_[0], __ATOMIC_ACQUIRE) == kOpTimeout)
       fatal("k_resident ended on its time-out before a posted merge completed");
-    if (res_dbg_ && now_seconds() - t0 > 3.0) resident_dump("no flag after 3 s");
+    if (dbg_ && now_seconds() - t0 > 3.0) dump("no flag after 3 s");
     if (now_seconds() - t0 > 120.0) {
       const hipError_t e = hipStreamQuery(S(stream_));
       if (e != hipSuccess && e != hipErrorNotReady) HIP_OK(e);
@@ -1356,77 +1346,47 @@ bool Device::wait_resident(const MergeSlot& sl, int32_t X) {
   return true;
 }
 
-size_t Device::collect_resident(int32_t X, const DeltaRecord** recs) {
-  if (res_posted_.empty() || res_posted_.front().X != X) fatal("collect: merge X is not the oldest posted merge");
+bool ResidentLoop::collect(int32_t X, Collected* c) {
+  if (posted_.empty() || posted_.front().X != X) fatal("collect: merge X is not the oldest posted merge");
   const double tw = now_seconds();
-  if (!wait_resident(slot_[res_posted_.front().slot], X)) {  // not co-resident: nothing ran
-    resident_abort_fallback();
-    return collect(X, recs);
+  if (!wait(slot_[posted_.front().slot], X)) return false;  // not co-resident: nothing ran
+  const Post rp = posted_.front();
+  posted_.erase(posted_.begin());
+  const MergeSlot& sl = slot_[rp.slot];
+  const double t1 = now_seconds();  // host clock: post -> flag seen, and the part of it spent waiting here
+  post_flag_us_ += 1e6 * (t1 - rp.t_post);
+  host_wait_ += 1e6 * (t1 - tw);
+  parts_sum_ += rp.nparts;
+  const uint64_t* hs = (const uint64_t*)(sl.host_count + 4);
+  lat_us_ += 1e-2 * (double)hs[2];  // s_memrealtime: 100 MHz
+  lat_n_ += 1;
+  if (stamps_) {
+    for (int k = 0; k < 4; ++k) ph_[k] += 1e-2 * (double)hs[3 + k];
+    ph_raw_ += (double)hs[7];
+    ph_flag_ += 1e-2 * (double)hs[2];
+    ph_n_ += 1;
   }
-  const ResPost rp = res_posted_.front();
-  res_posted_.erase(res_posted_.begin());
-  MergeSlot& sl = slot_[rp.slot];
-  {  // host clock: post -> flag seen, and the part of it spent waiting here
-    const double t1 = now_seconds();
-    res_post_flag_us_ += 1e6 * (t1 - rp.t_post);
-    res_post_flag_last_ = 1e6 * (t1 - rp.t_post);
-    res_host_wait_ += 1e6 * (t1 - tw);
-    res_parts_sum_ += rp.nparts;
-  }
-  const u64* hs = (const u64*)(sl.host_count + 4);
-  const size_t n = sl.host_count[0];
-  const uint32_t nm = sl.host_count[2];
-  if (nm == kAllTiles) index_.set_all(X);
-  else index_.set_tiles_bits(X, sl.host_mlist, nm);  // the gatherer's bitmap (k_resident)
-  res_lat_us_ += 1e-2 * (double)hs[2];  // s_memrealtime: 100 MHz
-  res_lat_n_ += 1;
-  if (res_stamps_ && merge_log_)  // diagnostic: host post / flag-seen clock beside the device's dispatch / flag
-    std::fprintf(merge_log_, "S %d %u %.2f %.2f %.2f %llu %llu %zu %u\n", X, rp.nparts, 1e6 * rp.t_post, 1e6 * tw,
-                 1e6 * (rp.t_post + 1e-6 * res_post_flag_last_), (unsigned long long)hs[8],
-                 (unsigned long long)(hs[8] + hs[2]), (size_t)sl.host_count[0], nm);
-  if (res_stamps_) {
-    for (int k = 0; k < 4; ++k) res_ph_[k] += 1e-2 * (double)hs[3 + k];
-    res_phase_[4] += (double)hs[7];
-    res_phase_[3] += 1e-2 * (double)hs[2];
-    res_phase_n_ += 1;
-  }
-  if (timing_) {
-    times_.merge_bytes += 4.0 * (double)live_tokens_est_;
-    times_.res_bytes += 4.0 * (double)live_tokens_est_;
-    times_.res_k3_bytes += 8.0 * (double)hs[1];  // hs[1]: tokens the merge's matched tiles hold after it
-    times_.res_merges += 1;
-  }
-  ++res_merges_;
-  if (hybrid_ && !idx_phase_ && index_on_ && wl_ && wl_->ready()) {
-    // entries merged per merge is far from monotone (a frequent pair of a few common words sits
-    // between pairs spread over many words): switch once a whole window of merges stayed small
-    sw_win_[sw_n_++ % kSwitchWindow] = hs[0];
-    uint64_t mx = 0;
-    for (uint64_t v : sw_win_) mx = std::max(mx, v);
-    if (sw_n_ >= kSwitchWindow && mx < switch_occ_) switch_pending_ = true;
-  }
-  live_tokens_est_ -= hs[0];
-  records_total_ += n;
-  records_max_ = std::max<uint64_t>(records_max_, n);
-  *recs = sl.host_recs;
-  return n;
+  ++merges_;
+  // host_mlist: the gatherer's bitmap (k_resident)
+  *c = {sl.host_recs, sl.host_count[0], sl.host_mlist, sl.host_count[2], hs, rp.nparts, rp.t_post, tw, t1};
+  return true;
 }
 
 // Diagnostic (SHREDWORD_RESIDENT_DEBUG=1): the state of a stuck resident launch, then exit.
-void Device::resident_dump(const char* why) {
-  const uint32_t G = res_grid_;
+void ResidentLoop::dump(const char* why) {
+  const uint32_t G = grid_;
   hipStream_t s;
   HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   std::vector<uint32_t> dbg(4 * G), cmd(kResRing * 8);
   std::vector<uint64_t> q((size_t)G * kResRing * 2);
-  HIP_OK(hipMemcpyAsync(dbg.data(), res_dbg_, dbg.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(cmd.data(), res_cmd_, cmd.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(q.data(), res_q_, q.size() * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(dbg.data(), dbg_, dbg.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(cmd.data(), cmd_, cmd.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(q.data(), q_, q.size() * 8, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
-  std::fprintf(stderr, "[RESIDENT] %s: seq_=%u status=%u posted=%zu flags=%u/%u\n", why, seq_, res_status_[0],
-               res_posted_.size(), slot_[0].host_count[1], slot_[1].host_count[1]);
-  for (int k = 2; k < kResSlots; ++k) std::fprintf(stderr, "[RESIDENT] flag[%d]=%u\n", k, slot_[k].host_count[1]);
-  for (const ResPost& rp : res_posted_)
+  std::fprintf(stderr, "[RESIDENT] %s: seq_=%u status=%u posted=%zu flags=%u/%u\n", why, seq_, status_[0],
+               posted_.size(), slot_[0].host_count[1], slot_[1].host_count[1]);
+  for (int k = 2; k < kSlots; ++k) std::fprintf(stderr, "[RESIDENT] flag[%d]=%u\n", k, slot_[k].host_count[1]);
+  for (const Post& rp : posted_)
     std::fprintf(stderr, "[RESIDENT]   posted X=%d seq=%u slot=%d np=%u\n", rp.X, rp.seq, rp.slot, rp.nparts);
   for (uint32_t g = 0; g < G; ++g) {
     std::fprintf(stderr, "[RESIDENT] wg %u: phase %u seq %u pi %u T %u | q", g, dbg[4 * g], dbg[4 * g + 1], dbg[4 * g + 2],
@@ -1441,69 +1401,42 @@ void Device::resident_dump(const char* why) {
   std::_Exit(3);
 }
 
-void Device::park() {
-  index_sync();
-  if (!res_running_) return;
-  HIP_OK(hipSetDevice(ordinal_));
-  if (!res_posted_.empty()) fatal("park: a resident merge was not collected");
-  post_resident(kOpStop, 0, 0, 0, 0);
+uint64_t ResidentLoop::stop(double* ms_out) {
+  if (!posted_.empty()) fatal("park: a resident merge was not collected");
+  post(kOpStop, 0, 0, 0, 0);
   HIP_OK(hipStreamSynchronize(S(stream_)));
-  res_running_ = false;
-  for (int32_t& x : res_abandoned_) x = -1;  // every command ran
-  for (MergeSlot& s2 : slot_)  // flags carried merge ids: the launch path compares launch numbers
-    if (s2.host_count) s2.host_count[1] = 0xFFFFFFFFu;
-  res_status_[0] = 0;
+  running_ = false;
+  for (int32_t& x : abandoned_) x = -1;  // every command ran
+  for (int k = 0; k < kSlots; ++k)  // flags carried merge ids: the launch path compares launch numbers
+    if (slot_[k].host_count) slot_[k].host_count[1] = 0xFFFFFFFFu;
+  status_[0] = 0;
   float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)res_ev_[0], (hipEvent_t)res_ev_[1]));
-  res_ms_ += ms;
-  if (timing_ && res_merges_) {  // one launch: its wall time is the merge loop's device time
-    times_.merge_ms += ms;
-    times_.merge_launches += res_merges_;
-    times_.res_ms += ms;
-  }
-  if (res_merges_ && std::getenv("SHREDWORD_RESIDENT_REPORT")) {
-    const double n = (double)res_merges_;
+  HIP_OK(hipEventElapsedTime(&ms, (hipEvent_t)ev_[0], (hipEvent_t)ev_[1]));
+  ms_ += ms;
+  *ms_out = ms;
+  if (merges_ && std::getenv("SHREDWORD_RESIDENT_REPORT")) {
+    const double n = (double)merges_;
     std::fprintf(stderr, "[RESIDENT] %llu merges in %.2f ms | host: post->flag %.2f us, waited %.2f us | participants %.1f",
-                 (unsigned long long)res_merges_, ms, res_post_flag_us_ / n, res_host_wait_ / n, res_parts_sum_ / n);
-    if (res_phase_n_)
+                 (unsigned long long)merges_, ms, post_flag_us_ / n, host_wait_ / n, parts_sum_ / n);
+    if (ph_n_)
       std::fprintf(stderr,
                    " | device after dispatch: all published %.2f prefix %.2f loaded %.2f combined %.2f flag %.2f",
-                   res_ph_[0] / res_phase_n_, res_ph_[1] / res_phase_n_,
-                   res_ph_[2] / res_phase_n_, res_ph_[3] / res_phase_n_, res_phase_[3] / res_phase_n_);
-    if (res_phase_n_) std::fprintf(stderr, " | records before combine %.1f", res_phase_[4] / res_phase_n_);
+                   ph_[0] / ph_n_, ph_[1] / ph_n_, ph_[2] / ph_n_, ph_[3] / ph_n_, ph_flag_ / ph_n_);
+    if (ph_n_) std::fprintf(stderr, " | records before combine %.1f", ph_raw_ / ph_n_);
     std::fprintf(stderr, "\n");
   }
-  res_post_flag_us_ = res_host_wait_ = res_parts_sum_ = 0;
-  res_phase_[0] = res_phase_[1] = res_phase_[2] = res_phase_[3] = res_phase_[4] = 0;
-  for (double& x : res_ph_) x = 0;
-  res_phase_n_ = 0;
-  rebuild_signatures();  // the tiles are back in HBM: their pair signatures for k_merge / k_unmerge
+  post_flag_us_ = host_wait_ = parts_sum_ = ph_flag_ = ph_raw_ = 0;
+  for (double& x : ph_) x = 0;
+  ph_n_ = 0;
+  return merges_;
 }
 
-// The resident launch aborted before dispatching anything (some workgroups never became
-// resident: another kernel or process holds CUs).  Resident is off for this device from here on;
-// the merges posted to it run again, in order, on the indexed loop (or the launch path).  The
-// launch's missing workgroups may start only once those CUs free up, and they hold its stream
-// until then, so all further work moves to a fresh stream.
-void Device::resident_abort_fallback() {
-  std::vector<ResPost> inflight;
-  inflight.swap(res_posted_);
-  res_running_ = false;
-  resident_ok_ = false;
-  ++res_aborts_;
-  for (int32_t& x : res_abandoned_) x = -1;
-  retired_streams_.push_back(stream_);
-  hipStream_t s;
-  HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  stream_ = s;
-  if (wl_) wl_->set_stream(stream_);
-  if (std::getenv("SHREDWORD_RESIDENT_REPORT"))
-    std::fprintf(stderr, "[RESIDENT] launch aborted (not every workgroup resident): %zu merges move to the %s\n",
-                 inflight.size(), wl_ && wl_->ready() ? "indexed loop" : "launch path");
-  for (const ResPost& rp : inflight) {
-    const int32_t ab[2] = {rp.a, rp.b};
-    merge_chain(ab, 1, rp.X);
-  }
+std::vector<ResidentLoop::Post> ResidentLoop::abandon() {
+  std::vector<Post> inflight;
+  inflight.swap(posted_);
+  running_ = false;
+  for (int32_t& x : abandoned_) x = -1;
+  return inflight;
 }
 
 }  // namespace shred

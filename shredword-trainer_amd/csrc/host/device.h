@@ -9,9 +9,10 @@
 //   dsum/dft  u64 per (neighbour slot, category): summed weight and min first-touch of the
 //             current merge's neighbour-pair deltas; dlist/dcount: the touched keys.  Two sets
 //             (merge parity), so a speculative merge X+1 can run while merge X is consumed.
-// No HIP type appears here so host C++ can include it.  Three units implement it: bpe_device.hip
-// (tables, launch path, the choice between the merge paths), resident_loop.hip (k_resident) and
-// pair_count.hip (K1, K6, probes).
+// No HIP type appears here so host C++ can include it.  Two units implement it: bpe_device.hip
+// (tables, launch path, the choice between the merge paths and what a collected merge means) and
+// pair_count.hip (K1, K6, probes).  The persistent loops are classes of their own that Device only
+// drives: ResidentLoop (resident_loop.h, k_resident) and WordLoop (word_loop.h, k_word_loop).
 #pragma once
 
 #include <algorithm>
@@ -23,6 +24,7 @@
 
 #include "corpus.h"
 #include "engine.h"
+#include "resident_loop.h"
 #include "selector.h"
 #include "tiles.h"
 #include "word_loop.h"
@@ -117,7 +119,7 @@ class Device : public Backend {
   }
   // k_resident takes up to kResSlots merges in flight (the current one and the guesses behind
   // it); the launch path two launches.
-  static constexpr int kResSlots = 4;
+  static constexpr int kResSlots = ResidentLoop::kSlots;
   int overlap_depth() const override { return resident_eligible() || index_eligible() ? spec_depth_ : 1; }
   // k_resident and the indexed loop queue up to kResSlots / WordLoop::kSlots merges; the launch
   // path's two launches hold one guess behind the current merge.
@@ -137,9 +139,9 @@ class Device : public Backend {
   // leaves the HBM stream current.  Results are identical with it on or off.
   void quiesce() override { park(); }
   void park();
-  void set_resident(bool on);
+  void set_resident(bool on) { park(); resident_on_ = on; }
   bool resident() const { return resident_on_; }
-  bool resident_eligible() const { return resident_on_ && resident_ok_ && !exchange_ && !index_eligible(); }
+  bool resident_eligible() const { return resident_on_ && res_.ok() && !exchange_ && !index_eligible(); }
   // The indexed merge loop (word_loop.h): the default for the types layout on one GPU.
   void set_index(bool on);
   bool index_on() const { return index_on_; }
@@ -148,7 +150,7 @@ class Device : public Backend {
   // entries each, the indexed loop (one workgroup, a few round trips per merge) takes over for
   // the rest of train().
   bool hybrid_resident_phase() const {
-    return hybrid_ && !idx_phase_ && resident_on_ && resident_ok_ && !exchange_ && ntiles_ > 0;
+    return hybrid_ && !idx_phase_ && resident_on_ && res_.ok() && !exchange_ && ntiles_ > 0;
   }
   bool index_eligible() const {
     return index_on_ && wl_ && wl_->ready() && !exchange_ && !hybrid_resident_phase();
@@ -170,12 +172,9 @@ class Device : public Backend {
   int64_t switch_merge() const { return switch_x_; }
   double switch_ms() const { return switch_ms_; }
   const WordLoop* word_loop() const { return wl_; }
-  uint64_t resident_launches() const { return res_launches_; }
+  const ResidentLoop& resident_loop() const { return res_; }
   uint64_t resident_aborts() const { return res_aborts_; }
-  bool resident_tokens_in_lds() const { return res_lds_tok_; }
-  double resident_ms() const { return res_ms_; }
-  // mean dispatch -> host flag time of a resident merge (device clock), us
-  double resident_latency_us() const { return res_lat_n_ ? res_lat_us_ / (double)res_lat_n_ : 0.0; }
+  bool resident_tokens_in_lds() const { return res_.tokens_in_lds(); }
   void set_speculation(bool on) { speculate_ = on; }
   uint64_t rollbacks() const { return rollbacks_; }
   // Tuning: k_merge grid cap.
@@ -203,9 +202,7 @@ class Device : public Backend {
     times_ = KernelTimes();
     records_total_ = records_max_ = 0;
     visited_tiles_ = 0;
-    res_launches_ = 0;
-    res_ms_ = res_lat_us_ = 0;
-    res_lat_n_ = 0;
+    res_.clear_stats();
     if (wl_) {
       wl_->clear_stats();
       wl_ms_seen_ = 0;
@@ -219,37 +216,6 @@ class Device : public Backend {
   void* stream_handle() const { return stream_; }
 
  private:
-  // Device tables and host-visible buffers of a merge launch.
-  struct MergeSlot {
-    uint32_t cap = 0;  // neighbour slots: id+1 for ids < cap, slot 0 for unk outside
-    uint64_t* dsum = nullptr;  // kChainMax x 4 (cap + 1) keys + 2 stats words
-    uint64_t* dft = nullptr;
-    uint32_t* dlist = nullptr;
-    uint32_t* dcount = nullptr;  // [0] touched-slot count, [1..9] completion tickets, [10] matched tiles
-    DeltaRecord* host_recs = nullptr;  // pinned, device-visible
-    void* dev_recs = nullptr;
-    uint32_t* host_count = nullptr;    // pinned: [0] records (| need-collect), [1] flag, [2] matched tiles,
-    void* dev_count = nullptr;         //         [3] k_collect offset, bytes 16..31: occurrences, tokens
-    uint32_t* dmlist = nullptr;        // device: matched tiles beyond a workgroup's LDS list / multi-GPU
-    uint32_t* rhdr = nullptr;          // device: per-workgroup regions of the fused completion
-    uint64_t* rrec = nullptr;
-    uint32_t* rtile = nullptr;
-    uint32_t* host_mlist = nullptr;    // pinned: matched tiles (tile | chain index << 27)
-    void* dev_mlist = nullptr;
-    // multi-GPU: this rank's bucket (32-byte header, then records; records past the bucket
-    // stay behind it for the overflow round), the gathered buckets, and their pinned copy
-    uint8_t* xsend = nullptr;
-    uint8_t* xrecv = nullptr;
-    DeltaRecord* host_xrecs = nullptr;  // pinned: world x bucket records, concatenated
-    void* dev_xrecs = nullptr;
-    uint32_t* host_xhdr = nullptr;      // pinned: per rank [records | need-collect, k_collect offset]
-    void* dev_xhdr = nullptr;
-    std::vector<DeltaRecord> xall;      // all ranks' records when a bucket overflowed
-    uint32_t grid = 0;
-    uint32_t n_iter = 0;  // candidate tiles of the launch
-    bool launched = false;
-    uint32_t seq = 0;
-  };
   // A launch: merges X0 .. X0+n-1, collected in order.  Up to two runs are in flight (the
   // second launched before the first is collected); run r uses slot_[r's slot].
   struct ChainRun {
@@ -338,7 +304,8 @@ class Device : public Backend {
   void* dev_ulist_ = nullptr;
   std::vector<uint32_t> ulist_;
   bool unmerge_pending_ = false;  // a k_unmerge reading host_ulist_ may still run
-  uint32_t seq_ = 0;            // launch sequence number echoed by the device flag
+  uint32_t seq_ = 0;            // launch sequence number echoed by the device flag (shared with res_)
+  ResidentLoop res_{ordinal_, slot_, seq_, keys_per_merge_};
   int32_t unk_ = 0;
   uint64_t records_total_ = 0, records_max_ = 0;
   int32_t max_id_seen_ = 0;
@@ -385,75 +352,15 @@ class Device : public Backend {
   void resident_abort_fallback();
   std::vector<void*> retired_streams_;  // streams of aborted resident launches
   uint64_t res_aborts_ = 0;
-  uint32_t* res_arrive_ = nullptr;      // k_resident: workgroups that started
-  uint32_t res_arrive_polls_ = 20000;   // the leader's co-residency bound (~20 ms; env SHREDWORD_RESIDENT_ARRIVE_POLLS)
-  uint32_t res_region_keys_ = 32;       // participants with more delta keys add them to the global tables
-                                        // (env SHREDWORD_RESIDENT_REGION_KEYS)
   uint64_t wl_ms_seen_ = 0;        // merges already folded into times_
   double wl_kms_seen_ = 0;         // launch time already folded into times_
 
-  // ---- k_resident state (resident_loop.hip "K2+K3 resident")
-  struct ResPost {          // a merge posted to the resident loop and not yet collected
-    int32_t X, a, b;
-    uint32_t seq;
-    int slot;
-    uint32_t nparts;
-    double t_post;
-  };
-  void plan_resident(const TiledStream& ts);
-  void free_resident();
+  // ---- the resident loop (resident_loop.h): what merge_chain, collect and rollback do with it
   void drain_retired();  // syncs and destroys retired_streams_ (before their buffers go)
-  void start_resident();
-  uint32_t post_resident(uint32_t op, int32_t a, int32_t b, int32_t X, int slot);
-  bool wait_resident(const MergeSlot& sl, int32_t X);  // false: the launch aborted
-  int pick_resident_slot();
-  // what merge_chain and rollback need of the resident loop
-  bool resident_aborted() const;
   void post_resident_merge(const int32_t* ab, int32_t X0);
-  void undo_resident_from(int32_t X);
   size_t collect_resident(int32_t X, const DeltaRecord** recs);
-  [[noreturn]] void resident_dump(const char* why);
   bool resident_on_ = true;       // option (SHREDWORD_RESIDENT / set_option resident)
-  bool resident_ok_ = false;      // the uploaded table fits (plan_resident)
-  bool res_running_ = false;      // a k_resident launch is live
-  bool res_lds_tok_ = true;       // the tokens are in LDS (else in HBM, LDS holds weights + signatures)
-  std::vector<ResPost> res_posted_;  // oldest first (a merge and the guesses behind it)
-  std::vector<uint32_t> res_post_parts_[kResSlots];  // participants of the posted merges, by slot
-  int spec_depth_ = 1;               // guesses in flight behind the current merge (resident)
-  int32_t res_abandoned_[kResSlots] = {-1, -1, -1, -1};  // by slot: an undone guess not yet completed
-  int res_next_slot_ = 0;
-  uint32_t res_grid_ = 0, res_tok_words_ = 0, res_w_words_ = 0;
-  uint32_t res_sig_words_ = 0;   // LDS signature words per tile in this plan
-  bool res_w_global_ = false;    // the plan reads word weights from HBM
-  size_t res_shm_ = 0;
-  uint32_t* res_wg_tiles_ = nullptr;   // device: grid + 1
-  uint32_t* res_wg_rank_ = nullptr;    // device: grid + 1
-  uint32_t* res_tile_lofs_ = nullptr;  // device: per tile
-  std::vector<uint32_t> res_owner_;    // tile -> workgroup (0 dispatches and 1 gathers: they own none)
-  std::vector<uint32_t> res_wg_ntiles_;
-  std::vector<uint32_t> res_all_;      // every worker workgroup (1 .. grid-1)
-  std::vector<uint32_t> res_wg_first_; // grid + 1: first tile of each workgroup
-  std::vector<uint32_t> res_parts_;
-  void* res_mbox_ = nullptr;           // pinned host ResMbox (command ring)
-  void* res_mbox_dev_ = nullptr;
-  uint32_t* res_cmd_ = nullptr;        // device command ring
-  uint64_t* res_q_ = nullptr;          // device per-workgroup queues
-  uint32_t* res_dbg_ = nullptr;        // device: per-workgroup progress (SHREDWORD_RESIDENT_DEBUG)
-  uint64_t* res_stamps_ = nullptr;     // device: per-participant phase stamps (SHREDWORD_RESIDENT_STAMPS)
-  double res_phase_[5] = {};
-  double res_ph_[4] = {};  // diagnostic: the gatherer's phases
-  uint64_t res_phase_n_ = 0;
-  bool res_stamp_detail_ = false;
-  double res_post_flag_last_ = 0;      // the last collected merge's post -> flag seen (µs)
-  double res_host_wait_ = 0, res_parts_sum_ = 0, res_post_flag_us_ = 0;
-  uint32_t* res_status_ = nullptr;     // pinned host status
-  void* res_status_dev_ = nullptr;
-  void* res_ev_[2] = {};
-  uint64_t res_launches_ = 0;
-  uint64_t res_merges_ = 0;            // merges collected in the current launch
-  double res_ms_ = 0;                  // Σ k_resident launch durations (HIP events)
-  double res_lat_us_ = 0;              // Σ per-merge dispatch -> flag times (device clock)
-  uint64_t res_lat_n_ = 0;
+  int spec_depth_ = 1;            // guesses in flight behind the current merge (resident, indexed)
 };
 
 }  // namespace shred

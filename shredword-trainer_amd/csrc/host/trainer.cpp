@@ -481,9 +481,9 @@ int shred_get_stats(const Trainer* tc, ShredStats* s) {
     s->device_bytes = t->dev->device_bytes();
     s->num_tiles = t->dev->num_tiles();
     s->live_tokens = t->dev->live_tokens();
-    s->resident_launches = t->dev->resident_launches();
-    s->resident_ms = t->dev->resident_ms();
-    s->resident_latency_us = t->dev->resident_latency_us();
+    s->resident_launches = t->dev->resident_loop().launches();
+    s->resident_ms = t->dev->resident_loop().ms();
+    s->resident_latency_us = t->dev->resident_loop().latency_us();
     s->resident_aborts = t->dev->resident_aborts();
     s->resident_merges = k.res_merges;
     s->resident_bytes = k.res_bytes;
