@@ -50,7 +50,7 @@ constexpr uint32_t kInlineTiles = 768;     // candidate tiles that fit the kerne
 constexpr int kGroup = 4;                  // tiles walked together per wave (loads in flight)
 constexpr uint32_t kWin = 32;              // candidate tiles per workgroup window (filter pass)
 constexpr int kMaxChain = 8;               // merges one k_merge launch applies in order
-constexpr int kChainShift = 27;            // matched-tile entries: tile | (chain index << 27)
+constexpr int kChainShift = Device::kChainShift;  // matched-tile entries: tile | (chain index << 27)
 constexpr uint32_t kMtLds = 256;           // matched tiles a workgroup keeps in LDS (more: global list)
 [[maybe_unused]] constexpr int kStamps = 18;               // SHRED_STAMPS: entry, init, windows, flush, ticket, collect, flag
 #ifdef SHRED_STAMPS
@@ -1713,8 +1713,12 @@ void Device::finish_launch(ChainRun& run_) {
   records_total_ += n;
   records_max_ = std::max<uint64_t>(records_max_, n);
   if (merge_log_) {
-    std::fprintf(merge_log_, "C %u %d %u %u %d %llu %zu", sl.seq, run_.X0, sl.n_iter, sl.grid, run_.n,
-                 (unsigned long long)hs[0], n);
+    // ... then this rank's records that left the workgroups' LDS hashes for the global tables
+    // (host_count[3]: the LDS records ahead of them, 0 without a spill) and whether they were too
+    // many for the fused collect (k_collect ran)
+    const uint32_t own = launched ? sl.host_count[0] : 0, lds = launched ? sl.host_count[3] : 0;
+    std::fprintf(merge_log_, "C %u %d %u %u %d %llu %zu %u %d", sl.seq, run_.X0, sl.n_iter, sl.grid, run_.n,
+                 (unsigned long long)hs[0], n, lds ? (own & ~kNeedCollect) - lds : 0u, (own & kNeedCollect) ? 1 : 0);
 #ifdef SHRED_STAMPS
     // per phase: when the last workgroup got there, in us after the first workgroup started
     std::vector<u64> st((size_t)sl.grid * kStamps);

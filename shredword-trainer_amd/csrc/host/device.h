@@ -106,8 +106,12 @@ class Device : public Backend {
   // The indexed loop's finished merge X, without collecting it (Engine's apply helper).
   bool peek(int32_t X, const DeltaRecord** recs, size_t* n) override;
   static constexpr int kChainMax = 8;
+  // A chain's matched-tile entries carry the merge's index above the tile: tile | index << kChainShift,
+  // so a table of 2^kChainShift tiles or more runs single merges (their entries carry no index).
+  static constexpr int kChainShift = 27;
+  static constexpr bool chain_fits(size_t ntiles) { return ntiles < ((size_t)1 << kChainShift); }
   int max_chain() const override {
-    return speculate_ && !resident_eligible() && !index_eligible() ? kChainMax : 1;
+    return speculate_ && !resident_eligible() && !index_eligible() && chain_fits(ntiles_) ? kChainMax : 1;
   }
   bool index_id_room(int32_t max_id) const;
   bool can_overlap() const override {

@@ -52,7 +52,8 @@ class Backend {
   // Non-blocking look at the oldest outstanding merge X: true with its records once the device
   // has finished it (they stay valid until X is collected or rolled back).  Default: never.
   virtual bool peek(int32_t X, const DeltaRecord** recs, size_t* n) { return false; }
-  // Longest chain the backend runs (1: one merge per pass, e.g. under a multi-GPU exchange).
+  // Longest chain the backend runs (1: one merge per pass, as the device's persistent loops do;
+  // its launch path runs chains, under a multi-GPU exchange too).
   virtual int max_chain() const { return 1; }
   // True when a second launch may be issued before the first is collected (its merges run
   // after the first launch's on the device).

@@ -66,6 +66,8 @@ def load():
     lib.hh_set_chain.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.hh_chain_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     lib.hh_chain_hist.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+    lib.hh_chain_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+    lib.hh_device_chain_fits.argtypes = [ctypes.c_uint64]
     lib.hh_spec.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
     lib.hh_word.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64,
                             ctypes.POINTER(ctypes.c_uint64)]
@@ -79,6 +81,16 @@ def open_case(lib, corpus, cfg, layout="types", rank=0, world=1):
     if not h:
         raise IOError(corpus)
     return h
+
+
+CHAIN_STATS = ("launches", "launches_ge2", "launches_8", "undos_ge2", "tails_confirmed", "max_len", "max_undo")
+
+
+def chain_stats(lib, h):
+    """The emulated backend's view of a run's chains (hh_chain_stats), by name."""
+    out = (ctypes.c_uint64 * len(CHAIN_STATS))()
+    lib.hh_chain_stats(h, out)
+    return dict(zip(CHAIN_STATS, (int(v) for v in out)))
 
 
 def table_fingerprint(lib, h):

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "corpus.h"
+#include "device.h"
 #include "engine.h"
 #include "selector.h"
 #include "tiles.h"
@@ -123,8 +124,20 @@ class EmuBackend : public Backend {
   uint32_t slot(int32_t id) const { return (uint32_t)id < cap_ ? (uint32_t)id + 1 : 0; }
 
   void merge_chain(const int32_t* ab, int n, int32_t X0) override {
-    for (int i = 0; i < n; ++i) merge_one(ab[2 * i], ab[2 * i + 1], X0 + i);
+    ++cs_[kLaunches];
+    if (n >= 2) ++cs_[kLaunches2];
+    if (n == 8) ++cs_[kLaunches8];
+    cs_[kMaxLen] = std::max<uint64_t>(cs_[kMaxLen], (uint64_t)n);
+    for (int i = 0; i < n; ++i) {
+      merge_one(ab[2 * i], ab[2 * i + 1], X0 + i);
+      queue_.back().tail = i > 0;
+    }
   }
+  // What the chains of a run looked like from the backend's side (hh_chain_stats): launches, those
+  // of >= 2 and of exactly 8 merges, rollbacks that undid >= 2 merges at once, tail merges (not the
+  // first of their launch) that were collected, the longest launch and the largest undo.
+  enum { kLaunches, kLaunches2, kLaunches8, kUndo2, kTailConfirmed, kMaxLen, kMaxUndo, kChainStats };
+  uint64_t cs_[kChainStats] = {};
 
   void merge_one(int32_t a, int32_t b, int32_t X) {
     if ((uint32_t)X >= cap_) fatal("emulated slot capacity exceeded");
@@ -206,6 +219,10 @@ class EmuBackend : public Backend {
   }
 
   void rollback(int32_t X) override {
+    uint64_t undone = 0;
+    for (const Pending& pd : queue_) undone += pd.X >= X;
+    if (undone >= 2) ++cs_[kUndo2];
+    cs_[kMaxUndo] = std::max(cs_[kMaxUndo], undone);
     while (!queue_.empty() && queue_.back().X >= X) {  // newest first
       const Pending& pd = queue_.back();
       std::vector<int32_t> out;
@@ -236,6 +253,7 @@ class EmuBackend : public Backend {
     if (queue_.empty() || queue_.front().X != X) fatal("emulated collect of a merge that is not outstanding");
     Pending pd = std::move(queue_.front());
     queue_.erase(queue_.begin());
+    if (pd.tail) ++cs_[kTailConfirmed];
     if (gather_) {  // multi-rank: every rank's records, concatenated (the host combines them)
       size_t nb = 0;
       const void* all = gather_(ctx_, pd.recs.data(), pd.recs.size() * sizeof(DeltaRecord), &nb);
@@ -402,6 +420,7 @@ class EmuBackend : public Backend {
   std::vector<DeltaRecord> recs_;
   struct Pending {
     int32_t a = 0, b = 0, X = 0;
+    bool tail = false;  // not the first merge of its launch
     std::vector<uint32_t> matched;
     std::vector<DeltaRecord> recs;
   };
@@ -647,6 +666,14 @@ void hh_chain_hist(void* p, uint64_t* hist, int k) {
     hist[m]++;
   }
 }
+// out[0..6]: EmuBackend::cs_ (launches, of >= 2, of 8, undos of >= 2, confirmed tails, max length, max undo)
+void hh_chain_stats(void* p, uint64_t* out) {
+  const EmuBackend& be = *((Harness*)p)->be;
+  for (int i = 0; i < EmuBackend::kChainStats; ++i) out[i] = be.cs_[i];
+}
+// Device::max_chain()'s bound on the table size (the predicate alone: a Device needs a GPU).
+int hh_device_chain_fits(uint64_t ntiles) { return Device::chain_fits((size_t)ntiles) ? 1 : 0; }
+int hh_device_chain_shift() { return Device::kChainShift; }
 void hh_spec(void* p, int on, uint64_t* out) {
   Harness* h = (Harness*)p;
   if (on >= 0) {

@@ -135,16 +135,20 @@ def medium_oracle(medium_corpus, tmp_path_factory):
     return open(om, "rb").read(), open(ov, "rb").read()
 
 
-@pytest.mark.parametrize("layout,bucket", [("types", 0), ("types", 8), ("stream", 64)])
-def test_exchange_path_matches_oracle(layout, bucket, medium_corpus, medium_oracle, tmp_path):
+@pytest.mark.parametrize("layout,bucket,chain", [("types", 0, 1), ("types", 8, 1), ("stream", 64, 1),
+                                                 ("types", 8, 8), ("stream", 64, 2)],
+                         ids=["types-0", "types-8", "stream-64", "types-8-chain8", "stream-64-chain2"])
+def test_exchange_path_matches_oracle(layout, bucket, chain, medium_corpus, medium_oracle, tmp_path):
     """The multi-GPU path on one GPU: every merge's records go through the RCCL all-gather (a
     single-rank communicator) and k_xout, small buckets force the overflow round.  torch is
     imported first, as in a real multi-GPU process (torch.distributed): the library then shares
-    torch's RCCL instead of opening its own (two RCCLs in one process abort at exit)."""
+    torch's RCCL instead of opening its own (two RCCLs in one process abort at exit).  chain > 1:
+    a launch's records carry chain-indexed keys through the bucket, k_xout and the overflow round."""
     import torch  # noqa: F401
     t = _trainer(vocab_size=6000, unk_id=0, character_coverage=0.9995, min_pair_freq=20)
     t.set_option("layout", layout)
     t.set_option("exchange", "local")
+    t.set_option("chain", chain)
     if bucket:
         t.set_option("exchange_bucket", bucket)
     t.load_corpus(medium_corpus)
@@ -205,6 +209,43 @@ def test_speculation_lockstep(layout, index, medium_corpus):
     assert st["spec_hits"] > 0 and st["spec_misses"] > 0
     for t in ts:
         t.destroy()
+
+
+@pytest.mark.parametrize("chain", [2, 8])
+@pytest.mark.parametrize("layout", ["stream", "types"])
+def test_chain_lockstep(layout, chain, medium_corpus):
+    """Chained launches against single merges on the launch path, in bpe_merge_batch chunks: the same
+    merge count and an identical device token stream after every chunk.  A chunk's end cuts the
+    chain short (`remaining`), a rejected guess undoes the rest of its chain with one k_unmerge, and
+    tokens() reads the stream behind it.  About 2,000 merges: the early ones touch most tiles and
+    are mispredicted most.  (The reference comparison of chains: test_gpu_parity.py.)"""
+    from shredword.cbase import lib
+    ts = []
+    for k in (1, chain):
+        t = _trainer(vocab_size=6000, unk_id=0, character_coverage=0.9995, min_pair_freq=20)
+        t.set_option("layout", layout)
+        t.set_option("chain", k)
+        t.set_option("resident", 0)
+        t.set_option("index", 0)
+        t.load_corpus(medium_corpus)
+        lib.bpe_init(t.trainer)
+        ts.append(t)
+    try:
+        done = 0
+        for chunk in [1, 2, 7, 8, 9, 64, 300] * 6:
+            na = lib.bpe_merge_batch(ts[0].trainer, chunk)
+            nb = lib.bpe_merge_batch(ts[1].trainer, chunk)
+            assert na == nb == chunk
+            xa, xb = ts[0].tokens(), ts[1].tokens()
+            assert xa.shape == xb.shape and (xa == xb).all(), f"streams differ after {done + na} merges"
+            done += na
+        assert done > 2000
+        st = ts[1].stats()
+        assert st["spec_hits"] > 0 and st["spec_misses"] > 0
+        assert st["resident_launches"] == 0 and st["index_merges"] == 0
+    finally:
+        for t in ts:
+            t.destroy()
 
 
 @pytest.mark.parametrize("tokens,depth", [("lds", 1), ("hbm", 1), ("lds", 2), ("hbm", 3)])

@@ -254,6 +254,59 @@ def test_stream_layout_matches_reference(name, case_corpus, tmp_path):
     _check(case, _train(case, corpus, tmp_path, "stream"))
 
 
+STREAM_CASES = ["c1_ascii10m_v8192", "ascii1m_v3000_mpf2", "adv_unk0", "adv_unkm1", "ascii1m_unk7_cov09", "small_v300"]
+CHAINED = ([("types", n) for n in API_CASES if n not in DEEP] + [("stream", n) for n in STREAM_CASES])
+
+
+def _chain_stats(case, st):
+    """Chains formed (tests/test_chain_cpu.py::test_goldens_form_chains) on the launch path."""
+    assert st["resident_launches"] == 0 and st["index_merges"] == 0
+    if case["merges"] >= 50:
+        assert st["spec_hits"] > 0 and st["spec_misses"] > 0
+
+
+@pytest.mark.parametrize("chain", [2, 8])
+@pytest.mark.parametrize("layout,name", CHAINED)
+def test_chained_launch_matches_reference(layout, name, chain, case_corpus, tmp_path):
+    """The launch path with chains (`chain` = 2, 8): the selected merge and its predicted successors
+    in one k_merge, the confirmed ones collected from it, the rejected tail undone by one k_unmerge."""
+    case, corpus = case_corpus(name)
+    st = {}
+    _check(case, _train(case, corpus, tmp_path, layout, resident=0, index=0, stats=st, chain=chain))
+    _chain_stats(case, st)
+
+
+@pytest.mark.parametrize("name", ["mixed24m_v64000_cov9995_mpf2"])
+def test_chained_launch_deep_matches_reference(name, case_corpus, tmp_path):
+    """Chains of 8 through the deep runs: ids above 32 k in the chain-indexed key space (8 key ranges
+    of 4 * (slot capacity + 1)) and the delta tables grown while training."""
+    case, corpus = case_corpus(name)
+    st = {}
+    _check(case, _train(case, corpus, tmp_path, "types", resident=0, index=0, stats=st, chain=8))
+    _chain_stats(case, st)
+
+
+@pytest.mark.parametrize("groups,chain", [(1, 1), (8, 1), (32, 1), (33, 1), (40, 1), (256, 1), (33, 8)])
+def test_merge_grid_sizes_match_reference(groups, chain, case_corpus, tmp_path, monkeypatch):
+    """k_merge's completion ticket at the grid sizes that tell its forms apart, on the stream layout's
+    9,804 tiles (307 windows of 32): one counter up to 32 workgroups; above that tickets sharded by
+    blockIdx % 8 -- 33 (groups of 5, 4, 4, ...), 40, 256 -- and the last workgroup's gather of one
+    region header per thread.  SHREDWORD_MERGE_GROUPS is read when the device is created."""
+    from test_gpu_shapes import check_grids, parse_merge_log
+    case, corpus = case_corpus("c1_ascii10m_v8192")
+    log = tmp_path / "merge.log"
+    monkeypatch.setenv("SHREDWORD_MERGE_GROUPS", str(groups))
+    monkeypatch.setenv("SHREDWORD_MERGE_LOG", str(log))
+    st = {}
+    _check(case, _train(case, corpus, tmp_path, "stream", stats=st, chain=chain))
+    launches, undos = parse_merge_log(log.read_text())
+    check_grids(launches, groups)
+    assert st["num_tiles"] > 32 * 256
+    assert any(c["grid"] == groups for c in launches), sorted({c["grid"] for c in launches})
+    if chain > 1:
+        assert any(c["n"] == 8 and c["grid"] == groups for c in launches) and any(u["nundo"] >= 2 for u in undos)
+
+
 @pytest.mark.parametrize("name", [n for n in golden_cases() if n.startswith("cli_")])
 def test_cli_matches_reference(name, case_corpus, tmp_path):
     case, corpus = case_corpus(name)

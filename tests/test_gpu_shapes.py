@@ -84,23 +84,115 @@ PATHS = {
     "launch": ("types", {"resident": 0, "index": 0}, {}),
     "launch_no_speculation": ("types", {"resident": 0, "index": 0, "speculate": 0}, {}),
     "stream": ("stream", {}, {}),
+    # chained launches: the selected merge and up to 7 predicted successors in one k_merge, the
+    # rejected tail undone by one k_unmerge (tests/test_chain_cpu.py: which shapes form chains)
+    "launch_chain2": ("types", {"resident": 0, "index": 0, "chain": 2}, {}),
+    "launch_chain8": ("types", {"resident": 0, "index": 0, "chain": 8}, {}),
+    "stream_chain2": ("stream", {"chain": 2}, {}),
+    "stream_chain8": ("stream", {"chain": 8}, {}),
+    "launch_chain8_verify": ("types", {"resident": 0, "index": 0, "chain": 8, "verify_argmax": 1}, {}),
+    # k_merge's grid cap: one completion counter up to 32 workgroups, tickets sharded by
+    # blockIdx % 8 above (33: groups of 5, 4, 4, ...)
+    "launch_groups1": ("types", {"resident": 0, "index": 0}, {"SHREDWORD_MERGE_GROUPS": "1"}),
+    "launch_groups8": ("types", {"resident": 0, "index": 0}, {"SHREDWORD_MERGE_GROUPS": "8"}),
+    "launch_groups32": ("types", {"resident": 0, "index": 0}, {"SHREDWORD_MERGE_GROUPS": "32"}),
+    "launch_groups33": ("types", {"resident": 0, "index": 0}, {"SHREDWORD_MERGE_GROUPS": "33"}),
+    "launch_groups40": ("types", {"resident": 0, "index": 0}, {"SHREDWORD_MERGE_GROUPS": "40"}),
+    "launch_chain8_groups33": ("types", {"resident": 0, "index": 0, "chain": 8}, {"SHREDWORD_MERGE_GROUPS": "33"}),
 }
+CHAIN_PATHS = [p for p in PATHS if "chain" in p]
+LOGGED_PATHS = [p for p in PATHS if "chain" in p or "groups" in p]
 # k_resident must really run here: every tile at most kWaveTok tokens.  (tile_edge holds words of 1024
 # tokens and more, which plan_resident refuses for the whole table; tile_edge_short is its part of
 # words up to 1023 tokens.)
 RESIDENT_SHAPES = ["strip_edge", "tile_edge_short"] + sc.TILE_FILL
 
 
+# The shapes whose training forms chains (tests/test_chain_cpu.py proves it from the host logic alone):
+# the degenerate ones end before a chain can (at most 7 merges; `remaining` cuts the chain to 1).
+CHAIN_SHAPES = [n for n in sc.TRAINER_SHAPES if n not in sc.DEGENERATE]
+_MERGE_LOGS = {}
+
+
+def parse_merge_log(text):
+    """SHREDWORD_MERGE_LOG -> (launches, undos).  `C seq X0 n_iter grid n occurrences records spilled
+    wide` is a collected k_merge launch of n merges over n_iter candidate tiles (spilled: records that
+    went through the global delta tables, wide: k_collect ran); `R seq X ntiles nundo` a k_unmerge of
+    nundo merges from X over ntiles tiles."""
+    launches, undos = [], []
+    for line in text.splitlines():
+        f = line.split()
+        if f[0] == "C":
+            launches.append(dict(zip(("seq", "X0", "n_iter", "grid", "n", "occ", "records", "spilled", "wide"),
+                                     (int(v) for v in f[1:10]))))
+        elif f[0] == "R":
+            undos.append(dict(zip(("seq", "X", "ntiles", "nundo"), (int(v) for v in f[1:5]))))
+    return launches, undos
+
+
+def check_grids(launches, cap):
+    """One filter window of 32 candidate tiles per workgroup and pass, up to the cap."""
+    for c in launches:
+        assert c["grid"] == min((c["n_iter"] + 31) // 32, cap), c
+
+
+@pytest.fixture(scope="module")
+def logged_run(shape_corpus, tmp_path_factory):
+    """(name, path) -> (outputs, stats, launches, undos) of one training with the merge log on; run
+    once per module, so the per-set assertions below share the per-case trainings."""
+    def get(name, path):
+        if (name, path) not in _MERGE_LOGS:
+            case, corpus = shape_corpus(name)
+            layout, opts, env = PATHS[path]
+            tmp = tmp_path_factory.mktemp(f"{name}_{path}")
+            env = dict(env, SHREDWORD_MERGE_LOG=str(tmp / "merge.log"))
+            old = {k: os.environ.get(k) for k in env}
+            os.environ.update(env)
+            try:
+                got, st = _train(case, corpus, tmp, layout, **opts)
+            finally:
+                for k, v in old.items():
+                    if v is None:
+                        os.environ.pop(k, None)
+                    else:
+                        os.environ[k] = v
+            _MERGE_LOGS[(name, path)] = (got, st) + parse_merge_log(open(tmp / "merge.log").read())
+        return _MERGE_LOGS[(name, path)]
+    return get
+
+
 @pytest.mark.parametrize("path", list(PATHS))
 @pytest.mark.parametrize("name", sc.TRAINER_SHAPES)
-def test_shape_matches_reference(name, path, shape_corpus, tmp_path, monkeypatch):
+def test_shape_matches_reference(name, path, shape_corpus, tmp_path, monkeypatch, logged_run):
     case, corpus = shape_corpus(name)
     layout, opts, env = PATHS[path]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    got, st = _train(case, corpus, tmp_path, layout, **opts)
+    if path in LOGGED_PATHS:
+        got, st, launches, undos = logged_run(name, path)
+    else:
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        got, st = _train(case, corpus, tmp_path, layout, **opts)
     _check(case, got)
     n = case["merges"]
+    if path in LOGGED_PATHS:
+        cap = int(env.get("SHREDWORD_MERGE_GROUPS", 256))
+        check_grids(launches, cap)
+        assert sum(c["n"] for c in launches) - sum(u["nundo"] for u in undos) == n or st["num_tiles"] == 0
+        assert st["index_merges"] == 0
+        if path == "launch_groups1":
+            assert all(c["grid"] == 1 for c in launches)
+    if path in CHAIN_PATHS and name in CHAIN_SHAPES:
+        k = opts["chain"]
+        assert st["resident_launches"] == 0 and st["index_merges"] == 0
+        if path != "launch_chain8_verify":  # (the argmax check undoes the tail before every select)
+            assert st["spec_hits"] > 0 and st["spec_misses"] > 0
+        assert max(c["n"] for c in launches) == k and any(c["n"] == k for c in launches)
+        if k == 8:
+            assert any(u["nundo"] >= 2 for u in undos)
+        else:
+            assert undos and all(u["nundo"] == 1 for u in undos)
+    if path == "launch_chain8_verify":
+        assert st["verify_failures"] == 0 and st["verify_checks"] == n
     if path == "hybrid_verify":
         assert st["verify_failures"] == 0 and st["verify_checks"] == n
     if path.startswith("index_") and n > 0:
@@ -154,6 +246,74 @@ def test_shape_rollback_restores_long_words(name, layout, shape_corpus):
             assert after.shape == before.shape and (after == before).all(), pair
     finally:
         t.destroy()
+
+
+@pytest.mark.parametrize("path", CHAIN_PATHS)
+def test_chain_paths_cover_both_candidate_modes(path, logged_run):
+    """Over the shapes that chain, per path: launches that scanned the union of the chain's candidate
+    tile lists (n_iter < tiles) and launches that scanned every tile, both with n > 1; and the
+    records' way out is reported (spilled / wide: see parse_merge_log)."""
+    listed = full = 0
+    for name in CHAIN_SHAPES:
+        _, st, launches, _ = logged_run(name, path)
+        chains = [c for c in launches if c["n"] > 1]
+        assert chains
+        listed += sum(c["n_iter"] < st["num_tiles"] for c in chains)
+        full += sum(c["n_iter"] == st["num_tiles"] for c in chains)
+        assert all(c["n_iter"] <= st["num_tiles"] for c in launches)
+    assert listed > 0 and full > 0
+
+
+def test_grid_caps_bound_every_launch(logged_run):
+    """SHREDWORD_MERGE_GROUPS on the shapes: at most 254 tiles here, so at most 8 workgroups (the
+    single completion counter); under the cap 1 every launch is one workgroup, under 8 and above
+    some launch has 8.  (Grids of 33 and more: test_gpu_parity.py::test_merge_grid_sizes_match_reference, on a
+    table of 9,804 tiles.)"""
+    for path in [p for p in LOGGED_PATHS if "groups" in p]:
+        cap = int(PATHS[path][2]["SHREDWORD_MERGE_GROUPS"])
+        grids = set()
+        for name in ("tile_edge", "tile_fill32_p1"):
+            grids |= {c["grid"] for c in logged_run(name, path)[2]}
+        assert max(grids) == min(cap, 3), (path, grids)   # types: 90 and 33 tiles -> 3 and 2 windows
+    grids = {c["grid"] for c in logged_run("tile_edge", "stream_chain8")[2]}
+    assert max(grids) == 8, grids                         # stream: 254 tiles -> 8 windows
+
+
+@pytest.mark.parametrize("layout", ["types", "stream"])
+@pytest.mark.parametrize("name", ["tile_edge", "chunk_edge"])
+def test_shape_chained_undo_restores_long_words(name, layout, shape_corpus, tmp_path, monkeypatch):
+    """k_unmerge with several merges to undo over words longer than a tile and longer than a chunk:
+    56 merges in bpe_merge_batch steps of 8 under chain = 8, the device token stream after every step
+    equal to that of a trainer without speculation stepped alongside.  A rejected guess undoes the
+    rest of its chain at once, in place, over the multi-chunk tiles; the merge log shows undos of
+    >= 2 merges and launches of 8.  (Steps of one merge would not do: `remaining` = 1 cuts every
+    chain to 1, tests/test_chain_cpu.py::test_stepped_training_chains_only_in_batches.)"""
+    from shredword.cbase import lib
+    case, corpus = shape_corpus(name)
+    log = tmp_path / "merge.log"
+    ref = _trainer(case, layout, resident=0, index=0, chain=1, speculate=0)
+    t = _trainer(case, layout, resident=0, index=0, chain=8)
+    try:
+        ref.load_corpus(corpus)
+        monkeypatch.setenv("SHREDWORD_MERGE_LOG", str(log))   # read when the device is created, at the load
+        t.load_corpus(corpus)
+        monkeypatch.delenv("SHREDWORD_MERGE_LOG")
+        for x in (ref, t):
+            lib.bpe_init(x.trainer)
+        assert ref.tokens().size > 50_000
+        for step in range(7):
+            assert lib.bpe_merge_batch(ref.trainer, 8) == 8
+            assert lib.bpe_merge_batch(t.trainer, 8) == 8
+            want, got = ref.tokens(), t.tokens()
+            assert got.shape == want.shape and (got == want).all(), f"streams differ after {8 * step + 8} merges"
+        st = t.stats()
+    finally:
+        ref.destroy()
+        t.destroy()
+    assert st["spec_hits"] > 0 and st["spec_misses"] > 0 and st["resident_launches"] == 0 and st["index_merges"] == 0
+    launches, undos = parse_merge_log(log.read_text())
+    assert any(c["n"] == 8 for c in launches)
+    assert any(u["nundo"] >= 2 and u["ntiles"] > 0 for u in undos)
 
 
 # ---- the on-device word count ----------------------------------------------------------------------
