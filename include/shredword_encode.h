@@ -689,6 +689,108 @@ int64_t shred_mlm_device(ShredEncoder* enc, const void* ids, size_t n, const voi
 int64_t shred_mlm_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
                        const ShredMlmOpts* opts, const int64_t* starts, int32_t* out, int32_t* labels);
 
+/* ---- span-corruption inputs and targets on the GPU (T5 / UL2 denoising) ----------------------------
+ *
+ * The encoder-decoder denoising objective (T5, UL2, ByT5, BART-style infilling) removes spans of
+ * tokens from the input, leaves one sentinel where each was, and asks the decoder for the spans, each
+ * behind its sentinel.  These calls work on the flat (ids, row_off) pair and return two flat streams
+ * in the same format, the input and the target, so pad, pack, window and decode take both unchanged.
+ *
+ * Inputs:
+ *   ids         n int32.
+ *   row_off     the usual rows + 1 int64, or NULL with rows == 0 for one row; validated as elsewhere (-6).
+ *   opts        the scalar options, ShredCorruptOpts below:
+ *     index_base, seed   as in ShredMlmOpts.
+ *     p_start            in [0, 1]: the probability that a position starts a span.
+ *     len_cum, len_n     host pointer to 1 <= len_n <= SHRED_CORRUPT_MAX_SPAN uint64 values
+ *                        C_1 <= ... <= C_len_n with C_len_n == 2^32; C_i = 2^32 * P(L <= i) for the
+ *                        span length L.  Anything else returns -1.
+ *     sentinel_first, sentinel_step, sentinel_n
+ *                        sentinel j is S_j = sentinel_first + j * sentinel_step, computed in int32;
+ *                        -1 when sentinel_n > 0 and S_{sentinel_n - 1} leaves int32, or sentinel_n < 0.
+ *                        T5 uses (V - 1, -1, 100).
+ *     final_sentinel     non-zero: every target row ends with the next unused sentinel (T5's closing one).
+ *     protect, protect_n, protect_specials   as in ShredMlmOpts, with the same limit.
+ *
+ * Definitions.  mix, G, d(x, c) and T(q) are those of the masked-LM section; the constants are
+ * START = (1 << 40) + 2 and LEN = (1 << 40) + 3, so one seed gives draws unrelated to dropout and masking.
+ *   Position k, with h = index_base + k:
+ *             starts a span iff (d(h, START) >> 32) < T(p_start), whatever its id;
+ *             has the length L(k) = 1 + #{ i in [1, len_n) : v >= C_i }, v = d(h, LEN) >> 32;
+ *             has the reach min(k + L(k), the end of k's row).
+ *   Token j is noise iff it is not guarded (the protect list, and the specials under protect_specials)
+ *             and some start k has k <= j < reach(k).  A reach never passes a row's end, so no span
+ *             crosses rows; a guarded token inside a span stays in the input and splits it.
+ *   A run is a maximal sequence of consecutive noise tokens of one row.  The runs of a row have the
+ *             ranks 0, 1, ...  With Rmax = max(sentinel_n - (final_sentinel != 0), 0), the runs of
+ *             rank >= Rmax are not corrupted: their tokens count as ordinary tokens from here on.
+ *             J_r: the number of corrupted runs of row r.
+ *   Input row r:   the row's tokens in order, every corrupted run replaced by its one sentinel S_rank.
+ *   Target row r:  for every corrupted run in order, S_rank and then the run's tokens; with
+ *             final_sentinel and sentinel_n > 0, S_{J_r} after them.  A row without noise (an empty
+ *             one too) is then just [S_0].
+ *
+ * Outputs:
+ *   in_ids, tgt_ids          in_cap and tgt_cap int32: the two streams.
+ *   in_row_off, tgt_row_off  rows + 1 int64 each (2 without row_off), in the line_off format over
+ *                            their own streams.
+ *   in_src                   NULL, or in_cap int64: for every input id, the index in ids of a kept
+ *                            token, or of its run's first token for a sentinel.  The same index into
+ *                            the starts of shred_encode_spans / shred_encode_docs is its byte offset.
+ *   *tgt_n                   (may be NULL) T_tgt, the number of target ids.
+ *
+ * Returns T_in, the number of input ids.  T_in <= n, because every token puts at most one id into
+ * the input (itself, or its run's sentinel in the place of the run's first token).  T_tgt <= 2 n +
+ * rows, because a token puts at most two ids into the target (a run of one token: its sentinel and
+ * itself) and a row at most one closing sentinel.  So in_cap = n and tgt_cap = 2 n + rows (2 n + 1
+ * without row_off) always suffice.  If in_ids or tgt_ids is NULL, or a cap is too small, nothing but
+ * *tgt_n is written: the sizing call.
+ *
+ * Errors, with nothing written: -1 bad argument (above; p_start outside [0, 1] or NaN; protect_n above
+ * the limit; in_ids and tgt_ids without both offset arrays; in_ids or tgt_ids aliasing ids) or HIP
+ * error; -6 bad row_off.  (A HIP error after the first piece of shred_corrupt_rows leaves the earlier
+ * pieces' output in place.)
+ *
+ * A decision depends on (seed, index_base + k, ids) alone: host and device calls, and every piece
+ * size, agree, and a new seed (per epoch, say) gives a new corruption.
+ *
+ * The corruption scratch (three result words, events, 1 B per id and 48 B per 1024 ids of the largest
+ * call, the scans' scratch and the host call's staging) is allocated on the first corrupt call and
+ * freed with the encoder, so the other calls' footprints are unchanged.
+ */
+#define SHRED_CORRUPT_MAX_SPAN 32
+
+typedef struct ShredCorruptOpts {
+  uint64_t index_base;
+  uint64_t seed;
+  double p_start;
+  const uint64_t* len_cum;
+  size_t len_n;
+  int32_t sentinel_first, sentinel_step, sentinel_n;
+  int final_sentinel;
+  const int32_t* protect;
+  size_t protect_n;
+  int protect_specials;
+} ShredCorruptOpts;
+
+/* All buffers on the encoder's device (row_off is validated there, and a bad one keeps the later
+ * passes from writing); queued on `stream` (NULL = the encoder's own) and synchronised before
+ * return.  Every buffer needs only its element's alignment, so tensor views fit.  kernel_ms (may be
+ * NULL) receives the device time of the passes. */
+int64_t shred_corrupt_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             const ShredCorruptOpts* opts, void* in_ids, size_t in_cap, void* in_row_off, void* in_src,
+                             void* tgt_ids, size_t tgt_cap, void* tgt_row_off, size_t* tgt_n, void* stream,
+                             double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget
+ * of the batch calls (one row is taken whole, however long).  Each piece runs the device passes with
+ * index_base + the index of its first id; spans never cross rows and positions are global, so the
+ * result is the same for every piece size.  row_off is validated on the host before anything is
+ * staged.  Caps below n and 2 n + rows cost a round of counting passes before the writing one. */
+int64_t shred_corrupt_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           const ShredCorruptOpts* opts, int32_t* in_ids, size_t in_cap, int64_t* in_row_off,
+                           int64_t* in_src, int32_t* tgt_ids, size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -661,4 +661,62 @@ int64_t shred_mlm_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const in
   return enc->dev->mask_host(ids, n, row_off, rows, o, starts, enc->lens, out, labels);
 }
 
+namespace {
+// What the two span-corruption calls refuse before any work (0 or -1), and their options.
+int corrupt_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                 const ShredCorruptOpts* o, const void* in_ids, const void* in_row_off, const void* tgt_ids,
+                 const void* tgt_row_off, shred::EncodeDevice::CorruptOpts* c) {
+  if (!enc || !o || (n && !ids) || (!row_off && rows)) return -1;
+  if (in_ids && tgt_ids && (!in_row_off || !tgt_row_off)) return -1;
+  if (n && (in_ids == ids || tgt_ids == ids)) return -1;
+  const uint64_t t_start = mlm_threshold(o->p_start);
+  if (t_start == ~0ull) return -1;
+  if (o->len_n < 1 || o->len_n > SHRED_CORRUPT_MAX_SPAN || !o->len_cum) return -1;
+  for (size_t i = 1; i < o->len_n; ++i)
+    if (o->len_cum[i - 1] > o->len_cum[i]) return -1;
+  if (o->len_cum[o->len_n - 1] != (1ull << 32)) return -1;
+  if (o->sentinel_n < 0) return -1;
+  if (o->sentinel_n > 0) {
+    const int64_t last = (int64_t)o->sentinel_first + (int64_t)(o->sentinel_n - 1) * (int64_t)o->sentinel_step;
+    if (last < (int64_t)INT32_MIN || last > (int64_t)INT32_MAX) return -1;
+  }
+  if (o->protect_n > SHRED_MLM_MAX_PROTECT || (o->protect_n && !o->protect)) return -1;
+  const int fin = o->final_sentinel != 0;
+  const int32_t sp_lo = (int32_t)(256 + enc->first.size());
+  *c = shred::EncodeDevice::CorruptOpts{};
+  c->index_base = o->index_base, c->seed = o->seed, c->t_start = t_start, c->len_n = (uint32_t)o->len_n;
+  for (size_t i = 0; i < o->len_n; ++i) c->len_cum[i] = o->len_cum[i];
+  c->sent_first = o->sentinel_first, c->sent_step = o->sentinel_step;
+  c->rmax = o->sentinel_n > fin ? (uint64_t)(o->sentinel_n - fin) : 0;
+  c->closing = fin && o->sentinel_n > 0;
+  c->sp_lo = sp_lo, c->sp_hi = (int32_t)(sp_lo + enc->num_specials);
+  c->protect_specials = o->protect_specials != 0, c->protect_n = (uint32_t)o->protect_n;
+  for (size_t i = 0; i < o->protect_n; ++i) c->protect[i] = o->protect[i];
+  return 0;
+}
+}  // namespace
+
+int64_t shred_corrupt_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             const ShredCorruptOpts* opts, void* in_ids, size_t in_cap, void* in_row_off, void* in_src,
+                             void* tgt_ids, size_t tgt_cap, void* tgt_row_off, size_t* tgt_n, void* stream,
+                             double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::CorruptOpts o;
+  if (const int r = corrupt_args(enc, ids, n, row_off, rows, opts, in_ids, in_row_off, tgt_ids, tgt_row_off, &o)) return r;
+  return enc->dev->corrupt((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, (int32_t*)in_ids, in_cap,
+                           (int64_t*)in_row_off, (int64_t*)in_src, (int32_t*)tgt_ids, tgt_cap, (int64_t*)tgt_row_off,
+                           tgt_n, stream, kernel_ms);
+}
+
+int64_t shred_corrupt_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           const ShredCorruptOpts* opts, int32_t* in_ids, size_t in_cap, int64_t* in_row_off,
+                           int64_t* in_src, int32_t* tgt_ids, size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n) {
+  shred::EncodeDevice::CorruptOpts o;
+  if (const int r = corrupt_args(enc, ids, n, row_off, rows, opts, in_ids, in_row_off, tgt_ids, tgt_row_off, &o)) return r;
+  if (!shred::batch_rows_fit(rows)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  return enc->dev->corrupt_host(ids, n, row_off, rows, o, in_ids, in_cap, in_row_off, in_src, tgt_ids, tgt_cap,
+                                tgt_row_off, tgt_n);
+}
+
 }  // extern "C"

@@ -222,6 +222,32 @@ class EncodeDevice {
   int64_t mask_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MaskOpts& o,
                     const int64_t* starts, const std::vector<int32_t>& lens, int32_t* out, int32_t* labels);
 
+  // ---- span-corruption inputs and targets (batch_corrupt.hip; shred_corrupt_*).  The callers have
+  // checked the arguments' ranges and turned p_start into a threshold.  corrupt takes device buffers
+  // and returns T_in, -1 or -6, with T_tgt in *tgt_n; the outputs are written when in_ids and tgt_ids
+  // are given and the caps suffice.  corrupt_host takes host buffers whose row_off the caller has
+  // checked on the host and returns T_in or -1.
+  static constexpr int kCorruptMaxSpan = 32;  // SHRED_CORRUPT_MAX_SPAN
+  struct CorruptOpts {
+    uint64_t index_base, seed;
+    uint64_t t_start;                    // T(p_start)
+    uint32_t len_n;
+    uint64_t len_cum[kCorruptMaxSpan];   // C_1 .. C_len_n
+    int32_t sent_first, sent_step;
+    uint64_t rmax;                       // runs of rank >= rmax are kept
+    bool closing;                        // every target row ends with a sentinel
+    int32_t sp_lo, sp_hi;                // the registered specials are the ids [sp_lo, sp_hi)
+    bool protect_specials;
+    uint32_t protect_n;
+    int32_t protect[kMaskMaxProtect];
+  };
+  int64_t corrupt(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const CorruptOpts& o,
+                  int32_t* in_ids, size_t in_cap, int64_t* in_row_off, int64_t* in_src, int32_t* tgt_ids,
+                  size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n, void* stream, double* kernel_ms);
+  int64_t corrupt_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const CorruptOpts& o,
+                       int32_t* in_ids, size_t in_cap, int64_t* in_row_off, int64_t* in_src, int32_t* tgt_ids,
+                       size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n);
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -263,7 +289,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kPasses };
+              kCorrupt, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

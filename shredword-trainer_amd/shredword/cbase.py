@@ -238,3 +238,18 @@ lib.shred_mlm_device.argtypes = _mlm_rows + [c_void_p, POINTER(c_double)]
 lib.shred_mlm_device.restype = c_int64
 lib.shred_mlm_rows.argtypes = _mlm_rows
 lib.shred_mlm_rows.restype = c_int64
+# span-corruption inputs and targets: ids, n, row_off, rows, opts, in_ids, in_cap, in_row_off, in_src, tgt_ids,
+# tgt_cap, tgt_row_off, tgt_n
+class ShredCorruptOpts(ctypes.Structure):
+    _fields_ = [("index_base", c_uint64), ("seed", c_uint64), ("p_start", c_double), ("len_cum", POINTER(c_uint64)),
+                ("len_n", c_size_t), ("sentinel_first", c_int32), ("sentinel_step", c_int32),
+                ("sentinel_n", c_int32), ("final_sentinel", c_int), ("protect", POINTER(c_int32)),
+                ("protect_n", c_size_t), ("protect_specials", c_int)]
+
+
+_corrupt_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredCorruptOpts), c_void_p, c_size_t,
+                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(c_size_t)]
+lib.shred_corrupt_device.argtypes = _corrupt_rows + [c_void_p, POINTER(c_double)]
+lib.shred_corrupt_device.restype = c_int64
+lib.shred_corrupt_rows.argtypes = _corrupt_rows
+lib.shred_corrupt_rows.restype = c_int64

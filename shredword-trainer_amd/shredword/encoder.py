@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from .cbase import ShredMlmOpts, lib
+from .cbase import ShredCorruptOpts, ShredMlmOpts, lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
@@ -32,6 +32,7 @@ BATCH_STAGE = 512
 # batch_pair.hip: the strategies of shred_pair_*, by number
 PAIR_TRUNCATION = ("longest_first", "only_first", "only_second", "window_second")
 MLM_MAX_PROTECT = 16   # SHRED_MLM_MAX_PROTECT
+CORRUPT_MAX_SPAN = 32  # SHRED_CORRUPT_MAX_SPAN
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -977,6 +978,129 @@ class BPEEncoder:
                 lab_kw[k] = ignore_id
         lab_batch = self.pad_device(labels, row, **lab_kw)[0]
         return batch, lab_batch, lengths, attn, selected
+
+    # ---- span-corruption inputs and targets (include/shredword_encode.h, shred_corrupt_*) -----------
+
+    @staticmethod
+    def corrupt_lengths(lengths=(1, 5), length_probs=None):
+        """-> (len_cum, mean): the C ABI's C_1 .. C_m (Python ints, C_i = 2^32 * P(L <= i), C_m = 2^32) and the
+        mean span length.  lengths=(lo, hi): uniform on lo .. hi (C_i = 0 below lo, then equal steps);
+        length_probs: P(L = 1), .., P(L = m) directly."""
+        if length_probs is not None:
+            probs = [float(q) for q in length_probs]
+            if not 1 <= len(probs) <= CORRUPT_MAX_SPAN or any(not 0.0 <= q <= 1.0 for q in probs):
+                raise ValueError(f"length_probs holds 1 to {CORRUPT_MAX_SPAN} probabilities")
+            cum = [min(int(sum(probs[:i]) * 4294967296.0), 2 ** 32) for i in range(1, len(probs) + 1)]
+            cum[-1] = 2 ** 32
+            if any(a > b for a, b in zip(cum, cum[1:])):
+                raise ValueError("length_probs must sum to 1")
+            total = sum(probs)
+            return cum, sum((i + 1) * q for i, q in enumerate(probs)) / (total if total > 0 else 1.0)
+        lo, hi = (int(v) for v in lengths)
+        if not 1 <= lo <= hi <= CORRUPT_MAX_SPAN:
+            raise ValueError(f"lengths must be (lo, hi) with 1 <= lo <= hi <= {CORRUPT_MAX_SPAN}")
+        k = hi - lo + 1
+        return [0 if i < lo else ((i - lo + 1) * 2 ** 32) // k for i in range(1, hi + 1)], (lo + hi) / 2.0
+
+    def _corrupt_opts(self, sentinel_first, sentinel_step, sentinels, p_start, noise_density, lengths, length_probs,
+                      seed, final_sentinel, protect, protect_specials, index_base):
+        """-> (ShredCorruptOpts as the C ABI takes it, the arrays its pointers keep alive)."""
+        import math
+        cum, mean = self.corrupt_lengths(lengths, length_probs)
+        if p_start is None:
+            nd = float(noise_density)
+            if not 0.0 <= nd < 1.0:
+                raise ValueError("noise_density must be in [0, 1)")
+            p_start = min(1.0, -math.log(1.0 - nd) / mean)
+        p_start = float(p_start)
+        if not 0.0 <= p_start <= 1.0:
+            raise ValueError("p_start must be a probability in [0, 1]")
+        first, step, sn = self._int32("sentinel_first", sentinel_first), self._int32("sentinel_step", sentinel_step), \
+            int(sentinels)
+        if not 0 <= sn < 2 ** 31:
+            raise ValueError("sentinels must be in [0, INT32_MAX]")
+        if sn:
+            self._int32("the last sentinel", first + (sn - 1) * step)
+        prot = np.array([self._int32("protect", v) for v in protect], dtype=np.int32)
+        if prot.size > MLM_MAX_PROTECT:
+            raise ValueError(f"protect holds at most {MLM_MAX_PROTECT} ids")
+        base = int(index_base)
+        if not 0 <= base < 2 ** 64:
+            raise ValueError("index_base must fit a uint64")
+        c_cum = (ctypes.c_uint64 * len(cum))(*cum)
+        opts = ShredCorruptOpts(base, int(seed) & (2 ** 64 - 1), p_start, c_cum, len(cum), first, step, sn,
+                                int(bool(final_sentinel)),
+                                prot.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if prot.size else None, prot.size,
+                                int(bool(protect_specials)))
+        return opts, (c_cum, prot)
+
+    def corrupt_rows(self, ids, row_offsets=None, *, sentinel_first, sentinel_step=-1, sentinels=100, p_start=None,
+                     noise_density=0.15, lengths=(1, 5), length_probs=None, seed=0, final_sentinel=True, protect=(),
+                     protect_specials=True, index_base=0, src=False):
+        """-> (in_ids, in_row_offsets, tgt_ids, tgt_row_offsets[, in_src]): span-corruption (T5 / UL2
+        denoising) inputs and targets of the rows ids[row_offsets[r]:row_offsets[r + 1]] (None: one row),
+        both as flat streams with their own offsets, so pad / pack / window / decode take them unchanged.
+        Every position starts a span with probability p_start; a span's length is drawn from `lengths`
+        (lo, hi: uniform) or from length_probs (P(L = 1), ..); spans end with their row, and overlapping or
+        touching spans make one run.  In the input every run becomes one sentinel (sentinel j is
+        sentinel_first + j * sentinel_step; T5: V - 1 downwards); the target holds each sentinel and then
+        its run, and with final_sentinel the row's next unused sentinel at the end.  Runs beyond the
+        available sentinels are kept.  protect: up to 16 ids that are never noise (they split a span);
+        protect_specials: nor are the registered special tokens.  src: also in_src, int64 per input id, the
+        index in ids of a kept token or of a run's first token.
+        p_start None: -ln(1 - noise_density) / mean length, a first-order choice: the exact expected noise
+        share without protection is 1 - prod_{i >= 0} (1 - p_start * P(L > i)), 0.1528 for the defaults.
+        A decision is a function of (seed, index_base + the token's index) alone.  Built on the GPU."""
+        opts, _keep = self._corrupt_opts(sentinel_first, sentinel_step, sentinels, p_start, noise_density, lengths,
+                                         length_probs, seed, final_sentinel, protect, protect_specials, index_base)
+        a, row, R = self._host_rows(ids, row_offsets)
+        n = a.size
+        in_ids, tgt_ids = np.empty(max(1, n), dtype=np.int32), np.empty(2 * n + R, dtype=np.int32)
+        in_row, tgt_row = np.empty(R + 1, dtype=np.int64), np.empty(R + 1, dtype=np.int64)
+        in_src = np.empty(max(1, n), dtype=np.int64) if src else None
+        t_tgt = ctypes.c_size_t()
+        t_in = self._check_batch(lib.shred_corrupt_rows(
+            self.enc, a.ctypes.data, n, None if row is None else row.ctypes.data, 0 if row is None else R,
+            ctypes.byref(opts), in_ids.ctypes.data, n, in_row.ctypes.data, None if in_src is None else in_src.ctypes.data,
+            tgt_ids.ctypes.data, tgt_ids.size, tgt_row.ctypes.data, ctypes.byref(t_tgt)))
+        res = (in_ids[:t_in], in_row, tgt_ids[:t_tgt.value], tgt_row)
+        return res + ((in_src[:t_in],) if src else ())
+
+    def corrupt_device(self, ids, row_offsets=None, *, sentinel_first, sentinel_step=-1, sentinels=100, p_start=None,
+                       noise_density=0.15, lengths=(1, 5), length_probs=None, seed=0, final_sentinel=True, protect=(),
+                       protect_specials=True, index_base=0, src=False, stream=None):
+        """corrupt_rows on device tensors (ids 1-D int32, row_offsets 1-D int64, on the encoder's GPU; views
+        that are only element-aligned fit) -> (in_ids, in_row_offsets, tgt_ids, tgt_row_offsets[, in_src],
+        device milliseconds of the corruption passes).  The streams are views of tensors sized for the
+        bound (len(ids) and 2 len(ids) + rows), so the call runs once."""
+        import torch
+        opts, _keep = self._corrupt_opts(sentinel_first, sentinel_step, sentinels, p_start, noise_density, lengths,
+                                         length_probs, seed, final_sentinel, protect, protect_specials, index_base)
+        R = self._device_rows(ids, row_offsets)
+        n = ids.numel()
+        new = lambda dt, k: torch.empty(max(1, k), dtype=dt, device=ids.device)
+        in_ids, tgt_ids = new(torch.int32, n), new(torch.int32, 2 * n + R)
+        in_row, tgt_row = new(torch.int64, R + 1), new(torch.int64, R + 1)
+        in_src = new(torch.int64, n) if src else None
+        t_tgt, ms = ctypes.c_size_t(), ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        t_in = self._check_batch(lib.shred_corrupt_device(
+            self.enc, ids.data_ptr(), n, None if row_offsets is None else row_offsets.data_ptr(),
+            0 if row_offsets is None else R, ctypes.byref(opts), in_ids.data_ptr(), n, in_row.data_ptr(),
+            None if in_src is None else in_src.data_ptr(), tgt_ids.data_ptr(), 2 * n + R, tgt_row.data_ptr(),
+            ctypes.byref(t_tgt), st, ctypes.byref(ms)))
+        res = (in_ids[:t_in], in_row, tgt_ids[:t_tgt.value], tgt_row)
+        return res + ((in_src[:t_in],) if src else ()) + (ms.value,)
+
+    def encode_corrupted(self, text, *, specials: bool = False, doc_offsets=None, **kw):
+        """encode_lines, then corrupt_device(**kw) on the encoder's GPU: every '\\n' line of the text is one row.
+        With a list / tuple of documents (encode_batch) or with doc_offsets (encode_docs): every document is.
+        -> corrupt_device's tuple."""
+        import torch
+        ids, row = self._encode_rows(text, specials, doc_offsets)[:2]
+        d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).cuda(self.device)
+        d_row = torch.from_numpy(np.ascontiguousarray(row, dtype=np.int64)).cuda(self.device)
+        return self.corrupt_device(d_ids, d_row, **kw)
 
     def destroy(self):
         if getattr(self, "enc", None):

@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -33,7 +33,13 @@ cut from the corpus without its delimiters, with the rounds each word took; with
 from the token lengths, a delimiter before 30 % of the tokens), p = 0.15 with four protected ids: device ms (median of
 7 after two warm-up calls) and GB/s by the traffic model of batch_mask.hip, beside the torch composition on the same
 tensors in the same process (rand for selection and action, an isin protect mask, where for ids and labels; whole
-words: begins from starts, a cumsum for the word of every token and one draw per word gathered back)."""
+words: begins from starts, a cumsum for the word of every token and one draw per word gathered back); with a trailing
+`corrupt`, corrupt_device on the same ids and rows (default options: p_start from a noise density of 0.15, lengths 1..5,
+100 sentinels, the closing one, four protected ids, with in_src): device ms (median of 7 after two warm-up calls) and GB/s
+by the traffic model of batch_corrupt.hip, beside a torch composition of the same definition on the same tensors in the
+same process (rand and randint for start and length, a difference array and a cumsum for the coverage with the reach cut
+at the row's end by bucketize, run firsts, a cumsum for the rank within the row, cumsums of the two emit counts, masked
+scatters for both streams, the offsets and the closing sentinels)."""
 import os
 import subprocess
 import sys
@@ -74,7 +80,8 @@ else:
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
-    long_leg, pair, mlm = args[-1] == "long", args[-1] == "pair", args[-1] == "mlm"
+    long_leg, pair, corrupt = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt"
+    mlm = corrupt or args[-1] == "mlm"  # the corrupt leg runs on the mlm leg's stream, in its place
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -450,7 +457,8 @@ else:
             return torch_apply((torch.rand(int(word[-1].item()) + 1, device="cuda")[word] < P) & ~guarded)
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
-        for name, whole, per_id, ref in (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole)):
+        legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
+        for name, whole, per_id, ref in () if corrupt else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -463,4 +471,58 @@ else:
                   "| ms", med, "GB/s at", per_id, "B per id", per_id * n / med / 1e6, "min", ms[0], "max", ms[-1],
                   "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1], "max", t[2],
                   "selected share", picked / n, "| torch / ours", t[0] / med, flush=True)
+    if corrupt:
+        del starts
+        import math
+        R, S0, SN = row.numel() - 1, V + 99, 100
+        p_start, RMAX = -math.log(1 - 0.15) / 3.0, SN - 1
+        ar = torch.arange(n, device="cuda")
+
+        def torch_corrupt():
+            start = torch.rand(n, device="cuda") < p_start
+            L = torch.randint(1, 6, (n,), device="cuda")
+            k = start.nonzero().squeeze(1)
+            end = torch.minimum(k + L[k], row[torch.bucketize(k, row, right=True)])  # the reach, cut at the row's end
+            delta = torch.zeros(n + 1, dtype=torch.int32, device="cuda")
+            delta.index_add_(0, k, torch.ones_like(k, dtype=torch.int32))
+            delta.index_add_(0, end, -torch.ones_like(k, dtype=torch.int32))
+            noise = (delta.cumsum(0)[:n] > 0) & ~torch.isin(ids, prot)
+            begin = torch.zeros(n, dtype=torch.bool, device="cuda")
+            begin[row[:-1][row[:-1] < n]] = True
+            first = noise.clone()
+            first[1:] &= begin[1:] | ~noise[:-1]
+            c = first.cumsum(0)
+            base = (c - first.long())[begin.nonzero().squeeze(1)]        # runs before each non-empty row
+            rank = c - 1 - base[begin.cumsum(0) - 1]
+            gone = noise & (rank < RMAX)
+            sent = (S0 - rank).int()
+            keep = ~gone | first
+            in_ids, in_src = torch.where(gone, sent, ids)[keep], ar[keep]
+            kc = torch.cat([keep.new_zeros(1, dtype=torch.long), keep.cumsum(0)])
+            tg = gone.long() + (gone & first).long()
+            tc = torch.cat([tg.new_zeros(1), tg.cumsum(0)])
+            in_row, tgt_row = kc[row], tc[row] + torch.arange(R + 1, device="cuda")
+            tgt = torch.empty(int(tgt_row[-1].item()), dtype=torch.int32, device="cuda")
+            at = tc[:n] + torch.bucketize(ar, row, right=True) - 1   # the rows before close with one sentinel each
+            gf = gone & first
+            tgt[at[gf]] = sent[gf]
+            tgt[(at + first)[gone]] = ids[gone]
+            cp = torch.cat([c.new_zeros(1), c])
+            tgt[tgt_row[1:] - 1] = (S0 - (cp[row[1:]] - cp[row[:-1]]).clamp(max=RMAX)).int()
+            return in_ids, in_row, tgt, tgt_row, in_src
+
+        run = lambda: enc.corrupt_device(ids, row, sentinel_first=S0, seed=1, protect=(0, 1, 2, 3), src=True)
+        run()  # first call: allocates the corruption scratch
+        run()
+        res = [run() for _ in range(reps)]
+        ms = sorted(r[5] for r in res)
+        med = ms[len(ms) // 2]
+        t, c = events(torch_corrupt), events(run)
+        ref = torch_corrupt()
+        t_in, t_tgt = res[0][0].numel(), res[0][2].numel()
+        nbytes = 11 * n + 12 * t_in + 4 * t_tgt + 40 * R
+        print("corrupt: ids", n, "rows", R, "input ids", t_in, "target ids", t_tgt, "noise share",
+              (t_tgt - R + n - t_in) / 2 / n, "| ms", med, "GB/s by the traffic model", nbytes / med / 1e6, "min", ms[0], "max", ms[-1],
+              "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1], "max", t[2],
+              "input ids", ref[0].numel(), "target ids", ref[2].numel(), "| torch / ours", t[0] / med, flush=True)
     enc.destroy()
