@@ -791,6 +791,112 @@ int64_t shred_corrupt_rows(ShredEncoder* enc, const int32_t* ids, size_t n, cons
                            const ShredCorruptOpts* opts, int32_t* in_ids, size_t in_cap, int64_t* in_row_off,
                            int64_t* in_src, int32_t* tgt_ids, size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n);
 
+/* ---- fill-in-the-middle rows on the GPU (FIM) -------------------------------------------------------
+ *
+ * The infilling objective of decoder-only code models (Bavarian et al. 2022; SantaCoder, StarCoder, Code
+ * Llama, DeepSeek-Coder) cuts a document into prefix, middle and suffix and re-emits them with three
+ * sentinels, the middle last, so that an ordinary left-to-right model learns to fill it in.  These calls
+ * work on the flat (ids, row_off) pair and return one flat stream in the same format, so pad, pack,
+ * window and decode take it unchanged; bos / eos come from those calls as usual.
+ *
+ * Inputs:
+ *   ids         n int32.
+ *   row_off     the usual rows + 1 int64, or NULL with rows == 0 for one row; validated as elsewhere (-6).
+ *               R below is the number of rows, 1 without row_off.
+ *   opts        the scalar options, ShredFimOpts below:
+ *     row_base           uint64 added to every row index below.  The host call's pieces use it; a caller
+ *                        sharding a stream over calls may use it too.
+ *     seed               a 64-bit seed.
+ *     fim_rate, spm_rate in [0, 1]: the share of rows transformed, and of those the share in SPM order.
+ *     min_len            >= 0: shorter rows are never transformed.
+ *     pre_id, suf_id, mid_id   the three sentinels, any int32.  Callers pass registered specials' ids.
+ *   cuts        NULL, or R x 3 int64 (a, b, mode) per row; the triple -1, -1, -1 means "not
+ *               transformed".  When given, no draw is made and the rows are assembled by it (the
+ *               character-level path below uses this).  Each triple must be all -1, or have
+ *               0 <= a <= b <= L and mode in {0, 1}: anything else returns -8.
+ *
+ * Definitions.  mix, G, d(x, c) and T(q) are those of the masked-LM section; the constants are
+ * FIM = (1 << 40) + 4, CUT_A = (1 << 40) + 5, CUT_B = (1 << 40) + 6 and MODE = (1 << 40) + 7, beside
+ * START and LEN of span corruption.  Decisions are per row, not per token.  Row r of length L, with
+ * h = row_base + r:
+ *   is transformed iff L >= min_len and (d(h, FIM) >> 32) < T(fim_rate);
+ *   has the cuts x = ((d(h, CUT_A) >> 32) * (L + 1)) >> 32 and y, the same from CUT_B (in uint64
+ *             arithmetic), a = min(x, y), b = max(x, y), so 0 <= a <= b <= L: the prefix is [0, a), the
+ *             middle [a, b) and the suffix [b, L) of the row;
+ *   has the mode 1 (SPM) iff (d(h, MODE) >> 32) < T(spm_rate), else 0 (PSM).
+ *   Output row, PSM:  pre_id, prefix, suf_id, suffix, mid_id, middle.
+ *   Output row, SPM:  pre_id, suf_id, suffix, mid_id, prefix, middle (the Code Llama order).
+ *             Its length is L + 3.  A row that is not transformed is copied, length L.  L == 0 is legal
+ *             and gives the three sentinels when transformed.
+ *
+ * Outputs:
+ *   out_ids      out_cap int32: the stream.
+ *   out_row_off  R + 1 int64, in the line_off format over the stream.
+ *   out_src      NULL, or out_cap int64: for every output id the index in ids of the token it copies,
+ *                or -1 for a sentinel.  The same index into the starts of shred_encode_spans /
+ *                shred_encode_docs is its byte offset.
+ *   out_seg      NULL, or out_cap uint8, for a loss on the middle only: 0 = row not transformed,
+ *                1 = prefix, 2 = suffix, 3 = middle, 4 = sentinel.
+ *   row_info     NULL, or R x 3 int64 in the format of cuts: what was drawn or given.
+ *
+ * Returns T_out = n + 3 F, where F is the number of transformed rows; out_cap = n + 3 R always
+ * suffices.  If out_ids is NULL or out_cap < T_out, nothing is written: the sizing call.
+ *
+ * Errors, with nothing written: -1 bad argument (a rate outside [0, 1] or NaN; min_len < 0; out_ids
+ * without out_row_off; out_ids aliasing ids) or HIP error; -6 bad row_off; -8 bad cuts.  (A HIP error
+ * after the first piece of shred_fim_rows leaves the earlier pieces' output in place.)
+ *
+ * A decision depends on (seed, row_base + r, L) alone: host and device calls, and every piece size,
+ * agree, and a new seed (per epoch, say) gives a new transformation.
+ *
+ * The FIM scratch (three result words, events, 48 B per row of the largest call, the scan's scratch
+ * and the host call's staging) is allocated on the first FIM call and freed with the encoder, so the
+ * other calls' footprints are unchanged.
+ */
+typedef struct ShredFimOpts {
+  uint64_t row_base;
+  uint64_t seed;
+  double fim_rate, spm_rate;
+  int64_t min_len;
+  int32_t pre_id, suf_id, mid_id;
+} ShredFimOpts;
+
+/* All buffers on the encoder's device (row_off and cuts are validated there, and a bad one keeps the
+ * later passes from writing); queued on `stream` (NULL = the encoder's own) and synchronised before
+ * return.  Every buffer needs only its element's alignment, so tensor views fit.  kernel_ms (may be
+ * NULL) receives the device time of the passes. */
+int64_t shred_fim_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const ShredFimOpts* opts, const void* cuts, void* out_ids, size_t out_cap, void* out_row_off,
+                         void* out_src, void* out_seg, void* row_info, void* stream, double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget
+ * of the batch calls (one row is taken whole, however long).  Each piece runs the device passes with
+ * row_base + its first row and its slice of cuts, so the result is the same for every piece size.
+ * row_off and cuts are validated on the host before anything is staged.  A cap below n + 3 R costs a
+ * round of counting passes before the writing one. */
+int64_t shred_fim_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const ShredFimOpts* opts, const int64_t* cuts, int32_t* out_ids, size_t out_cap,
+                       int64_t* out_row_off, int64_t* out_src, uint8_t* out_seg, int64_t* row_info);
+
+/* Character-level cuts: the FIM paper recommends cutting the text, not the tokens, so that the model
+ * sees broken tokens at the joins.  text (n bytes) and doc_off (NULL with docs == 0: one document;
+ * else docs + 1 int64, validated as in shred_encode_docs_device, -6) on the device.  Document d, bytes
+ * [s, e) with B = e - s and h = row_base + d, takes the three draws above with L = B (min_len is in
+ * bytes here).  Both cuts are then snapped to UTF-8.  snap(p): while p > 0, p < B,
+ * (text[s + p] & 0xC0) == 0x80 and fewer than 3 steps have been taken, p -= 1.  a' = snap(a),
+ * b' = max(snap(b), a').
+ *   piece_off   3 * D + 1 int64 (D = docs, 1 without doc_off): s, s + a', s + b' for a transformed
+ *               document and s, e, e for one that is not; the last entry is n.  It is a doc_off of
+ *               3 D documents: shred_encode_docs_device encodes every piece as if alone.
+ *   doc_mode    D int8: -1 not transformed, 0 PSM, 1 SPM.
+ * With the row offsets R3 that shred_encode_docs_device returns for piece_off, document d is the row
+ * [R3[3 d], R3[3 d + 3]) with cuts = (R3[3 d + 1] - R3[3 d], R3[3 d + 2] - R3[3 d], doc_mode[d]), or all
+ * -1, for shred_fim_device.  A cut that falls inside a special token's bytes leaves ordinary text on
+ * both sides.  Returns 0, -1 (bad argument, as above, or HIP error) or -6, with nothing written then.
+ * A device-only entry point: both outputs on the device, queued and timed as above. */
+int shred_fim_cuts_device(ShredEncoder* enc, const void* text, size_t n, const void* doc_off, size_t docs,
+                          const ShredFimOpts* opts, void* piece_off, void* doc_mode, void* stream, double* kernel_ms);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -719,4 +719,66 @@ int64_t shred_corrupt_rows(ShredEncoder* enc, const int32_t* ids, size_t n, cons
                                 tgt_row_off, tgt_n);
 }
 
+namespace {
+// The scalar options of the FIM calls: 0 or -1.
+int fim_opts(const ShredFimOpts* o, shred::EncodeDevice::FimOpts* f) {
+  if (!o) return -1;
+  const uint64_t t_fim = mlm_threshold(o->fim_rate), t_spm = mlm_threshold(o->spm_rate);
+  if (t_fim == ~0ull || t_spm == ~0ull || o->min_len < 0) return -1;
+  *f = shred::EncodeDevice::FimOpts{o->row_base, o->seed, t_fim, t_spm, o->min_len, o->pre_id, o->suf_id, o->mid_id};
+  return 0;
+}
+
+// What the two token-level FIM calls refuse before any work (0 or -1), and their options.
+int fim_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+             const ShredFimOpts* o, const void* out_ids, const void* out_row_off, shred::EncodeDevice::FimOpts* f) {
+  if (!enc || (n && !ids) || (!row_off && rows)) return -1;
+  if (out_ids && !out_row_off) return -1;
+  if (n && out_ids == ids) return -1;
+  return fim_opts(o, f);
+}
+
+// The -8 case on the host: every triple all -1, or 0 <= a <= b <= L and a mode of 0 or 1.
+bool fim_cuts_ok(const int64_t* cuts, const int64_t* row_off, size_t R, size_t n) {
+  for (size_t r = 0; r < R; ++r) {
+    const int64_t a = cuts[3 * r], b = cuts[3 * r + 1], m = cuts[3 * r + 2];
+    const int64_t L = row_off ? row_off[r + 1] - row_off[r] : (int64_t)n;
+    if (a == -1 && b == -1 && m == -1) continue;
+    if (a < 0 || a > b || b > L || (m != 0 && m != 1)) return false;
+  }
+  return true;
+}
+}  // namespace
+
+int64_t shred_fim_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                         const ShredFimOpts* opts, const void* cuts, void* out_ids, size_t out_cap, void* out_row_off,
+                         void* out_src, void* out_seg, void* row_info, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::FimOpts o;
+  if (const int r = fim_args(enc, ids, n, row_off, rows, opts, out_ids, out_row_off, &o)) return r;
+  return enc->dev->fim((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, (const int64_t*)cuts,
+                       (int32_t*)out_ids, out_cap, (int64_t*)out_row_off, (int64_t*)out_src, (uint8_t*)out_seg,
+                       (int64_t*)row_info, stream, kernel_ms);
+}
+
+int64_t shred_fim_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                       const ShredFimOpts* opts, const int64_t* cuts, int32_t* out_ids, size_t out_cap,
+                       int64_t* out_row_off, int64_t* out_src, uint8_t* out_seg, int64_t* row_info) {
+  shred::EncodeDevice::FimOpts o;
+  if (const int r = fim_args(enc, ids, n, row_off, rows, opts, out_ids, out_row_off, &o)) return r;
+  if (!shred::batch_rows_fit(rows)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  if (cuts && !fim_cuts_ok(cuts, row_off, row_off ? rows : 1, n)) return -8;
+  return enc->dev->fim_host(ids, n, row_off, rows, o, cuts, out_ids, out_cap, out_row_off, out_src, out_seg, row_info);
+}
+
+int shred_fim_cuts_device(ShredEncoder* enc, const void* text, size_t n, const void* doc_off, size_t docs,
+                          const ShredFimOpts* opts, void* piece_off, void* doc_mode, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::FimOpts o;
+  if (!enc || (n && !text) || (!doc_off && docs) || !piece_off || !doc_mode || fim_opts(opts, &o)) return -1;
+  return enc->dev->fim_cuts((const uint8_t*)text, n, (const int64_t*)doc_off, docs, o, (int64_t*)piece_off,
+                            (int8_t*)doc_mode, stream, kernel_ms);
+}
+
 }  // extern "C"

@@ -248,6 +248,27 @@ class EncodeDevice {
                        int32_t* in_ids, size_t in_cap, int64_t* in_row_off, int64_t* in_src, int32_t* tgt_ids,
                        size_t tgt_cap, int64_t* tgt_row_off, size_t* tgt_n);
 
+  // ---- fill-in-the-middle rows (batch_fim.hip; shred_fim_*).  The callers have checked the arguments'
+  // ranges and turned the rates into thresholds.  fim takes device buffers (cuts: nullptr, or 3 int64
+  // per row, validated on the device) and returns T_out, -1, -6 or -8; the outputs are written when
+  // out_ids is given and out_cap suffices.  fim_host takes host buffers whose row_off and cuts the
+  // caller has checked on the host and returns T_out or -1.  fim_cuts (shred_fim_cuts_device) takes
+  // device buffers and returns 0, -1 or -6.
+  struct FimOpts {
+    uint64_t row_base, seed;
+    uint64_t t_fim, t_spm;  // T(fim_rate), T(spm_rate)
+    int64_t min_len;
+    int32_t pre_id, suf_id, mid_id;
+  };
+  int64_t fim(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const FimOpts& o, const int64_t* cuts,
+              int32_t* out_ids, size_t out_cap, int64_t* out_row_off, int64_t* out_src, uint8_t* out_seg,
+              int64_t* row_info, void* stream, double* kernel_ms);
+  int64_t fim_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const FimOpts& o,
+                   const int64_t* cuts, int32_t* out_ids, size_t out_cap, int64_t* out_row_off, int64_t* out_src,
+                   uint8_t* out_seg, int64_t* row_info);
+  int fim_cuts(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, const FimOpts& o,
+               int64_t* piece_off, int8_t* doc_mode, void* stream, double* kernel_ms);
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -289,7 +310,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kPasses };
+              kCorrupt, kFim, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -253,3 +253,19 @@ lib.shred_corrupt_device.argtypes = _corrupt_rows + [c_void_p, POINTER(c_double)
 lib.shred_corrupt_device.restype = c_int64
 lib.shred_corrupt_rows.argtypes = _corrupt_rows
 lib.shred_corrupt_rows.restype = c_int64
+# fill-in-the-middle rows: ids, n, row_off, rows, opts, cuts, out_ids, out_cap, out_row_off, out_src, out_seg, row_info
+class ShredFimOpts(ctypes.Structure):
+    _fields_ = [("row_base", c_uint64), ("seed", c_uint64), ("fim_rate", c_double), ("spm_rate", c_double),
+                ("min_len", c_int64), ("pre_id", c_int32), ("suf_id", c_int32), ("mid_id", c_int32)]
+
+
+_fim_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredFimOpts), c_void_p, c_void_p, c_size_t,
+             c_void_p, c_void_p, c_void_p, c_void_p]
+lib.shred_fim_device.argtypes = _fim_rows + [c_void_p, POINTER(c_double)]
+lib.shred_fim_device.restype = c_int64
+lib.shred_fim_rows.argtypes = _fim_rows
+lib.shred_fim_rows.restype = c_int64
+# character-level cuts: text, n, doc_off, docs, opts, piece_off, doc_mode, stream, kernel_ms
+lib.shred_fim_cuts_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredFimOpts), c_void_p,
+                                      c_void_p, c_void_p, POINTER(c_double)]
+lib.shred_fim_cuts_device.restype = c_int

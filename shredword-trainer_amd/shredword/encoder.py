@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from .cbase import ShredCorruptOpts, ShredMlmOpts, lib
+from .cbase import ShredCorruptOpts, ShredFimOpts, ShredMlmOpts, lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
@@ -1101,6 +1101,167 @@ class BPEEncoder:
         d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).cuda(self.device)
         d_row = torch.from_numpy(np.ascontiguousarray(row, dtype=np.int64)).cuda(self.device)
         return self.corrupt_device(d_ids, d_row, **kw)
+
+    # ---- fill-in-the-middle rows (include/shredword_encode.h, shred_fim_*) ---------------------------
+
+    def _fim_opts(self, pre_id, suf_id, mid_id, fim_rate, spm_rate, seed, min_len, row_base):
+        """-> ShredFimOpts as the C ABI takes it."""
+        fr, sr = float(fim_rate), float(spm_rate)
+        for name, q in (("fim_rate", fr), ("spm_rate", sr)):
+            if not 0.0 <= q <= 1.0:
+                raise ValueError(f"{name} must be a probability in [0, 1]")
+        ml, base = int(min_len), int(row_base)
+        if not 0 <= ml < 2 ** 63:
+            raise ValueError("min_len must be in [0, INT64_MAX]")
+        if not 0 <= base < 2 ** 64:
+            raise ValueError("row_base must fit a uint64")
+        return ShredFimOpts(base, int(seed) & (2 ** 64 - 1), fr, sr, ml, self._int32("pre_id", pre_id),
+                            self._int32("suf_id", suf_id), self._int32("mid_id", mid_id))
+
+    @staticmethod
+    def _check_fim(r: int) -> int:
+        if r == -8:
+            raise ValueError("cuts must hold, per row, -1 -1 -1 or 0 <= a <= b <= len(row) and a mode of 0 or 1")
+        return BPEEncoder._check_batch(r)
+
+    def fim_rows(self, ids, row_offsets=None, *, pre_id, suf_id, mid_id, fim_rate=0.5, spm_rate=0.5, seed=0,
+                 min_len=0, row_base=0, cuts=None, src=False, seg=False, info=False):
+        """-> (out_ids, out_row_offsets[, out_src][, out_seg][, row_info]): fill-in-the-middle rows of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row), a flat stream with its own offsets, so pad /
+        pack / window / decode take it unchanged.  A row of at least min_len ids is transformed with
+        probability fim_rate: cut at two uniform points into prefix, middle and suffix and re-emitted as
+        pre_id prefix suf_id suffix mid_id middle (PSM), or with probability spm_rate as pre_id suf_id suffix
+        mid_id prefix middle (SPM).  Other rows are copied.  cuts: None, or [rows, 3] int64 (a, b, mode) per
+        row, -1 -1 -1 for a row to copy: the rows are assembled by it and nothing is drawn.  src: also
+        out_src, int64 per output id, the index in ids of the token or -1 for a sentinel.  seg: also out_seg,
+        uint8 per output id: 0 row not transformed, 1 prefix, 2 suffix, 3 middle, 4 sentinel.  info: also
+        row_info, [rows, 3] int64 in the format of cuts, what was drawn or given.
+        A decision is a function of (seed, row_base + the row's index, the row's length) alone.  Built on
+        the GPU."""
+        opts = self._fim_opts(pre_id, suf_id, mid_id, fim_rate, spm_rate, seed, min_len, row_base)
+        a, row, R = self._host_rows(ids, row_offsets)
+        n = a.size
+        c = None
+        if cuts is not None:
+            c = np.ascontiguousarray(cuts, dtype=np.int64).reshape(-1)
+            if c.size != 3 * R:
+                raise ValueError("cuts must hold 3 entries per row")
+        cap = n + 3 * R
+        out, out_row = np.empty(cap, dtype=np.int32), np.empty(R + 1, dtype=np.int64)
+        o_src = np.empty(cap, dtype=np.int64) if src else None
+        o_seg = np.empty(cap, dtype=np.uint8) if seg else None
+        o_info = np.empty((R, 3), dtype=np.int64) if info else None
+        ptr = lambda x: None if x is None else x.ctypes.data
+        t = self._check_fim(lib.shred_fim_rows(
+            self.enc, a.ctypes.data, n, ptr(row), 0 if row is None else R, ctypes.byref(opts), ptr(c), out.ctypes.data,
+            cap, out_row.ctypes.data, ptr(o_src), ptr(o_seg), ptr(o_info)))
+        return (out[:t], out_row) + ((o_src[:t],) if src else ()) + ((o_seg[:t],) if seg else ()) \
+            + ((o_info,) if info else ())
+
+    def fim_device(self, ids, row_offsets=None, *, pre_id, suf_id, mid_id, fim_rate=0.5, spm_rate=0.5, seed=0,
+                   min_len=0, row_base=0, cuts=None, src=False, seg=False, info=False, stream=None):
+        """fim_rows on device tensors (ids 1-D int32, row_offsets 1-D int64, cuts [rows, 3] int64, on the
+        encoder's GPU; views that are only element-aligned fit) -> (out_ids, out_row_offsets[, out_src]
+        [, out_seg][, row_info], device milliseconds of the FIM passes).  The stream is a view of a tensor
+        sized for the bound (len(ids) + 3 rows), so the call runs once."""
+        import torch
+        opts = self._fim_opts(pre_id, suf_id, mid_id, fim_rate, spm_rate, seed, min_len, row_base)
+        R = self._device_rows(ids, row_offsets)
+        n = ids.numel()
+        if cuts is not None:
+            if not isinstance(cuts, torch.Tensor) or cuts.dtype != torch.int64 or not cuts.is_cuda \
+                    or not cuts.is_contiguous() or cuts.device != ids.device or cuts.numel() != 3 * R:
+                raise ValueError("cuts must be a contiguous int64 tensor of 3 entries per row on the ids' device")
+        cap = n + 3 * R
+        new = lambda dt, k: torch.empty(k, dtype=dt, device=ids.device)
+        out, out_row = new(torch.int32, cap), new(torch.int64, R + 1)
+        o_src = new(torch.int64, cap) if src else None
+        o_seg = new(torch.uint8, cap) if seg else None
+        o_info = new(torch.int64, 3 * R).view(R, 3) if info else None
+        ptr = lambda x: None if x is None else x.data_ptr()
+        ms = ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        t = self._check_fim(lib.shred_fim_device(
+            self.enc, ids.data_ptr(), n, ptr(row_offsets), 0 if row_offsets is None else R, ctypes.byref(opts),
+            ptr(cuts), out.data_ptr(), cap, out_row.data_ptr(), ptr(o_src), ptr(o_seg), ptr(o_info), st,
+            ctypes.byref(ms)))
+        return (out[:t], out_row) + ((o_src[:t],) if src else ()) + ((o_seg[:t],) if seg else ()) \
+            + ((o_info,) if info else ()) + (ms.value,)
+
+    def fim_cuts_device(self, text, doc_offsets=None, *, fim_rate=0.5, spm_rate=0.5, seed=0, min_len=0, row_base=0,
+                        stream=None):
+        """Character-level cuts of the documents text[doc_offsets[d]:doc_offsets[d + 1]] (device tensors as
+        encode_docs_device takes them) -> (piece_offsets, doc_mode, device milliseconds): 3 docs + 1 int64
+        offsets that cut every document into prefix, middle and suffix at UTF-8 character boundaries (a
+        document that is not transformed into itself and two empty pieces), and int8 per document: -1 not
+        transformed, 0 PSM, 1 SPM.  min_len is in bytes."""
+        import torch
+        opts = self._fim_opts(0, 0, 0, fim_rate, spm_rate, seed, min_len, row_base)
+        for name, t, dt in (("text", text, torch.uint8), ("doc_offsets", doc_offsets, torch.int64)):
+            if t is None and name != "text":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_cuda \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} CUDA tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the encoder on cuda:{self.device}")
+        if doc_offsets is not None and doc_offsets.numel() == 0:
+            raise ValueError("doc_offsets must hold docs + 1 entries")
+        D = 1 if doc_offsets is None else doc_offsets.numel() - 1
+        piece = torch.empty(3 * D + 1, dtype=torch.int64, device=text.device)
+        mode = torch.empty(max(1, D), dtype=torch.int8, device=text.device)[:D]
+        ms = ctypes.c_double()
+        st = self._stream(stream, text.device)
+        self._check_docs(lib.shred_fim_cuts_device(
+            self.enc, text.data_ptr(), text.numel(), None if doc_offsets is None else doc_offsets.data_ptr(),
+            0 if doc_offsets is None else D, ctypes.byref(opts), piece.data_ptr(), mode.data_ptr(), st,
+            ctypes.byref(ms)))
+        return piece, mode, ms.value
+
+    def encode_fim(self, text, *, doc_offsets=None, specials: bool = False, level: str = "char", starts: bool = False,
+                   **kw):
+        """Text to fill-in-the-middle rows on the GPU -> fim_device's tuple, with starts=True the byte offset
+        of every encoded token (int64, indexed by out_src) before the milliseconds.  **kw: fim_device's.
+        level="token": the rows are encoded (lines, or documents with a list / tuple or doc_offsets, as
+        encode_corrupted takes them) and fim_device cuts them between tokens.
+        level="char" (documents only; one text without doc_offsets is one document): fim_cuts_device cuts
+        the text of every document between characters, with min_len in bytes; encode_docs_device encodes
+        every piece as if alone, so the model sees the broken tokens at the joins; fim_device assembles
+        the rows by the pieces' lengths.  A cut that falls inside a special token's bytes leaves ordinary
+        text on both sides: neither part is matched as that special."""
+        import torch
+        if level not in ("char", "token"):
+            raise ValueError('level must be "char" or "token"')
+        if isinstance(text, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(text)
+        else:
+            buf = self._host_text(text)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        if level == "token":
+            if off is None:
+                ids, st, row = self._spans_host(buf, starts, True, specials)
+            else:
+                ids, row, *st = self.encode_docs(buf, off, starts=starts, specials=specials)
+                st = st[0] if starts else None
+            res = self.fim_device(dev(np.ascontiguousarray(ids, dtype=np.int32)),
+                                  dev(np.ascontiguousarray(row, dtype=np.int64)), **kw)
+            return res[:-1] + ((dev(st),) if starts else ()) + res[-1:]
+        if "cuts" in kw:
+            raise ValueError('level="char" draws the cuts itself')
+        d_buf, d_off = dev(buf), None if off is None else dev(off)
+        draw = {k: kw[k] for k in ("fim_rate", "spm_rate", "seed", "min_len", "row_base") if k in kw}
+        piece, mode, _ = self.fim_cuts_device(d_buf, d_off, **draw)
+        ids, row3, st, _ = self.encode_docs_device(d_buf, piece, starts=starts, specials=specials)
+        first = row3[0:-1:3]
+        m = mode.to(torch.int64)
+        keep = m >= 0
+        cuts = torch.stack([torch.where(keep, row3[1::3] - first, m), torch.where(keep, row3[2::3] - first, m), m],
+                           dim=1).contiguous()
+        res = self.fim_device(ids, row3[0::3].contiguous(), **dict(kw, min_len=0, cuts=cuts))
+        return res[:-1] + ((st,) if starts else ()) + res[-1:]
 
     def destroy(self):
         if getattr(self, "enc", None):

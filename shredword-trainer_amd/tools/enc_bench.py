@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -39,7 +39,11 @@ words: begins from starts, a cumsum for the word of every token and one draw per
 by the traffic model of batch_corrupt.hip, beside a torch composition of the same definition on the same tensors in the
 same process (rand and randint for start and length, a difference array and a cumsum for the coverage with the reach cut
 at the row's end by bucketize, run firsts, a cumsum for the rank within the row, cumsums of the two emit counts, masked
-scatters for both streams, the offsets and the closing sentinels)."""
+scatters for both streams, the offsets and the closing sentinels); with a trailing `fim`, fim_device on the same ids and
+rows (fim_rate = spm_rate = 0.5, with out_src, out_seg and row_info): device ms (median of 7 after two warm-up calls) and
+GB/s by the traffic model of batch_fim.hip, beside a torch composition of the same definition on the same tensors in the
+same process (the per-row draws by the same hash in int64 arithmetic, a cumsum for the output offsets, bucketize for every
+output position's row, where for its source index and one gather); the two results must be equal, or the leg fails."""
 import os
 import subprocess
 import sys
@@ -80,8 +84,8 @@ else:
     spans, batch = args[-1] == "spans", args[-1] == "batch"
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
-    long_leg, pair, corrupt = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt"
-    mlm = corrupt or args[-1] == "mlm"  # the corrupt leg runs on the mlm leg's stream, in its place
+    long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
+    mlm = corrupt or fim or args[-1] == "mlm"  # the corrupt and fim legs run on the mlm leg's stream, in its place
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -458,7 +462,7 @@ else:
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
         legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
-        for name, whole, per_id, ref in () if corrupt else legs:
+        for name, whole, per_id, ref in () if corrupt or fim else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -525,4 +529,68 @@ else:
               (t_tgt - R + n - t_in) / 2 / n, "| ms", med, "GB/s by the traffic model", nbytes / med / 1e6, "min", ms[0], "max", ms[-1],
               "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1], "max", t[2],
               "input ids", ref[0].numel(), "target ids", ref[2].numel(), "| torch / ours", t[0] / med, flush=True)
+    if fim:
+        del starts
+        R, SEED, PRE, SUF, MID = row.numel() - 1, 1, V, V + 1, V + 2
+        s64 = lambda v: v - (1 << 64) if v >= 1 << 63 else v           # a uint64 constant as torch's int64 holds it
+        lsr = lambda x, s: (x >> s) & ((1 << (64 - s)) - 1)            # the logical shift of a uint64
+
+        def tmix(x):
+            x = x ^ lsr(x, 33)
+            x = x * s64(0xff51afd7ed558ccd)
+            x = x ^ lsr(x, 33)
+            x = x * s64(0xc4ceb9fe1a85ec53)
+            return x ^ lsr(x, 33)
+
+        def draw(h, c):
+            return lsr(tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (h + 1)) ^ c), 32)
+
+        def torch_fim():
+            """the header's definition: per-row draws by the same hash in int64 arithmetic, the output offsets by
+            a cumsum, every output position's row by bucketize, its source index by where, and one gather"""
+            L = row[1:] - row[:-1]
+            h = torch.arange(R, device="cuda")
+            on = draw(h, (1 << 40) + 4) < (1 << 31)
+            x, y = (draw(h, (1 << 40) + 5) * (L + 1)) >> 32, (draw(h, (1 << 40) + 6) * (L + 1)) >> 32
+            a, b = torch.minimum(x, y), torch.maximum(x, y)
+            mode = torch.where(on, (draw(h, (1 << 40) + 7) < (1 << 31)).long(), -1)
+            info = torch.stack([torch.where(on, a, -1), torch.where(on, b, -1), mode], dim=1)
+            out_row = row + torch.cat([row.new_zeros(1), (on.long() * 3).cumsum(0)])
+            T = int(out_row[-1].item())
+            p = torch.arange(T, device="cuda")
+            r = torch.bucketize(p, out_row, right=True) - 1
+            off, pa, pb, pm = p - out_row[r], a[r], b[r], mode[r]
+            tail = L[r] - pb
+            spm = pm == 1
+            s1 = torch.where(spm, 1, pa + 1)                # the position of suf_id, of mid_id
+            s2 = torch.where(spm, 2 + tail, pa + 2 + tail)
+            q = off - 3 - tail
+            psm = torch.where(off <= pa, off - 1, torch.where(off < s2, pb + off - pa - 2, q))
+            idx = torch.where(pm < 0, off, torch.where(spm, torch.where(off < s2, pb + off - 2, q), psm))
+            sent = (pm >= 0) & ((off == 0) | (off == s1) | (off == s2))
+            src = torch.where(sent, -1, row[r] + idx)
+            out = torch.where(sent, torch.where(off == 0, PRE, torch.where(off == s1, SUF, MID)).int(),
+                              torch.gather(ids, 0, src.clamp(min=0)))
+            mid = torch.where(spm, q >= pa, off > s2)
+            seg = torch.where(pm < 0, 0, torch.where(sent, 4, torch.where(mid, 3, torch.where(
+                torch.where(spm, off < s2, off > pa), 2, 1)))).to(torch.uint8)
+            return out, out_row, src, seg, info
+
+        run = lambda: enc.fim_device(ids, row, pre_id=PRE, suf_id=SUF, mid_id=MID, fim_rate=0.5, spm_rate=0.5, seed=SEED,
+                                     src=True, seg=True, info=True)
+        run()  # first call: allocates the FIM scratch
+        run()
+        res = [run() for _ in range(reps)]
+        ms = sorted(r[5] for r in res)
+        med = ms[len(ms) // 2]
+        t, c = events(torch_fim), events(run)
+        ref = torch_fim()
+        same = all(torch.equal(g, w) for g, w in zip(res[0][:5], ref))
+        T = res[0][0].numel()
+        nbytes = 17 * T + 130 * R + 48 * R  # batch_fim.hip's model, with out_src, out_seg and row_info
+        print("fim: ids", n, "rows", R, "output ids", T, "transformed rows", (T - n) // 3, "spm rows",
+              int((res[0][4][:, 2] == 1).sum().item()), "| ms", med, "GB/s by the traffic model", nbytes / med / 1e6,
+              "min", ms[0], "max", ms[-1], "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0],
+              "min", t[1], "max", t[2], "| equal to the torch composition", same, "| torch / ours", t[0] / med, flush=True)
+        assert same, "fim_device and the torch composition of the same definition differ"
     enc.destroy()
