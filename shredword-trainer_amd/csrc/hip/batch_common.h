@@ -1,6 +1,7 @@
-// What the batch units (batch_device.hip, batch_pair.hip) share on the device: the tile geometry of
-// their output-centric kernels, the search of a prefix sum by one wave, the kernel that writes a
-// prefix sum out as int64, and the limit of their grids.  The host side they share is batch_state.h.
+// What the batch units (batch_device.hip, batch_pair.hip, batch_mask.hip, batch_corrupt.hip,
+// batch_fim.hip) share on the device: the tile geometry of their kernels, a lane's four entries
+// loaded and stored at once, the search of a prefix sum by one wave, the kernel that writes a prefix
+// sum out as int64, and the limit of their grids.  The host side they share is batch_state.h.
 // Included by .hip files only.
 #pragma once
 
@@ -48,6 +49,31 @@ __device__ __forceinline__ u64 wave_upper_bound(const u64* __restrict__ E, u64 l
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// A lane's kLane consecutive entries of p at g, cnt of them inside the array (the others read as
+// 0 and are not written).  vec: the host found p 16-byte aligned (aligned16; tensor views are only
+// element-aligned); a full lane then takes vector accesses (V: the vector of four T), every other
+// one goes entry by entry.
+template <class V, class T>
+__device__ __forceinline__ void load4(const T* p, u64 g, int cnt, bool vec, T (&v)[kLane]) {
+  if (vec && cnt == kLane) {
+    const V w = *reinterpret_cast<const V*>(p + g);
+    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLane; ++i) v[i] = i < cnt ? p[g + i] : T(0);
+  }
+}
+
+__device__ __forceinline__ void store4(int32_t* p, u64 g, int cnt, bool vec, const int32_t (&v)[kLane]) {
+  if (vec && cnt == kLane) {
+    *reinterpret_cast<int4*>(p + g) = make_int4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLane; ++i)
+      if (i < cnt) p[g + i] = v[i];
+  }
+}
 
 // Grids are one workgroup per tile (per 256 rows: batch_rows_fit, host/encoder.h).
 static_assert(kThreads == (int)kBatchRowsPerGroup, "batch_rows_fit assumes the row kernels' workgroup");

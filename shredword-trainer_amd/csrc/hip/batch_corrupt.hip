@@ -1,20 +1,20 @@
 // Span-corruption inputs and targets on gfx950 (T5 / UL2 denoising): every noise run of a row collapses
 // to one sentinel in the input stream and follows its sentinel in the target stream (C ABI and
 // definitions: include/shredword_encode.h, shred_corrupt_*).  Both streams come out in the flat
-// (ids, row_off) format.  The passes share the batch units' tile geometry and wave search
-// (batch_common.h), their device-call driver and piece rule (batch_state.h) and the hash of the
-// dropout and masked-LM units.
+// (ids, row_off) format.  The passes share the batch units' tile geometry, 4-per-lane loads
+// and wave search (batch_common.h), their device-call driver and flat-stream host walk
+// (batch_state.h) and the seeded draw (draw_hash.h).
 //
-// A decision is a function of (seed, index, id) alone: d(x, c) = mix(mix(seed + G (x + 1)) ^ c) with
-// c = START for "a span starts at x" and c = LEN for its length, so nothing depends on the staging and
-// a piece of the host call is the device call at index_base + its first id.
+// A decision is a function of (seed, index, id) alone: draw(seed, x, c) with c = kStart for "a span
+// starts at x" and c = kLen for its length, so nothing depends on the staging and a piece of the
+// host call is the device call at index_base + its first id.
 //
 // One workgroup per kTile ids, 4 per lane, in every pass over the ids.  A workgroup finds the rows that
 // begin in its tile with two wave searches of row_off (wave_upper_bound; per tile, not per token) and
 // marks them in LDS, so no pass keeps per-id row data in global memory.
 //
-//   k_corrupt_rows     one thread per row_off entry: range, order and end points (word 0 of the result
-//                      words; ordinary stores).  The later passes write nothing when it is set.
+//   k_offsets_check    (encode_common.h) one thread per row_off entry, into word 0 of the result
+//                      words.  The later passes write nothing when it is set.
 //   k_corrupt_noise    hashes start and length of the tile's positions and of a halo of len_n positions
 //                      before it into LDS, once per position.  A lane looks back from the token before
 //                      its four (at most len_n LDS bytes, stopping at a row's first token) and then
@@ -38,7 +38,7 @@
 // k_corrupt_scatter) = 10 B.  Written: 1 (flags) + 12 per input id (in_ids, in_src; 4 without in_src)
 // + 4 per target id.  With the default options about 0.89 input and 0.20 target ids per id: about
 // 12.5 B written, 22.5 B in all.  Per tile of 1024 ids: 8 + 8 B (agg, carry) and 16 + 16 B (tot, base)
-// written and read once, and 6 wave searches of row_off.  Per row: 8 B read by k_corrupt_rows, 8 B read
+// written and read once, and 6 wave searches of row_off.  Per row: 8 B read by k_offsets_check, 8 B read
 // by each of the three passes, 16 B written (the two offsets) and 4 B for a closing sentinel.
 // All global indices are 64-bit; every global store is an ordinary vector store (the only atomics
 // count row boundaries in LDS).
@@ -54,25 +54,15 @@
 #include "../host/encoder.h"
 #include "batch_common.h"
 #include "batch_state.h"
+#include "draw_hash.h"
 #include "encode_common.h"
 
 namespace shred {
 namespace {
 
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull;
-constexpr u64 kStart = (1ull << 40) + 2, kLen = (1ull << 40) + 3;  // beside the masked-LM unit's SEL and ACT
 constexpr int kHalo = EncodeDevice::kCorruptMaxSpan;               // positions before a tile that can reach into it
 constexpr uint32_t kSeg = 1u << 31;                                // segmented sums: "a row begins here or later"
 constexpr u64 kSeg64 = 1ull << 63;
-
-__device__ __forceinline__ u64 mix64(u64 x) {  // murmur3's fmix64
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 
 // What the kernels know of a call's options; passed by value.
 struct CorruptRule {
@@ -84,16 +74,16 @@ struct CorruptRule {
   uint32_t protect_specials, protect_n;
   int32_t protect[EncodeDevice::kMaskMaxProtect];
 
-  __device__ __forceinline__ u64 draw(u64 x, u64 c) const { return mix64(mix64(seed + kGolden * (x + 1)) ^ c); }
   // L(pos) when a span starts at pos, else 0.
   __device__ __forceinline__ uint32_t span(u64 pos) const {
     const u64 h = base + pos;
-    if ((draw(h, kStart) >> 32) >= t_start) return 0;
-    const u64 v = draw(h, kLen) >> 32;
+    if ((draw(seed, h, kStart) >> 32) >= t_start) return 0;
+    const u64 v = draw(seed, h, kLen) >> 32;
     uint32_t L = 1;
     for (uint32_t i = 0; i + 1 < len_n; ++i) L += v >= cum[i];
     return L;
   }
+  // never noise
   __device__ __forceinline__ bool guarded(int32_t id) const {
     bool hit = protect_specials && id >= sp_lo && id < sp_hi;
     for (uint32_t i = 0; i < protect_n; ++i) hit |= protect[i] == id;
@@ -175,26 +165,6 @@ __device__ __forceinline__ void tile_rows(const u64* __restrict__ row, u64 R, u6
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kThreads) void k_corrupt_rows(const int64_t* __restrict__ row, u64 rows, u64 n,
-                                                           u64* __restrict__ res) {
-  const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
-  if (r > rows) return;
-  const int64_t v = row[r];
-  const int64_t prev = r ? row[r - 1] : 0;
-  if (v < 0 || (u64)v > n || prev > v || (r == 0 && v != 0) || (r == rows && (u64)v != n)) res[0] = 1;
-}
-
-// Four consecutive ids at g (cnt of them inside the array).
-__device__ __forceinline__ void load_ids(const int32_t* p, u64 g, int cnt, bool vec, int32_t (&v)[kLane]) {
-  if (vec && cnt == kLane) {
-    const int4 w = *reinterpret_cast<const int4*>(p + g);
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < kLane; ++i) v[i] = i < cnt ? p[g + i] : 0;
-  }
-}
-
 // flags: n rounded up to kLane bytes allocated; vec: ids may take 16-byte loads.
 __global__ __launch_bounds__(kThreads) void k_corrupt_noise(const int32_t* __restrict__ ids, u64 n,
                                                             const u64* __restrict__ row, u64 R, CorruptRule rule,
@@ -226,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void k_corrupt_noise(const int32_t* __res
   if (g < cnt) {
     const int c = cnt - g < kLane ? cnt - g : kLane;
     int32_t id[kLane];
-    load_ids(ids, tile0 + g, c, vec != 0, id);
+    load4<int4>(ids, tile0 + g, c, vec != 0, id);
     int reach = 0;      // furthest LDS index (exclusive) that a start of this row, seen so far, covers
     bool prev = false;  // the token before is noise
     if (tile0 + g > 0) {
@@ -373,7 +343,7 @@ __global__ __launch_bounds__(kThreads) void k_corrupt_scatter(
   uint32_t li = ex & 0xFFFFu, lt = ex >> 16;
   if (l.c) {
     int32_t id[kLane];
-    load_ids(ids, tile0 + g, l.c, vec != 0, id);
+    load4<int4>(ids, tile0 + g, l.c, vec != 0, id);
     for (int t = 0; t < l.c; ++t) {
       rows_to += s_nb[g + t];
       s_in[g + t] = li, s_tg[g + t] = lt;
@@ -427,9 +397,9 @@ struct CorruptCall {
 // and the tiles' words grown to the most ids seen, and the staging of the host path.
 struct CorruptState : PassState {
   DeviceWords res;            // [0] a bad row_off, [1] T_in, [2] T_tgt
-  PinnedWords host;           // the three; [3], [4]: the offsets {0, n} of a call without row_off
+  PinnedWords host;           // the three
   EventSet<4> ev;
-  DeviceBuf<int64_t> one;     // those offsets on the device
+  OneRow one;                 // a call without row_off
   DeviceBuf<uint8_t> flags;   // 1 B per id
   DeviceBuf<u64> agg;         // per tile: the aggregate, then the scanned carry
   DeviceBuf<Pair> tot;        // per tile: the emit counts, then their inclusive sums
@@ -437,7 +407,7 @@ struct CorruptState : PassState {
   DeviceBuf<int32_t> hids, hin, htgt;  // host path: a piece's ids and its two streams
   DeviceBuf<int64_t> hsrc, hrow;       // in_src; the piece's row_off, in_row_off and tgt_row_off (3 x hrow.cap())
 
-  bool reserve(size_t) { return res.ensure(3) && host.ensure(5) && ev.ensure() && one.grow(2); }
+  bool reserve(size_t) { return res.ensure(3) && host.ensure(3) && ev.ensure() && one.ensure(); }
 
   static u64 tiles_of(u64 n) { return (n + kTile - 1) / kTile; }
 
@@ -453,22 +423,11 @@ struct CorruptState : PassState {
     return tmp.grow(std::max<size_t>(std::max(a, b), 16));
   }
 
-  // Without a row_off: one row of all ids.
-  int one_row(u64 n, hipStream_t st) {
-    host[3] = 0, host[4] = n;
-    ENC_OK(hipMemcpyAsync(one.get(), host.get() + 3, 16, hipMemcpyHostToDevice, st));
-    return 0;
-  }
-
   // The passes up to the counts, which are in `host` when it returns: 0 or -1.  check: row is the
   // caller's and has not been validated.
   int measure(const CorruptCall& c, bool check, hipStream_t st) {
     ENC_OK(hipMemsetAsync(res.get(), 0, 24, st));
-    if (check) {
-      k_corrupt_rows<<<dim3((unsigned)((c.R + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(c.row, c.R, c.n,
-                                                                                                  res.get());
-      ENC_OK(hipGetLastError());
-    }
+    if (check && check_offsets(c.row, c.R, c.n, res.get(), st) < 0) return -1;
     const u64 tiles = tiles_of(c.n);
     u64* const carry = agg.get() + agg.cap();
     Pair* const base = tot.get() + tot.cap();
@@ -504,10 +463,14 @@ struct CorruptState : PassState {
     return 0;
   }
 
-  // Staging of a piece of len ids and m rows.
-  bool stage(size_t len, size_t m, bool src) {
-    return reserve_ids(len) && hids.grow(std::max<size_t>(len, 1)) && hin.grow(std::max<size_t>(len, 1)) &&
-           htgt.grow(2 * len + m) && (!src || hsrc.grow(std::max<size_t>(len, 1))) && hrow.grow(m + 1, 3);
+  // Staging of a piece (false: it cannot be staged).
+  bool stage(FlatPiece* p, bool src) {
+    const size_t len = p->len, m = p->m, ids = std::max<size_t>(len, 1);
+    if (!tiles_fit(len) || !reserve_ids(len) || !hids.grow(ids) || !hin.grow(ids) || !htgt.grow(2 * len + m) ||
+        (src && !hsrc.grow(ids)) || !hrow.grow(m + 1, 3))
+      return false;
+    p->ids = hids.get(), p->row = hrow.get();
+    return true;
   }
 };
 
@@ -527,10 +490,7 @@ int64_t EncodeDevice::corrupt(const int32_t* ids, size_t n, const int64_t* row_o
           std::fprintf(stderr, "[ERROR]\t encoder: corrupt allocation failed (%zu ids)\n", n);
           return -1;
         }
-        if (!row_off) {
-          if (cs.one_row(n, st) < 0) return -1;
-          c.row = cs.one.get();
-        }
+        if (!row_off && cs.one.put(n, st, &c.row) < 0) return -1;
         if (cs.measure(c, row_off != nullptr, st) < 0) return -1;
         if (cs.host[0]) return -6;
         if (tgt_n) *tgt_n = (size_t)cs.host[2];
@@ -540,11 +500,11 @@ int64_t EncodeDevice::corrupt(const int32_t* ids, size_t n, const int64_t* row_o
       [&](CorruptState& cs, hipStream_t st) { return cs.scatter(c, st); });
 }
 
-// Host ids in pieces of whole rows (piece_end).  A piece is the device passes on its own ids at
+// Host ids in pieces of whole rows (flat_pieces).  A piece is the device passes on its own ids at
 // index_base + the index of its first id; its two streams land in the piece's staging at 0 and are
 // copied behind the earlier pieces', and its offsets and in_src are written with the piece's bases
-// added.  The caller has validated row_off.  Caps that hold the bound (n and 2 n + rows) need one
-// round; smaller ones a round of counts first, so that nothing is written when they do not suffice.
+// added.  The caller has validated row_off.  The bound of the two streams is n and 2 n + rows
+// (count_then_write).
 int64_t EncodeDevice::corrupt_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
                                    const CorruptOpts& o, int32_t* in_ids, size_t in_cap, int64_t* in_row_off,
                                    int64_t* in_src, int32_t* tgt_ids, size_t tgt_cap, int64_t* tgt_row_off,
@@ -557,52 +517,34 @@ int64_t EncodeDevice::corrupt_host(const int32_t* ids, size_t n, const int64_t* 
     return -1;
   }
   hipStream_t st = (hipStream_t)stream_;
-  const size_t R = row_off ? rows : 1, piece = piece_ids();
-  const HostIn in{ids, n, row_off};
-  std::vector<int64_t> local;
-  u64 t_in = 0, t_tgt = 0;
-  const auto round = [&](bool write) -> int {
-    t_in = t_tgt = 0;
-    for (size_t r0 = 0; r0 < R;) {
-      u64 emitted = 0;
-      const size_t r1 = piece_end(&in, 1, R, r0, piece, 0, [](size_t) { return (u64)0; }, &emitted, nullptr);
-      const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a, m = r1 - r0;
-      if (!tiles_fit(len) || !cs.stage(len, m, write && in_src)) {
-        std::fprintf(stderr, "[ERROR]\t encoder: corrupt staging allocation failed (%zu ids, %zu rows)\n", len, m);
-        return -1;
-      }
-      int64_t *const drow = cs.hrow.get(), *const din_row = drow + cs.hrow.cap(), *const dtgt_row = din_row + cs.hrow.cap();
-      if (len) ENC_OK(hipMemcpyAsync(cs.hids.get(), ids + a, len * 4, hipMemcpyHostToDevice, st));
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off ? row_off[r0 + i] - (int64_t)a : (int64_t)(i ? n : 0);
-      ENC_OK(hipMemcpyAsync(drow, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-      const CorruptCall c{cs.hids.get(), len, drow, m, rule_of(o, a), a, t_in, t_tgt, cs.hin.get(),
-                          write && in_src ? cs.hsrc.get() : nullptr, cs.htgt.get(), din_row, dtgt_row};
-      if (cs.measure(c, false, st) < 0) return -1;
-      const u64 p_in = cs.host[1], p_tgt = cs.host[2];
-      if (write) {
-        if (cs.scatter(c, st) < 0) return -1;
-        if (p_in) ENC_OK(hipMemcpyAsync(in_ids + t_in, cs.hin.get(), p_in * 4, hipMemcpyDeviceToHost, st));
-        if (p_in && in_src) ENC_OK(hipMemcpyAsync(in_src + t_in, cs.hsrc.get(), p_in * 8, hipMemcpyDeviceToHost, st));
-        if (p_tgt) ENC_OK(hipMemcpyAsync(tgt_ids + t_tgt, cs.htgt.get(), p_tgt * 4, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipMemcpyAsync(in_row_off + r0, din_row, (m + 1) * 8, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipMemcpyAsync(tgt_row_off + r0, dtgt_row, (m + 1) * 8, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipStreamSynchronize(st));
-      }
-      t_in += p_in, t_tgt += p_tgt;
-      r0 = r1;
-    }
-    return 0;
+  const size_t R = row_off ? rows : 1;
+  const FlatCall fc{"corrupt", HostIn{ids, n, row_off}, R, 2, false};
+  u64 total[2] = {0, 0};  // T_in, T_tgt of the pieces so far
+  const auto round = [&](bool write) {
+    const bool src = write && in_src;
+    return flat_pieces(
+        st, fc, total,
+        [&](FlatPiece* p) { return cs.stage(p, src); },
+        [&](const FlatPiece& p, FlatOuts* outs) {
+          int64_t *const din_row = cs.hrow.get() + cs.hrow.cap(), *const dtgt_row = din_row + cs.hrow.cap();
+          const CorruptCall c{p.ids,        p.len,    p.row, p.m, rule_of(o, p.a), p.a, total[0], total[1],
+                              cs.hin.get(), src ? cs.hsrc.get() : nullptr, cs.htgt.get(), din_row, dtgt_row};
+          if (cs.measure(c, false, st) < 0) return -1;
+          outs->count = &cs.host[1];
+          if (!write) return 0;
+          if (cs.scatter(c, st) < 0) return -1;
+          outs->add(in_ids + total[0], cs.hin.get(), cs.host[1] * 4);
+          outs->add(src ? in_src + total[0] : nullptr, cs.hsrc.get(), cs.host[1] * 8);
+          outs->add(tgt_ids + total[1], cs.htgt.get(), cs.host[2] * 4);
+          outs->add(in_row_off + p.r0, din_row, (p.m + 1) * 8);
+          outs->add(tgt_row_off + p.r0, dtgt_row, (p.m + 1) * 8);
+          return 0;
+        });
   };
-  const bool write = in_ids && tgt_ids;
-  if (!(write && in_cap >= n && tgt_cap >= 2 * (u64)n + R)) {
-    if (round(false) < 0) return -1;
-    if (tgt_n) *tgt_n = (size_t)t_tgt;
-    if (!write || in_cap < t_in || tgt_cap < t_tgt) return (int64_t)t_in;
-  }
-  if (round(true) < 0) return -1;
-  if (tgt_n) *tgt_n = (size_t)t_tgt;
-  return (int64_t)t_in;
+  const u64 cap[2] = {in_cap, tgt_cap}, bound[2] = {n, 2 * (u64)n + R};
+  if (count_then_write(in_ids && tgt_ids, 2, cap, bound, total, round) < 0) return -1;
+  if (tgt_n) *tgt_n = (size_t)total[1];
+  return (int64_t)total[0];
 }
 
 }  // namespace shred

@@ -131,14 +131,12 @@ Rows rows_of(const EncodeDevice::BatchOpts& o, const int64_t* row, u64 n) {
 __global__ __launch_bounds__(kThreads) void k_bat_rows(Rows rw, u64 rows, int ends, u64* __restrict__ err) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r > rows) return;
-  const int64_t v = rw.row[r];
-  const int64_t prev = r ? rw.row[r - 1] : 0;
-  bool bad = v < 0 || (u64)v > rw.n || prev > v;
-  if (ends && ((r == 0 && v != 0) || (r == rows && (u64)v != rw.n))) bad = true;
-  if (bad) {
+  if (offset_bad(rw.row, r, rows, rw.n, ends != 0)) {
     err[0] = 1;
     return;
   }
+  const int64_t v = rw.row[r];
+  const int64_t prev = r ? rw.row[r - 1] : 0;
   if (r && prev >= 0 && (u64)(rw.bos_n + rw.eos_n) + rw.keep((u64)prev, (u64)v) > (u64)INT32_MAX) err[1] = 1;
 }
 

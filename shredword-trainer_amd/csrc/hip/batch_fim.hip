@@ -2,17 +2,16 @@
 // prefix, middle and suffix and re-emitted as pre prefix suf suffix mid middle (PSM) or pre suf suffix
 // mid prefix middle (SPM) (C ABI and definitions: include/shredword_encode.h, shred_fim_*).  The stream
 // comes out in the flat (ids, row_off) format.  The passes share the batch units' tile geometry and
-// wave search (batch_common.h), their device-call driver and piece rule (batch_state.h) and the hash of
-// the dropout, masked-LM and span-corruption units.
+// wave search (batch_common.h), their device-call driver and flat-stream host walk (batch_state.h)
+// and the seeded draw (draw_hash.h).
 //
-// A decision is a function of (seed, row index) alone: d(x, c) = mix(mix(seed + G (x + 1)) ^ c) with
-// c = FIM for "the row is transformed", CUT_A and CUT_B for the two cuts and MODE for the order, so
-// nothing depends on the staging and a piece of the host call is the device call at row_base + its
-// first row.
+// A decision is a function of (seed, row index) alone: draw(seed, x, c) with c = kFimC for "the row
+// is transformed", kCutA and kCutB for the two cuts and kMode for the order, so nothing depends on
+// the staging and a piece of the host call is the device call at row_base + its first row.
 //
-//   k_fim_rows     one thread per row_off entry: range, order and end points (word 0 of the result
-//                  words; ordinary stores), then the row's draws, or its triple of `cuts` checked (word
-//                  1).  (a, b, mode) go to the info scratch, the row's output length to the scan's input.
+//   k_fim_rows     one thread per row_off entry: offset_bad (encode_common.h) into word 0 of the
+//                  result words, then the row's draws, or its triple of `cuts` checked (word 1).
+//                  (a, b, mode) go to the info scratch, the row's output length to the scan's input.
 //   hipCUB scan    exclusive sum of the output lengths: O[r], the row's offset in the output stream;
 //                  O[rows] = T_out.
 //   k_fim_result   T_out beside words 0 and 1: one copy of three result words to the host, which
@@ -29,8 +28,8 @@
 //                  out_ids and out_src and 4-byte stores of out_seg where the buffers are aligned.
 //   k_fim_cuts     character-level cuts (shred_fim_cuts_device): one thread per document draws on the
 //                  document's bytes, snaps both cuts back to a UTF-8 character's first byte (at most 3
-//                  bytes read per cut) and writes the three piece offsets and the mode.  k_fim_docs
-//                  checks doc_off before it, as k_docs_check does.
+//                  bytes read per cut) and writes the three piece offsets and the mode.
+//                  k_offsets_check (encode_common.h) checks doc_off before it.
 //
 // Traffic per id: 4 B read (ids, k_fim_gather) and 4 B written (out_ids); 8 B more with out_src and 1 B
 // more with out_seg.  Per row: 16 B read by k_fim_rows (24 B more with cuts), 24 B (info) and 8 B (the
@@ -50,23 +49,11 @@
 #include "../host/encoder.h"
 #include "batch_common.h"
 #include "batch_state.h"
+#include "draw_hash.h"
 #include "encode_common.h"
 
 namespace shred {
 namespace {
-
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull;
-// beside the span-corruption unit's START and LEN
-constexpr u64 kFimC = (1ull << 40) + 4, kCutA = (1ull << 40) + 5, kCutB = (1ull << 40) + 6, kMode = (1ull << 40) + 7;
-
-__device__ __forceinline__ u64 mix64(u64 x) {  // murmur3's fmix64
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 
 // What the kernels know of a call's options; passed by value.
 struct FimRule {
@@ -75,15 +62,15 @@ struct FimRule {
   int64_t min_len;
   int32_t sent[3];  // pre_id, suf_id, mid_id
 
-  __device__ __forceinline__ u64 draw(u64 x, u64 c) const { return mix64(mix64(seed + kGolden * (x + 1)) ^ c); }
   // The decisions of row (or document) r of L ids (bytes): -1 not transformed, else the mode, with the cuts.
   __device__ __forceinline__ int64_t decide(u64 r, u64 L, u64* a, u64* b) const {
     const u64 h = base + r;
     *a = *b = 0;
-    if ((int64_t)L < min_len || (draw(h, kFimC) >> 32) >= t_fim) return -1;
-    const u64 x = ((draw(h, kCutA) >> 32) * (L + 1)) >> 32, y = ((draw(h, kCutB) >> 32) * (L + 1)) >> 32;
+    if ((int64_t)L < min_len || (draw(seed, h, kFimC) >> 32) >= t_fim) return -1;
+    const u64 x = ((draw(seed, h, kCutA) >> 32) * (L + 1)) >> 32,
+              y = ((draw(seed, h, kCutB) >> 32) * (L + 1)) >> 32;
     *a = x < y ? x : y, *b = x < y ? y : x;
-    return (draw(h, kMode) >> 32) < t_spm ? 1 : 0;
+    return (draw(seed, h, kMode) >> 32) < t_spm ? 1 : 0;
   }
 };
 
@@ -97,14 +84,12 @@ __global__ __launch_bounds__(kThreads) void k_fim_rows(const int64_t* __restrict
                                                        u64* __restrict__ len, u64* __restrict__ res) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r > rows) return;
-  const int64_t v = row[r];
-  const int64_t prev = r ? row[r - 1] : 0;
-  if (v < 0 || (u64)v > n || prev > v || (r == 0 && v != 0) || (r == rows && (u64)v != n)) res[0] = 1;
+  if (offset_bad(row, r, rows, n, true)) res[0] = 1;
   if (r == rows) {
     len[r] = 0;
     return;
   }
-  const int64_t Ls = row[r + 1] - v;
+  const int64_t Ls = row[r + 1] - row[r];
   const u64 L = Ls > 0 ? (u64)Ls : 0;  // a bad row_off: word 0 is set by this row's or the next one's thread
   u64 a = 0, b = 0;
   int64_t mode;
@@ -256,6 +241,8 @@ __global__ __launch_bounds__(kThreads) void k_fim_gather(const int32_t* __restri
   }
   if (p0 >= tlen) return;
   const u64 g = t0 + (u64)p0;
+  // (open-coded, not batch_common.h's store4: with the helper the kernel measured 5% slower at the
+  // same register counts, profiles/f5_shared_units_enc_bench.txt)
   const bool full = p0 + kLane <= tlen;
   if (full && (aligned & 1u)) {
     *reinterpret_cast<int4*>(out + g) = make_int4(w[0], w[1], w[2], w[3]);
@@ -286,16 +273,6 @@ __global__ __launch_bounds__(kThreads) void k_fim_gather(const int32_t* __restri
 }
 
 // ---- character-level cuts ----
-
-__global__ __launch_bounds__(kThreads) void k_fim_docs(const int64_t* __restrict__ doc_off, u64 docs, u64 n,
-                                                       u64* __restrict__ res) {
-  const u64 i = (u64)blockIdx.x * kThreads + threadIdx.x;
-  if (i > docs) return;
-  const int64_t v = doc_off[i];
-  bool bad = v < 0 || (u64)v > n || (i == 0 && v != 0) || (i == docs && (u64)v != n);
-  if (!bad && i < docs) bad = v > doc_off[i + 1];
-  if (bad) res[0] = 1;  // several threads may store at once, on purpose: all store the same value
-}
 
 // R >= 1 documents whose doc_off is good (nullptr: one document of n bytes).
 __global__ __launch_bounds__(kThreads) void k_fim_cuts(const uint8_t* __restrict__ text, u64 n,
@@ -346,9 +323,9 @@ struct FimCall {
 // largest call (info, the output lengths and their scan), and the staging of the host path.
 struct FimState : PassState {
   DeviceWords res;         // [0] a bad row_off / doc_off, [1] a bad cuts, [2] T_out
-  PinnedWords host;        // the three; [3], [4]: the offsets {0, n} of a call without row_off
+  PinnedWords host;        // the three
   EventSet<4> ev;
-  DeviceBuf<int64_t> one;  // those offsets on the device
+  OneRow one;              // a call without row_off
   DeviceBuf<int64_t> info; // 3 per row
   DeviceBuf<u64> len;      // rows + 1 output lengths, then their exclusive sum O
   DeviceBuf<uint8_t> tmp;  // hipCUB scan scratch
@@ -356,7 +333,7 @@ struct FimState : PassState {
   DeviceBuf<int64_t> hsrc, hrow, hcuts; // out_src; the piece's row_off and out_row_off (2 x hrow.cap()); its cuts
   DeviceBuf<uint8_t> hseg;
 
-  bool words() { return res.ensure(3) && host.ensure(5) && ev.ensure() && one.grow(2); }
+  bool words() { return res.ensure(3) && host.ensure(3) && ev.ensure() && one.ensure(); }
 
   bool reserve(size_t rows) {
     if (!words() || !info.grow(3 * std::max<size_t>(rows, 1)) || !len.grow(rows + 1, 2)) return false;
@@ -367,13 +344,6 @@ struct FimState : PassState {
   }
 
   u64* O() const { return len.get() + len.cap(); }
-
-  // Without a row_off: one row of all ids.
-  int one_row(u64 n, hipStream_t st) {
-    host[3] = 0, host[4] = n;
-    ENC_OK(hipMemcpyAsync(one.get(), host.get() + 3, 16, hipMemcpyHostToDevice, st));
-    return 0;
-  }
 
   // The passes up to the result words, which are in `host` when it returns: 0 or -1.
   int measure(const FimCall& c, hipStream_t st) {
@@ -405,10 +375,13 @@ struct FimState : PassState {
   }
 
   // Staging of a piece of n ids and m rows.
-  bool stage(size_t n, size_t m, bool cuts, bool src, bool seg) {
-    const size_t cap = n + 3 * m;
-    return reserve(m) && hids.grow(std::max<size_t>(n, 1)) && hout.grow(cap) && hrow.grow(m + 1, 2) &&
-           (!cuts || hcuts.grow(3 * m)) && (!src || hsrc.grow(cap)) && (!seg || hseg.grow(cap));
+  bool stage(FlatPiece* p, bool cuts, bool src, bool seg) {
+    const size_t n = p->len, m = p->m, cap = n + 3 * m;
+    if (!tiles_fit(cap) || !reserve(m) || !hids.grow(std::max<size_t>(n, 1)) || !hout.grow(cap) || !hrow.grow(m + 1, 2) ||
+        (cuts && !hcuts.grow(3 * m)) || (src && !hsrc.grow(cap)) || (seg && !hseg.grow(cap)))
+      return false;
+    p->ids = hids.get(), p->row = hrow.get();
+    return true;
   }
 };
 
@@ -425,10 +398,7 @@ int64_t EncodeDevice::fim(const int32_t* ids, size_t n, const int64_t* row_off, 
   return device_call<FimState>(
       pass_[kFim], device_, stream ? stream : stream_, "fim", R, kernel_ms,
       [&](FimState& fs, hipStream_t st, Plan* p) {
-        if (!row_off) {
-          if (fs.one_row(n, st) < 0) return -1;
-          c.row = fs.one.get();
-        }
+        if (!row_off && fs.one.put(n, st, &c.row) < 0) return -1;
         if (fs.measure(c, st) < 0) return -1;
         if (fs.host[0]) return -6;
         if (fs.host[1]) return -8;
@@ -439,12 +409,11 @@ int64_t EncodeDevice::fim(const int32_t* ids, size_t n, const int64_t* row_off, 
       [&](FimState& fs, hipStream_t st) { return fs.expand(c, T, st); });
 }
 
-// Host rows in pieces of whole rows (piece_end).  A piece is the device passes on its own rows at
+// Host rows in pieces of whole rows (flat_pieces).  A piece is the device passes on its own rows at
 // row_base + its first row, with its slice of cuts; its stream lands in the piece's staging at 0 and
 // is copied behind the earlier pieces', and its offsets and out_src are written with the piece's
-// bases added.  The caller has validated row_off and cuts.  A cap that holds the bound (n + 3 rows)
-// needs one round; a smaller one a round of counts first, so that nothing is written when it does
-// not suffice.
+// bases added.  The caller has validated row_off and cuts.  The bound of the stream is n + 3 rows
+// (count_then_write).
 int64_t EncodeDevice::fim_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const FimOpts& o,
                                const int64_t* cuts, int32_t* out_ids, size_t out_cap, int64_t* out_row_off,
                                int64_t* out_src, uint8_t* out_seg, int64_t* row_info) {
@@ -456,50 +425,34 @@ int64_t EncodeDevice::fim_host(const int32_t* ids, size_t n, const int64_t* row_
     return -1;
   }
   hipStream_t st = (hipStream_t)stream_;
-  const size_t R = row_off ? rows : 1, piece = piece_ids();
-  const HostIn in{ids, n, row_off};
-  std::vector<int64_t> local;
-  u64 total = 0;
-  const auto round = [&](bool write) -> int {
-    total = 0;
-    for (size_t r0 = 0; r0 < R;) {
-      u64 emitted = 0;
-      const size_t r1 = piece_end(&in, 1, R, r0, piece, 0, [](size_t) { return (u64)0; }, &emitted, nullptr);
-      const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a, m = r1 - r0;
-      if (!tiles_fit(len + 3 * m) || !fs.stage(len, m, cuts != nullptr, write && out_src, write && out_seg)) {
-        std::fprintf(stderr, "[ERROR]\t encoder: fim staging allocation failed (%zu ids, %zu rows)\n", len, m);
-        return -1;
-      }
-      int64_t *const drow = fs.hrow.get(), *const dout_row = drow + fs.hrow.cap();
-      if (len) ENC_OK(hipMemcpyAsync(fs.hids.get(), ids + a, len * 4, hipMemcpyHostToDevice, st));
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off ? row_off[r0 + i] - (int64_t)a : (int64_t)(i ? n : 0);
-      ENC_OK(hipMemcpyAsync(drow, local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-      if (cuts) ENC_OK(hipMemcpyAsync(fs.hcuts.get(), cuts + 3 * r0, m * 24, hipMemcpyHostToDevice, st));
-      const FimCall c{fs.hids.get(), len, drow, m, cuts ? fs.hcuts.get() : nullptr, rule_of(o, r0), a, total,
-                      fs.hout.get(), dout_row, write && out_src ? fs.hsrc.get() : nullptr,
-                      write && out_seg ? fs.hseg.get() : nullptr, nullptr};
-      if (fs.measure(c, st) < 0) return -1;
-      const u64 T = fs.host[2];
-      if (write) {
-        if (fs.expand(c, T, st) < 0) return -1;
-        if (T) ENC_OK(hipMemcpyAsync(out_ids + total, fs.hout.get(), T * 4, hipMemcpyDeviceToHost, st));
-        if (T && out_src) ENC_OK(hipMemcpyAsync(out_src + total, fs.hsrc.get(), T * 8, hipMemcpyDeviceToHost, st));
-        if (T && out_seg) ENC_OK(hipMemcpyAsync(out_seg + total, fs.hseg.get(), T, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipMemcpyAsync(out_row_off + r0, dout_row, (m + 1) * 8, hipMemcpyDeviceToHost, st));
-        if (row_info) ENC_OK(hipMemcpyAsync(row_info + 3 * r0, fs.info.get(), m * 24, hipMemcpyDeviceToHost, st));
-        ENC_OK(hipStreamSynchronize(st));
-      }
-      total += T;
-      r0 = r1;
-    }
-    return 0;
+  const size_t R = row_off ? rows : 1;
+  const FlatCall fc{"fim", HostIn{ids, n, row_off}, R, 1, false};
+  u64 total = 0;  // T_out of the pieces so far
+  const auto round = [&](bool write) {
+    const bool src = write && out_src, seg = write && out_seg;
+    return flat_pieces(
+        st, fc, &total,
+        [&](FlatPiece* p) { return fs.stage(p, cuts != nullptr, src, seg); },
+        [&](const FlatPiece& p, FlatOuts* outs) {
+          int64_t* const dout_row = fs.hrow.get() + fs.hrow.cap();
+          if (cuts) ENC_OK(hipMemcpyAsync(fs.hcuts.get(), cuts + 3 * p.r0, p.m * 24, hipMemcpyHostToDevice, st));
+          const FimCall c{p.ids, p.len, p.row, p.m, cuts ? fs.hcuts.get() : nullptr, rule_of(o, p.r0), p.a, total,
+                          fs.hout.get(), dout_row, src ? fs.hsrc.get() : nullptr, seg ? fs.hseg.get() : nullptr, nullptr};
+          if (fs.measure(c, st) < 0) return -1;
+          outs->count = &fs.host[2];
+          if (!write) return 0;
+          const u64 T = fs.host[2];
+          if (fs.expand(c, T, st) < 0) return -1;
+          outs->add(out_ids + total, fs.hout.get(), T * 4);
+          outs->add(src ? out_src + total : nullptr, fs.hsrc.get(), T * 8);
+          outs->add(seg ? out_seg + total : nullptr, fs.hseg.get(), T);
+          outs->add(out_row_off + p.r0, dout_row, (p.m + 1) * 8);
+          outs->add(row_info ? row_info + 3 * p.r0 : nullptr, fs.info.get(), p.m * 24);
+          return 0;
+        });
   };
-  if (!(out_ids && out_cap >= n + 3 * (u64)R)) {
-    if (round(false) < 0) return -1;
-    if (!out_ids || out_cap < total) return (int64_t)total;
-  }
-  if (round(true) < 0) return -1;
+  const u64 cap = out_cap, bound = n + 3 * (u64)R;
+  if (count_then_write(out_ids != nullptr, 1, &cap, &bound, &total, round) < 0) return -1;
   return (int64_t)total;
 }
 
@@ -520,8 +473,7 @@ int EncodeDevice::fim_cuts(const uint8_t* text, size_t n, const int64_t* doc_off
   ENC_OK(hipEventRecord(fs.ev[0], st));
   if (doc_off) {
     ENC_OK(hipMemsetAsync(fs.res.get(), 0, 8, st));
-    k_fim_docs<<<grid, dim3(kThreads), 0, st>>>(doc_off, R, n, fs.res.get());
-    ENC_OK(hipGetLastError());
+    if (check_offsets(doc_off, R, n, fs.res.get(), st) < 0) return -1;
     ENC_OK(hipMemcpyAsync(fs.host.get(), fs.res.get(), 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipStreamSynchronize(st));
     if (fs.host[0]) return -6;

@@ -1,16 +1,17 @@
 // Masked-LM inputs on gfx950: tokens selected per token or per whole word, replaced by a mask id, a
 // random id or themselves, with the labels beside them (C ABI and definitions:
 // include/shredword_encode.h, shred_mlm_*).  The passes work on the flat (ids, row_off) pair and use
-// none of the other units' kernels; they share the batch units' tile geometry (batch_common.h), their
-// device-call driver and piece rule (batch_state.h) and the span passes' token-length table.
+// none of the other units' kernels; they share the batch units' tile geometry and 4-per-lane accesses
+// (batch_common.h), their device-call driver and flat-stream host walk (batch_state.h),
+// the seeded draw (draw_hash.h) and the span passes' token-length table.
 //
-// A decision is a function of (seed, index, id) alone: d(x, c) = mix(mix(seed + G (x + 1)) ^ c) with
-// c = SEL for the selection of unit x and c = ACT for the action of token x, so nothing depends on
-// the staging and a piece of the host call is the device call at index_base + its first id.
+// A decision is a function of (seed, index, id) alone: draw(seed, x, c) with c = kSel for the
+// selection of unit x and c = kAct for the action of token x, so nothing depends on the staging and
+// a piece of the host call is the device call at index_base + its first id.
 //
-//   k_mlm_rows     one thread per row_off entry: range, order and end points (word 0 of the result
-//                  words; ordinary stores, no atomics).  Whole-word mode: it also marks the first
-//                  token of every row in the begin bytes (cleared before it);
+//   k_mlm_rows     one thread per row_off entry: offset_bad (encode_common.h) into word 0 of the
+//                  result words.  Whole-word mode: it also marks the first token of every row in
+//                  the begin bytes (cleared before it);
 //   k_mlm_begin    whole-word mode, one workgroup per kTile ids, 4 per lane: begin[k] = 1 iff token k
 //                  begins a word (the header's rule: k == 0, a row's first token, a special or a
 //                  protected id on either side, or a gap between the end of token k - 1 and starts[k]);
@@ -45,22 +46,11 @@
 #include "../host/encoder.h"
 #include "batch_common.h"
 #include "batch_state.h"
+#include "draw_hash.h"
 #include "encode_common.h"
 
 namespace shred {
 namespace {
-
-constexpr u64 kGolden = 0x9E3779B97F4A7C15ull;
-constexpr u64 kSel = 1ull << 40, kAct = (1ull << 40) + 1;  // above every merge rank (dropout's third input)
-
-__device__ __forceinline__ u64 mix64(u64 x) {  // murmur3's fmix64
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
 
 // What the kernels know of a call's options; passed by value, so the protect list is read from the
 // kernel arguments.
@@ -71,7 +61,6 @@ struct MaskRule {
   uint32_t protect_specials, protect_n;
   int32_t protect[EncodeDevice::kMaskMaxProtect];
 
-  __device__ __forceinline__ u64 draw(u64 x, u64 c) const { return mix64(mix64(seed + kGolden * (x + 1)) ^ c); }
   __device__ __forceinline__ bool special(int32_t id) const { return id >= sp_lo && id < sp_hi; }
   __device__ __forceinline__ bool listed(int32_t id) const {
     bool hit = false;
@@ -95,37 +84,12 @@ __global__ __launch_bounds__(kThreads) void k_mlm_rows(const int64_t* __restrict
                                                        uint8_t* __restrict__ begin, u64* __restrict__ res) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r > rows) return;
-  const int64_t v = row[r];
-  const int64_t prev = r ? row[r - 1] : 0;
-  bool bad = v < 0 || (u64)v > n || prev > v;
-  if (ends && ((r == 0 && v != 0) || (r == rows && (u64)v != n))) bad = true;
-  if (bad) {
+  if (offset_bad(row, r, rows, n, ends != 0)) {
     res[0] = 1;
     return;
   }
+  const int64_t v = row[r];
   if (begin && r < rows && (u64)v < n) begin[v] = 1;
-}
-
-// Four consecutive entries of p at g (cnt of them inside the array).
-template <class V, class T>
-__device__ __forceinline__ void load4(const T* p, u64 g, int cnt, bool vec, T (&v)[kLane]) {
-  if (vec && cnt == kLane) {
-    const V w = *reinterpret_cast<const V*>(p + g);
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < kLane; ++i) v[i] = i < cnt ? p[g + i] : T(0);
-  }
-}
-
-__device__ __forceinline__ void store4(int32_t* p, u64 g, int cnt, bool vec, const int32_t (&v)[kLane]) {
-  if (vec && cnt == kLane) {
-    *reinterpret_cast<int4*>(p + g) = make_int4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < kLane; ++i)
-      if (i < cnt) p[g + i] = v[i];
-  }
 }
 
 // begin: the rows' first tokens marked, n rounded up to kLane bytes allocated; aligned: bit 0 ids,
@@ -195,10 +159,10 @@ __global__ __launch_bounds__(kThreads) void k_mlm_apply(const int32_t* ids, u64 
     for (int i = 0; i < kLane; ++i) {
       o[i] = id[i];
       lab[i] = rule.ignore_id;
-      if (i < cnt && !rule.guarded(id[i]) && (rule.draw(rule.base + h[i], kSel) >> 32) < rule.t_sel) {
+      if (i < cnt && !rule.guarded(id[i]) && (draw(rule.seed, rule.base + h[i], kSel) >> 32) < rule.t_sel) {
         ++selected;
         lab[i] = id[i];
-        const u64 a = rule.draw(rule.base + g + (u64)i, kAct);
+        const u64 a = draw(rule.seed, rule.base + g + (u64)i, kAct);
         const u64 v = a >> 32;
         if (v < rule.t_mask) {
           o[i] = rule.mask_id;
@@ -292,9 +256,13 @@ struct MaskState : PassState {
     return 0;
   }
 
-  // Staging of a piece of len ids and m rows.
-  bool stage(size_t len, size_t m, bool whole) {
-    return hids.grow(len, 3) && (!whole || (hrow.grow(m + 1) && hstarts.grow(len) && reserve_words(len)));
+  // Staging of a piece; rows: its offsets go up too (whole-word mode with a row_off).
+  bool stage(FlatPiece* p, bool whole, bool rows) {
+    if (!tiles_fit(p->len) || !hids.grow(p->len, 3) ||
+        (whole && !(hrow.grow(p->m + 1) && hstarts.grow(p->len) && reserve_words(p->len))))
+      return false;
+    p->ids = hids.get(), p->row = rows ? hrow.get() : nullptr;
+    return true;
   }
 };
 
@@ -330,10 +298,11 @@ int64_t EncodeDevice::mask(const int32_t* ids, size_t n, const int64_t* row_off,
   return ms.host[0] ? -6 : (int64_t)ms.host[1];
 }
 
-// Host ids in pieces of whole rows (piece_end).  A piece is the device passes on its own ids at
-// index_base + the index of its first id; the caller has validated row_off on the host, so token
-// mode stages no offsets, and whole-word mode stages the piece's local ones for the rows' first
-// tokens.  The outputs are per id, so the pieces are cut, staged and copied back here.
+// Host ids in pieces of whole rows (flat_pieces; a piece without ids is passed over).  A piece is
+// the device passes on its own ids at index_base + the index of its first id; the caller has
+// validated row_off on the host, so token mode stages no offsets, and whole-word mode stages the
+// piece's local ones for the rows' first tokens.  The outputs are per id: they come back at the
+// piece's first id, and the one stream counted is the selected tokens.
 int64_t EncodeDevice::mask_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MaskOpts& o,
                                 const int64_t* starts, const std::vector<int32_t>& lens, int32_t* out,
                                 int32_t* labels) {
@@ -347,38 +316,23 @@ int64_t EncodeDevice::mask_host(const int32_t* ids, size_t n, const int64_t* row
     return -1;
   }
   hipStream_t st = (hipStream_t)stream_;
-  const size_t R = row_off ? rows : 1, piece = piece_ids();
-  const HostIn in{ids, n, row_off};
-  std::vector<int64_t> local;
+  const FlatCall fc{"mask", HostIn{ids, n, row_off}, row_off ? rows : 1, 1, true};
   u64 selected = 0;
-  for (size_t r0 = 0; r0 < R;) {
-    u64 emitted = 0;
-    const size_t r1 = piece_end(&in, 1, R, r0, piece, 0, [](size_t) { return (u64)0; }, &emitted, nullptr);
-    const size_t a = row_off ? (size_t)row_off[r0] : 0, len = (row_off ? (size_t)row_off[r1] : n) - a, m = r1 - r0;
-    r0 = r1;
-    if (!len) continue;
-    if (!tiles_fit(len) || !ms.stage(len, m, whole)) {
-      std::fprintf(stderr, "[ERROR]\t encoder: mask staging allocation failed (%zu ids, %zu rows)\n", len, m);
-      return -1;
-    }
-    int32_t *const dids = ms.hids.get(), *const dout = dids + ms.hids.cap(), *const dlab = dout + ms.hids.cap();
-    ENC_OK(hipMemcpyAsync(dids, ids + a, len * 4, hipMemcpyHostToDevice, st));
-    const bool rows_up = whole && row_off;
-    if (whole) ENC_OK(hipMemcpyAsync(ms.hstarts.get(), starts + a, len * 8, hipMemcpyHostToDevice, st));
-    if (rows_up) {
-      local.resize(m + 1);
-      for (size_t i = 0; i <= m; ++i) local[i] = row_off[r1 - m + i] - (int64_t)a;
-      ENC_OK(hipMemcpyAsync(ms.hrow.get(), local.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-    }
-    const MaskCall c{dids,  len,   rows_up ? ms.hrow.get() : nullptr, m,   false, whole, whole ? ms.hstarts.get() : nullptr,
-                     dlens, (uint32_t)lens.size(), rule_of(o, a),     dout, dlab};
-    if (ms.check(c, st) < 0 || ms.apply(c, st) < 0) return -1;
-    ENC_OK(hipMemcpyAsync(out + a, dout, len * 4, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipMemcpyAsync(labels + a, dlab, len * 4, hipMemcpyDeviceToHost, st));
-    ENC_OK(hipStreamSynchronize(st));
-    selected += ms.host[1];
-  }
-  return (int64_t)selected;
+  const int r = flat_pieces(
+      st, fc, &selected,
+      [&](FlatPiece* p) { return ms.stage(p, whole, whole && row_off); },
+      [&](const FlatPiece& p, FlatOuts* outs) {
+        int32_t *const dout = ms.hids.get() + ms.hids.cap(), *const dlab = dout + ms.hids.cap();
+        if (whole) ENC_OK(hipMemcpyAsync(ms.hstarts.get(), starts + p.a, p.len * 8, hipMemcpyHostToDevice, st));
+        const MaskCall c{p.ids, p.len, p.row, p.m,  false, whole, whole ? ms.hstarts.get() : nullptr,
+                         dlens, (uint32_t)lens.size(), rule_of(o, p.a), dout, dlab};
+        if (ms.check(c, st) < 0 || ms.apply(c, st) < 0) return -1;
+        outs->add(out + p.a, dout, p.len * 4);
+        outs->add(labels + p.a, dlab, p.len * 4);
+        outs->count = &ms.host[1];
+        return 0;
+      });
+  return r < 0 ? -1 : (int64_t)selected;
 }
 
 }  // namespace shred

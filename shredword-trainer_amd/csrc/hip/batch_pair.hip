@@ -60,14 +60,12 @@ namespace {
 __global__ __launch_bounds__(kThreads) void k_pair_rows(Pairs pr, u64 rows, u64* __restrict__ err) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r > rows) return;
-  const int64_t va = pr.ra[r], vb = pr.rb[r];
-  const int64_t pa = r ? pr.ra[r - 1] : 0, pb = r ? pr.rb[r - 1] : 0;
-  bool bad = va < 0 || (u64)va > pr.na || pa > va || vb < 0 || (u64)vb > pr.nb || pb > vb;
-  if ((r == 0 && (va != 0 || vb != 0)) || (r == rows && ((u64)va != pr.na || (u64)vb != pr.nb))) bad = true;
-  if (bad) {
+  if (offset_bad(pr.ra, r, rows, pr.na, true) || offset_bad(pr.rb, r, rows, pr.nb, true)) {
     err[0] = 1;
     return;
   }
+  const int64_t va = pr.ra[r], vb = pr.rb[r];
+  const int64_t pa = r ? pr.ra[r - 1] : 0, pb = r ? pr.rb[r - 1] : 0;
   if (r && pa >= 0 && pb >= 0) {
     u64 ka, kb;
     if (!pr.first((u64)(va - pa), (u64)(vb - pb), &ka, &kb)) {

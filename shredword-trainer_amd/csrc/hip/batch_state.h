@@ -1,5 +1,8 @@
-// What the batch units (batch_device.hip, batch_pair.hip) share on the host: the state of a length
-// pass, the driver of a device call and the piece loop of a host call.
+// What the batch units share on the host: the state of a length pass (batch_device.hip,
+// batch_pair.hip), the driver of a device call, the piece loop of a host call with rectangular
+// outputs (host_pieces) and the one of a host call with flat output streams (flat_pieces, with the
+// count-then-write protocol and the one-row offsets of batch_mask.hip, batch_corrupt.hip and
+// batch_fim.hip).
 //
 // A length pass runs a row pass over the call's offset arrays (error words), a hipCUB inclusive sum
 // over k = 0 .. rows of (k ? x_{k-1} : 0) through a transform iterator (the exclusive prefix sum of
@@ -13,6 +16,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cassert>
 #include <cstdint>
 #include <cstdio>
 #include <memory>
@@ -261,6 +265,117 @@ int host_pieces(int device, hipStream_t st, const HostCall& c, Count&& count, St
     r0 = p.r1;
   }
   return 0;
+}
+
+// ---- a host call whose outputs are flat streams (mask_host, corrupt_host, fim_host) ----
+// Only the device passes find a piece's stream lengths, where host_pieces places every output from
+// counts the host has before the piece runs: the two walks share the cut and stay two functions.
+
+// The piece cut of a call bounded by ids and rows only.
+inline size_t piece_end(const HostIn& in, size_t rows, size_t r0, size_t piece) {
+  u64 emitted;
+  return piece_end(&in, 1, rows, r0, piece, 0, [](size_t) { return (u64)0; }, &emitted, nullptr);
+}
+
+// The offsets {0, n} of a call without row_off (one row of all ids) on the device; part of a
+// unit's state.
+struct OneRow {
+  PinnedWords host;
+  DeviceBuf<int64_t> dev;
+  bool ensure() { return host.ensure(2) && dev.grow(2); }
+  int put(u64 n, hipStream_t st, const int64_t** row) {
+    host[0] = 0, host[1] = n;
+    ENC_OK(hipMemcpyAsync(dev.get(), host.get(), 16, hipMemcpyHostToDevice, st));
+    *row = dev.get();
+    return 0;
+  }
+};
+
+struct FlatCall {
+  const char* what;
+  HostIn in;
+  size_t rows;      // 1 without in.row
+  int streams;      // running totals kept: 1 or 2
+  bool skip_empty;  // a piece without ids is passed over
+};
+
+// Rows [r0, r0 + m) and ids [a, a + len) of the call, staged at ids and (when the unit stages
+// offsets) row: m + 1 entries rebased to the piece.
+struct FlatPiece {
+  size_t r0, m, a, len;
+  int32_t* ids;
+  int64_t* row;
+};
+
+// What a unit's step lists for a piece: the outputs to copy back, and where (pinned) the piece's
+// length in every stream is once the stream is idle.
+struct FlatOuts {
+  static constexpr int kMax = 5;
+  struct {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  } out[kMax];
+  int n = 0;
+  const u64* count = nullptr;
+  void add(void* host, const void* dev, size_t bytes) {
+    if (!host || !bytes) return;
+    assert(n < kMax);
+    out[n++] = {host, dev, bytes};
+  }
+};
+
+// One walk over the call.  Per piece: cut it; stage(&piece) grows the unit's staging and sets
+// where the ids and the offsets go (row stays nullptr: none staged; false: it cannot be staged);
+// both go up; step(piece, &outs) runs the unit's passes at the totals so far (0 or -1);
+// the outputs it lists come back, the stream is synchronised and the piece's counts are added to
+// total[0 .. streams).
+template <class Stage, class Step>
+int flat_pieces(hipStream_t st, const FlatCall& c, u64* total, Stage&& stage, Step&& step) {
+  const size_t piece = piece_ids();
+  std::vector<int64_t> local;
+  for (int k = 0; k < c.streams; ++k) total[k] = 0;
+  for (size_t r0 = 0; r0 < c.rows;) {
+    const size_t r1 = piece_end(c.in, c.rows, r0, piece);
+    const size_t a = c.in.row ? (size_t)c.in.row[r0] : 0;
+    FlatPiece p{r0, r1 - r0, a, (c.in.row ? (size_t)c.in.row[r1] : c.in.n) - a, nullptr, nullptr};
+    r0 = r1;
+    if (c.skip_empty && !p.len) continue;
+    if (!stage(&p)) {
+      std::fprintf(stderr, "[ERROR]\t encoder: %s staging allocation failed (%zu ids, %zu rows)\n", c.what, p.len, p.m);
+      return -1;
+    }
+    if (p.len) ENC_OK(hipMemcpyAsync(p.ids, c.in.ids + a, p.len * 4, hipMemcpyHostToDevice, st));
+    if (p.row) {
+      local.resize(p.m + 1);
+      for (size_t i = 0; i <= p.m; ++i)
+        local[i] = c.in.row ? c.in.row[p.r0 + i] - (int64_t)a : (int64_t)(i ? c.in.n : 0);
+      ENC_OK(hipMemcpyAsync(p.row, local.data(), (p.m + 1) * 8, hipMemcpyHostToDevice, st));
+    }
+    FlatOuts outs;
+    if (step(p, &outs) < 0) return -1;
+    for (int k = 0; k < outs.n; ++k)
+      ENC_OK(hipMemcpyAsync(outs.out[k].host, outs.out[k].dev, outs.out[k].bytes, hipMemcpyDeviceToHost, st));
+    ENC_OK(hipStreamSynchronize(st));
+    for (int k = 0; k < c.streams; ++k) total[k] += outs.count[k];
+  }
+  return 0;
+}
+
+// The caps of a call's streams against what it emits.  Caps that hold the static bound take one
+// write round; smaller ones a round of counts first, so that nothing is written when they do not
+// suffice or no output was given.  round(write) walks the call and leaves the totals, which are
+// the call's result either way, in total[0 .. streams).  0 or -1.
+template <class Round>
+int count_then_write(bool given, int streams, const u64* cap, const u64* bound, const u64* total, Round&& round) {
+  bool fits = given;
+  for (int k = 0; k < streams; ++k) fits = fits && cap[k] >= bound[k];
+  if (!fits) {
+    if (round(false) < 0) return -1;
+    for (int k = 0; k < streams; ++k)
+      if (!given || cap[k] < total[k]) return 0;
+  }
+  return round(true);
 }
 
 }  // namespace

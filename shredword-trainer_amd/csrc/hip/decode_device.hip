@@ -10,7 +10,7 @@
 // length 0 (unk_len == 0) repeat a Q value; "the last k" skips them.
 //
 //   k_dec_check     strict mode only: one workgroup per kChunk ids, flags an id outside the vocabulary;
-//   k_dec_rows      one thread per row_off entry: range, order and end points (an error word, no
+//   k_dec_rows      one thread per row_off entry: offset_bad of encode_common.h (an error word, no
 //                   atomics), and, with a separator, mark[v] = the number of rows that end just
 //                   before id v, written by the first row of each run of equal offsets (the run's
 //                   end by binary search), so no two threads write one entry;
@@ -87,15 +87,12 @@ __global__ __launch_bounds__(kThreads) void k_dec_rows(const int64_t* __restrict
                                                        uint32_t* __restrict__ mark, u64* __restrict__ err) {
   const u64 r = (u64)blockIdx.x * kThreads + threadIdx.x;
   if (r > rows) return;
-  const int64_t v = row[r];
-  const int64_t prev = r ? row[r - 1] : 0;
-  bool bad = v < 0 || (u64)v > n || prev > v;
-  if (ends && ((r == 0 && v != 0) || (r == rows && (u64)v != n))) bad = true;
-  if (bad) {
+  if (offset_bad(row, r, rows, n, ends != 0)) {
     err[1] = 1;
     return;
   }
-  if (mark && r >= 1 && (r == 1 || prev != v)) {  // rows r - 1 .. e - 2 end before id v (0 <= v <= n)
+  const int64_t v = row[r];
+  if (mark && r >= 1 && (r == 1 || row[r - 1] != v)) {  // rows r - 1 .. e - 2 end before id v (0 <= v <= n)
     u64 lo = r + 1, hi = rows + 1;
     while (lo < hi) {
       const u64 mid = lo + ((hi - lo) >> 1);

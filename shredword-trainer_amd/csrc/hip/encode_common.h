@@ -1,6 +1,7 @@
 // What the encoder units (encode_device.hip, encode_spans.hip, encode_special.hip, ...) share on the
 // host side: the error macro, the device guard, the device resources every pass's state is built
-// from, and the piece rules of the host paths.
+// from, and the piece rules of the host paths; and on the device the test of an offset array, with
+// the kernel of the units that only check one.
 // Included by .hip files only.
 #pragma once
 
@@ -168,6 +169,40 @@ struct HostStage : PassState {
     return false;
   }
 };
+
+// ---- offset arrays (row_off, doc_off) given on the device ----
+
+// An offset array is good when its count + 1 entries lie in [0, n] and do not decrease and, with
+// `ends`, off[0] == 0 and off[count] == n.  offset_bad: entry i, 0 <= i <= count, breaks that.  It
+// reads off[i] and the entry before it, off[i - 1] (i > 0), so a descent is seen by the thread of
+// its second entry.  The row kernels run one thread per entry, and each thread that finds one
+// stores the same 1 to the call's error word: ordinary stores, no atomics.
+__device__ __forceinline__ bool offset_bad(const int64_t* __restrict__ off, uint64_t i, uint64_t count, uint64_t n,
+                                           bool ends) {
+  const int64_t v = off[i];
+  if (v < 0 || (uint64_t)v > n || (i && off[i - 1] > v)) return true;
+  return ends && ((i == 0 && v != 0) || (i == count && (uint64_t)v != n));
+}
+
+constexpr int kRowThreads = (int)kBatchRowsPerGroup;  // the workgroup of every row kernel
+
+// (Not every unit has an offset array that is only checked.  As with k_bat_row_start, every .hip
+// that includes this header and launches the kernel carries a copy of its own: batch_corrupt,
+// batch_fim and encode_docs.)
+[[maybe_unused]] __global__ __launch_bounds__(kRowThreads) void k_offsets_check(const int64_t* __restrict__ off,
+                                                                                uint64_t count, uint64_t n,
+                                                                                uint64_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * kRowThreads + threadIdx.x;
+  if (i <= count && offset_bad(off, i, count, n, true)) *flag = 1;
+}
+
+// Launches it over a whole call's array, end points included (0 or -1); *flag was cleared on st.
+[[maybe_unused]] int check_offsets(const int64_t* off, uint64_t count, uint64_t n, uint64_t* flag, hipStream_t st) {
+  k_offsets_check<<<dim3((unsigned)((count + kRowThreads) / kRowThreads)), dim3(kRowThreads), 0, st>>>(off, count, n,
+                                                                                                      flag);
+  ENC_OK(hipGetLastError());
+  return 0;
+}
 
 // ---- pieces of the host paths ----
 

@@ -8,8 +8,8 @@
 // the encoder then sees no word, merge or special across a boundary ('\n' is a delimiter and no
 // special holds one), and the span passes' lines are exactly the documents.
 //
-//   k_docs_check    one thread per doc_off entry: first entry 0, last entry n, non-decreasing (an
-//                   error word, no atomics); the host reads it before anything else runs.
+//   k_offsets_check (encode_common.h) one thread per doc_off entry, into an error word; the host
+//                   reads it before anything else runs.
 //   k_docs_expand   the copy, n + docs bytes: document d goes to offset B[d] = doc_off[d] + d, its
 //                   '\n' bytes become ' ' (a delimiter too, so the words are unchanged), and one
 //                   '\n' follows it at B[d + 1] - 1.  One workgroup per 4096 output bytes, 16 per
@@ -60,16 +60,6 @@ __device__ __forceinline__ u64 last_not_above(u64 lo, u64 hi, u64 v, At at) {
     if (at(mid) <= v) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-__global__ __launch_bounds__(kThreads) void k_docs_check(const int64_t* __restrict__ doc_off, u64 docs, u64 n,
-                                                         u64* __restrict__ flag) {
-  const u64 i = (u64)blockIdx.x * kThreads + threadIdx.x;
-  if (i > docs) return;
-  const int64_t v = doc_off[i];
-  bool bad = v < 0 || (u64)v > n || (i == 0 && v != 0) || (i == docs && (u64)v != n);
-  if (!bad && i < docs) bad = v > doc_off[i + 1];
-  if (bad) *flag = 1;  // several threads may store at once, on purpose: all store the same value
 }
 
 // 0x80 in every byte of w that equals '\n'.
@@ -188,9 +178,7 @@ int64_t EncodeDevice::encode_docs(const uint8_t* text, size_t n, const int64_t* 
   ENC_OK(hipEventRecord(ev[0], st));
   if (doc_off) {
     ENC_OK(hipMemsetAsync(dx.flag.get(), 0, 8, st));
-    k_docs_check<<<dim3((unsigned)(((u64)docs + kThreads) / kThreads)), dim3(kThreads), 0, st>>>(doc_off, (u64)docs,
-                                                                                               (u64)n, dx.flag.get());
-    ENC_OK(hipGetLastError());
+    if (check_offsets(doc_off, (u64)docs, (u64)n, dx.flag.get(), st) < 0) return -1;
     ENC_OK(hipMemcpyAsync(dx.host.get(), dx.flag.get(), 8, hipMemcpyDeviceToHost, st));
     ENC_OK(hipEventRecord(ev[1], st));
     ENC_OK(hipStreamSynchronize(st));

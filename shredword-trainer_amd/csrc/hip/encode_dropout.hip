@@ -6,8 +6,8 @@
 // rank"; dropout masks the rank of a dropped candidate to "none" where the rank is looked up, so the
 // min-scan loops are those of encode_device.hip.  A candidate (a, b) of rank r whose right token b
 // begins at byte position pos is dropped iff
-//     mix(mix(seed + 0x9E3779B97F4A7C15 * (pos + 1)) ^ r) >> 32  <  T,   T = (u64)(p * 2^32)
-// (mix: murmur3's fmix64): a function of (seed, pos, r) alone, so a boundary that the loop looks at
+//     draw(seed, pos, r) >> 32  <  T,   T = (u64)(p * 2^32)
+// (draw_hash.h): a function of (seed, pos, r) alone, so a boundary that the loop looks at
 // again after a neighbouring merge gets the same answer, and the ids do not depend on how the text
 // was staged.  The word cache cannot serve this (every occurrence of a word differs), so a dropout
 // call always runs here.
@@ -30,6 +30,7 @@
 #include <cstdio>
 
 #include "../host/encoder.h"
+#include "draw_hash.h"
 #include "encode_common.h"
 #include "encode_words.h"
 
@@ -44,21 +45,11 @@ struct Drop {
   u64 seed, thresh;  // thresh = T in [1, 2^32]
 };
 
-__device__ __forceinline__ u64 mix64(u64 x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-
 // pair_rank with the dropped candidates' ranks masked: pos is the position of b's first byte.
 __device__ __forceinline__ int drop_rank(const u64* __restrict__ tab, u64 mask, int a, int b, const Drop& d, u64 pos) {
   const int r = pair_rank(tab, mask, a, b);
   if (r == kInf) return kInf;
-  const u64 u = mix64(mix64(d.seed + 0x9E3779B97F4A7C15ull * (pos + 1)) ^ (u64)(uint32_t)r);
-  return (u >> 32) < d.thresh ? kInf : r;
+  return (draw(d.seed, pos, (u64)(uint32_t)r) >> 32) < d.thresh ? kInf : r;
 }
 
 // Where the tokens of a strip word begin, as a bit mask of the word's bytes.

@@ -22,6 +22,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import bad_offsets
+
 from encode_ref import model_merges
 
 pytestmark = pytest.mark.gpu
@@ -439,7 +441,7 @@ def test_malformed_row_offsets(enc):
              [0, 600, 599, n],       # a decreasing pair
              [0, -1, n],             # a negative entry
              [-1, 500, n],
-             [0, n + 5, n]]
+             [0, n + 5, n]] + bad_offsets.at_256(n)
     for row in cases:
         R = len(row) - 1
         for r, out, lens, mask in _raw_pad(enc, ids, row, n, R * n):

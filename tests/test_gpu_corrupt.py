@@ -16,6 +16,8 @@ import sys
 import numpy as np
 import pytest
 
+import bad_offsets
+
 import corrupt_ref
 from corrupt_ref import uniform_cum
 
@@ -365,7 +367,7 @@ def test_errors_write_nothing(enc):
         return tuple(res)
 
     assert both(good)[0] >= 0
-    for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n]):
+    for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n], *bad_offsets.at_256(n)):
         assert both(good, np.array(bad_row, dtype=np.int64)) == (-6, -6), bad_row
 
     def raw_opts(**kw):
@@ -484,3 +486,66 @@ def test_first_use_in_any_order():
                 assert len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want)), order
         finally:
             e.destroy()
+
+
+# ---- 11. caps of a host call in many pieces ------------------------------------------
+
+CAPS_CHILD = r"""
+import ctypes, os, sys
+import numpy as np
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import corrupt_ref
+from shredword.cbase import lib
+from shredword.encoder import BPEEncoder
+e = BPEEncoder.from_merges(np.array([[97, 98, 256], [256, 256, 257]], dtype=np.int32), special_tokens=[b"<|s|>"])
+rng = np.random.default_rng(67)
+lens = rng.integers(0, 61, size=40)
+lens[[0, 7, 8, 39]] = 0
+row = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+n, R = int(row[-1]), 40
+assert lens.max() > 7 and n > 40 * 7
+ids = rng.integers(97, 100, size=n).astype(np.int32)
+cum, _ = e.corrupt_lengths((1, 5))
+want = corrupt_ref.corrupt_ref(ids, row, p_start=0.07, len_cum=cum, seed=77, sentinel_first=999, specials=(258, 259),
+                               index_base=5)
+ti, tt = want[0].size, want[2].size
+assert 0 < ti < n and 0 < tt < 2 * n + R   # below the bounds: exact caps take the count round
+opts, _keep = e._corrupt_opts(999, -1, 100, 0.07, 0.15, (1, 5), None, 77, True, (), True, 5)
+
+def call(in_cap, tgt_cap):
+    # in_ids, in_row, tgt_ids, tgt_row, in_src, pre-filled, as large as the bounds
+    b = [np.full(n + 1, -7, np.int32), np.full(R + 2, -7, np.int64), np.full(2 * n + R + 1, -7, np.int32),
+         np.full(R + 2, -7, np.int64), np.full(n + 1, -7, np.int64)]
+    tn = ctypes.c_size_t(12345)
+    r = lib.shred_corrupt_rows(e.enc, ids.ctypes.data, n, row.ctypes.data, R, ctypes.byref(opts), b[0].ctypes.data,
+                               in_cap, b[1].ctypes.data, b[4].ctypes.data, b[2].ctypes.data, tgt_cap,
+                               b[3].ctypes.data, ctypes.byref(tn))
+    assert (r, tn.value) == (ti, tt), (in_cap, tgt_cap, r, tn.value)
+    return b
+
+def written(b, what):
+    for k, w in enumerate(want):
+        assert np.array_equal(b[k][:w.size], w) and (b[k][w.size:] == -7).all(), (what, k)
+
+os.environ.pop("SHREDWORD_BATCH_PIECE", None)
+written(call(ti, tt), "one piece")
+os.environ["SHREDWORD_BATCH_PIECE"] = "7"
+written(call(ti, tt), "exact caps")                  # a count round, then the write round
+written(call(n, 2 * n + R), "caps at the bound")     # one round
+for short in ((ti - 1, tt), (ti, tt - 1), (n, tt - 1), (ti - 1, 2 * n + R)):
+    assert all((a == -7).all() for a in call(*short)), short
+e.destroy()
+print("caps ok")
+"""
+
+
+def test_host_pieces_caps_in_a_fresh_process(tmp_path):
+    """40 rows of 0..60 ids in pieces of 7: caps that are exactly T_in and T_tgt (below the static bounds)
+    and caps at the bounds give the reference's and the one-piece call's outputs; a cap one short, of
+    either stream, returns both totals and leaves every output untouched."""
+    from conftest import PKG, TESTS
+    script = tmp_path / "caps.py"
+    script.write_text(CAPS_CHILD)
+    r = subprocess.run([sys.executable, str(script), TESTS, PKG], env=dict(os.environ, SHREDWORD_BATCH_PIECE="7"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "caps ok" in r.stdout, r.stdout + r.stderr

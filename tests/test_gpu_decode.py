@@ -22,6 +22,8 @@ import re
 import numpy as np
 import pytest
 
+import bad_offsets
+
 from conftest import golden_cases
 from encode_ref import derived_byte_map, model_merges, oracle_encode, token_bytes, vocab_freqs
 
@@ -345,7 +347,7 @@ def test_malformed_rows():
              [0, 500, n - 1],        # row_off[rows] == n - 1
              [0, 500, n + 1],        # row_off[rows] == n + 1
              [0, -1, n],
-             [0, n + 5, n]]
+             [0, n + 5, n]] + bad_offsets.at_256(n)
     with _enc_from(merges) as enc:
         for row in cases:
             for sep in (10, -1):

@@ -20,6 +20,8 @@ import re
 import numpy as np
 import pytest
 
+import bad_offsets
+
 from encode_ref import oracle_encode, token_bytes
 
 pytestmark = pytest.mark.gpu
@@ -394,7 +396,8 @@ def test_bad_doc_off():
                  ([0, 5, n + 2], None),      # last entry > n
                  ([0, -1, n], None),
                  ([3], None),                # no document, but text
-                 ([0, 5, n], n - 4)]         # the offsets of a longer text
+                 ([0, 5, n], n - 4),         # the offsets of a longer text
+                 *[(off, None) for off in bad_offsets.at_256(n)]]
         for off, short in cases:
             for raw in (_raw_host, _raw_device):
                 r, row, st = raw(enc, text, off, n=short)

@@ -16,6 +16,8 @@ import sys
 import numpy as np
 import pytest
 
+import bad_offsets
+
 import fim_ref
 
 pytestmark = pytest.mark.gpu
@@ -252,7 +254,7 @@ def test_errors_write_nothing(enc):
         return tuple(res)
 
     assert both(good)[0] >= n and both(good, cuts=ok_cuts)[0] >= n
-    for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n]):
+    for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n], *bad_offsets.at_256(n)):
         assert both(good, np.array(bad_row, dtype=np.int64)) == (-6, -6), bad_row
     L2 = int(row[3] - row[2])
     for bad in ((1, 0, 0) if L2 else (0, -1, 0), (0, L2 + 1, 0), (0, 0, 2), (-1, -1, 0), (0, -1, -1), (-1, 0, 1),
@@ -424,10 +426,10 @@ def test_character_cuts(enc):
     ml = fim_ref.fim_cuts_ref(bytes(buf), off, **dict(kw, min_len=6))
     piece, mode, _ = enc.fim_cuts_device(d_buf, _dev(np.array(off)), **dict(kw, min_len=6))
     assert np.array_equal(piece.cpu().numpy(), ml[0]) and np.array_equal(mode.cpu().numpy(), ml[1])
-    with pytest.raises(ValueError):
-        bad = np.array(off)
-        bad[3] = bad[4] + 1
-        enc.fim_cuts_device(d_buf, _dev(bad), **kw)
+    n = len(buf)
+    for bad in ([0, 9, 5, n], [1, 5, n], [0, 5, n - 1], [0, -1, n], [0, n + 1, n], *bad_offsets.at_256(n)):
+        with pytest.raises(ValueError):   # the call's -6
+            enc.fim_cuts_device(d_buf, _dev(np.array(bad, dtype=np.int64)), **kw)
 
 
 def test_encode_fim(enc):
@@ -476,3 +478,63 @@ def test_encode_fim(enc):
     assert np.array_equal(starts.cpu().numpy(), enc.encode_spans(lines)[1])
     with pytest.raises(ValueError):
         enc.encode_fim(docs, level="word", **SENT)
+
+
+# ---- 11. caps of a host call in many pieces ---------------------------------------------
+
+CAPS_CHILD = r"""
+import ctypes, os, sys
+import numpy as np
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import fim_ref
+from shredword.cbase import lib
+from shredword.encoder import BPEEncoder
+e = BPEEncoder.from_merges(np.array([[97, 98, 256], [256, 256, 257]], dtype=np.int32), special_tokens=[b"<|s|>"])
+rng = np.random.default_rng(67)
+lens = rng.integers(0, 61, size=40)
+lens[[0, 7, 8, 39]] = 0
+row = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+n, R = int(row[-1]), 40
+assert lens.max() > 7 and n > 40 * 7
+ids = rng.integers(97, 100, size=n).astype(np.int32)
+kw = dict(pre_id=900, suf_id=901, mid_id=902, seed=77, row_base=5)
+want = fim_ref.fim_ref(ids, row, **kw)      # out_ids, out_row, out_src, out_seg, row_info
+T = want[0].size
+assert n < T < n + 3 * R                    # below the bound: an exact cap takes the count round
+opts = e._fim_opts(900, 901, 902, 0.5, 0.5, 77, 0, 5)
+
+def call(cap):
+    b = [np.full(n + 3 * R + 1, -7, np.int32), np.full(R + 2, -7, np.int64), np.full(n + 3 * R + 1, -7, np.int64),
+         np.full(n + 3 * R + 1, 249, np.uint8), np.full(3 * R + 1, -7, np.int64)]
+    r = lib.shred_fim_rows(e.enc, ids.ctypes.data, n, row.ctypes.data, R, ctypes.byref(opts), None, b[0].ctypes.data,
+                           cap, b[1].ctypes.data, b[2].ctypes.data, b[3].ctypes.data, b[4].ctypes.data)
+    assert r == T, (cap, r)
+    return b
+
+def written(b, what):
+    for k, w in enumerate(want):
+        w = w.reshape(-1)
+        fill = 249 if w.dtype == np.uint8 else -7
+        assert np.array_equal(b[k][:w.size], w) and (b[k][w.size:] == fill).all(), (what, k)
+
+os.environ.pop("SHREDWORD_BATCH_PIECE", None)
+written(call(T), "one piece")
+os.environ["SHREDWORD_BATCH_PIECE"] = "7"
+written(call(T), "exact cap")                    # a count round, then the write round
+written(call(n + 3 * R), "cap at the bound")     # one round
+assert all((a == (249 if a.dtype == np.uint8 else -7)).all() for a in call(T - 1))
+e.destroy()
+print("caps ok")
+"""
+
+
+def test_host_pieces_caps_in_a_fresh_process(tmp_path):
+    """40 rows of 0..60 ids in pieces of 7: a cap that is exactly T_out (below the static bound) and a cap at
+    the bound give the reference's and the one-piece call's outputs; a cap one short returns T_out and leaves
+    every output untouched."""
+    from conftest import PKG, TESTS
+    script = tmp_path / "caps.py"
+    script.write_text(CAPS_CHILD)
+    r = subprocess.run([sys.executable, str(script), TESTS, PKG], env=dict(os.environ, SHREDWORD_BATCH_PIECE="7"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "caps ok" in r.stdout, r.stdout + r.stderr

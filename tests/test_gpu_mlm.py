@@ -19,6 +19,8 @@ import re
 import numpy as np
 import pytest
 
+import bad_offsets
+
 import mlm_ref
 
 pytestmark = pytest.mark.gpu
@@ -400,7 +402,8 @@ def test_errors_write_nothing(enc):
     assert _raw_both(enc, ids, row, starts, _opts(p_mask=0.5, p_random=0.5)) [0] >= 0  # T sum = 2^32 exactly
     assert _raw_both(enc, ids, row, starts, _opts(p_random=0.0, rand_vocab=0))[0] >= 0  # not needed without random
     for whole in (0, 1):
-        for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n]):
+        for bad_row in ([0, 50, 40, n], [1, 50, n], [0, 50, n - 1], [0, -1, n], [0, 50, n + 1, n],
+                        *bad_offsets.at_256(n)):
             r = np.array(bad_row, dtype=np.int64)
             assert _raw_both(enc, ids, r, starts, _opts(whole_word=whole)) == (-6, -6), bad_row
     # rows without a row_off, and labels on top of an input

@@ -24,6 +24,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import bad_offsets
+
 import pair_ref
 
 pytestmark = pytest.mark.gpu
@@ -420,9 +422,14 @@ def test_malformed_row_offsets(enc):
                 [0, 500, 600, n - 1],      # a bad end point
                 [0, 500, 600, n + 1],
                 [0, 600, 599, n],          # a decreasing entry
-                [0, -1, 5, n]):            # a negative entry
+                [0, -1, 5, n],             # a negative entry
+                *bad_offsets.at_256(n)):
         row = np.array(row, dtype=np.int64)
-        for ex in ((ids, row, ids, good), (ids, good, ids, row)):
+        other = good
+        if row.size != good.size:              # as many examples on the good side
+            other = np.minimum(np.arange(row.size, dtype=np.int64) * 4, n)
+            other[-1] = n
+        for ex in ((ids, row, ids, other), (ids, other, ids, row)):
             for strategy in (0, 3):
                 for r, widest, *bufs in _raw(enc, ex, 64, 64 * 64, 64, max_len=64, strategy=strategy):
                     assert r == -6 and widest == 12345 and _untouched(*bufs), (row, strategy)

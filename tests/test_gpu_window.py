@@ -20,6 +20,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import bad_offsets
+
 import window_ref
 
 pytestmark = pytest.mark.gpu
@@ -306,7 +308,8 @@ def test_malformed_row_offsets(enc):
                 [0, 600, 599, n],       # a decreasing pair
                 [0, -1, n],             # a negative entry
                 [-1, 500, n],
-                [0, n + 5, n]):         # out of range
+                [0, n + 5, n],          # out of range
+                *bad_offsets.at_256(n)):
         for r, widest, *bufs in _raw(enc, ids, row, 64, 8, 64, 64 * 64, 64):
             assert r == -6 and widest == 12345 and _untouched(*bufs), row
         d_ids, d_row = torch.from_numpy(ids).cuda(), torch.tensor(row, dtype=torch.int64).cuda()
