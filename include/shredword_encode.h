@@ -897,6 +897,79 @@ int64_t shred_fim_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const in
 int shred_fim_cuts_device(ShredEncoder* enc, const void* text, size_t n, const void* doc_off, size_t docs,
                           const ShredFimOpts* opts, void* piece_off, void* doc_mode, void* stream, double* kernel_ms);
 
+/* ---- MinHash signatures and LSH band keys of rows on the GPU (near-duplicate removal) ----------------
+ *
+ * Near-duplicate removal (Broder's MinHash with locality-sensitive hashing over bands, as in the
+ * deduplication of most pre-training corpora) sits between "encoded" and "batched".  These calls work
+ * on the flat (ids, row_off) pair: every row gets a signature of K 32-bit minima over its shingles of
+ * w consecutive ids, and optionally B band keys; two rows are LSH candidates iff they share a key in
+ * some band, and the share of equal signature columns estimates the Jaccard similarity of their
+ * shingle sets.  The definition is exact, all arithmetic is mod 2^64, and every call gives the same bits.
+ *
+ * Inputs:
+ *   ids         n int32.  Any value: ids are never looked up.  An id enters the hash as its 32-bit
+ *               pattern, zero-extended.
+ *   row_off     the usual rows + 1 int64, or NULL with rows == 0 for one row; validated as elsewhere (-6).
+ *               R below is the number of rows, 1 without row_off.
+ *   opts        the scalar options, ShredMinhashOpts below:
+ *     seed      a 64-bit seed.
+ *     num_perm  K, 1 <= K <= SHRED_MINHASH_MAX_PERM.
+ *     shingle   w, 1 <= w <= SHRED_MINHASH_MAX_SHINGLE.
+ *     bands     B: 0 for none, else 1 <= B <= K with K % B == 0.  Anything else returns -1.
+ *
+ * Definitions.  mix, G and d(x, c) are those of the masked-LM section; the constants are
+ * SHINGLE = (1 << 40) + 8, A = (1 << 40) + 9, B = (1 << 40) + 10 and BAND = (1 << 40) + 11, beside those
+ * of the FIM section.
+ *   The shingles of a row of len ids: the len - w + 1 windows of w consecutive ids when len >= w; one
+ *             shingle of all len ids when 0 < len < w (a short document still has a signature); none
+ *             when len == 0.  No shingle crosses a row.
+ *   The hash of a shingle of c ids t_0 .. t_{c-1}:  h_0 = d(c, SHINGLE), h_{j+1} = mix(h_j ^ t_j),
+ *             x = h_c >> 32 (a 32-bit value).
+ *   Permutation i, 0 <= i < K:  a_i = d(i, A) | 1, b_i = d(i, B), v_i(x) = (a_i * x + b_i) >> 32 taken
+ *             as a uint32 (the multiply-add-shift family on a 32-bit key).
+ *   sig[r, i] = the minimum of v_i(x) over the shingles of row r; 0xFFFFFFFF for an empty row.
+ *   With bands, Rb = K / B:  g_0 = d(j, BAND), g_{k+1} = mix(g_k ^ sig[r, j * Rb + k]), key[r, j] = g_Rb.
+ *
+ * Outputs:
+ *   sig         R x K uint32, row-major.  Must not be NULL.
+ *   bands_out   R x B uint64, row-major; NULL iff bands == 0 (else -1).
+ *   With R == 0 (row_off of one entry) both hold nothing, and either may be NULL on both calls.
+ *
+ * Returns R.  Errors, with nothing written: -1 bad argument (above; sig NULL; an R x K that does not fit
+ * size_t / int64) or HIP error; -6 bad row_off.  (A HIP error after the first piece of shred_minhash_rows
+ * leaves the earlier pieces' output in place.)
+ *
+ * All empty rows share their signature and so their keys: callers filter by length.  The result depends
+ * on (seed, K, w, B) and the row's ids alone, not on where the row lies in the stream or on how a host
+ * call was staged, so there is no index base; host and device calls, and every piece size, agree.
+ *
+ * The MinHash scratch (one error word, events and the host call's staging) is allocated on the first
+ * MinHash call and freed with the encoder, so the other calls' footprints are unchanged.
+ */
+#define SHRED_MINHASH_MAX_PERM 512
+#define SHRED_MINHASH_MAX_SHINGLE 64
+
+typedef struct ShredMinhashOpts {
+  uint64_t seed;
+  int32_t num_perm;
+  int32_t shingle;
+  int32_t bands;
+} ShredMinhashOpts;
+
+/* All buffers on the encoder's device (row_off is validated there before anything is written); queued
+ * on `stream` (NULL = the encoder's own) and synchronised before return.  Every buffer needs only its
+ * element's alignment, so tensor views fit.  kernel_ms (may be NULL) receives the device time of the
+ * passes. */
+int64_t shred_minhash_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             const ShredMinhashOpts* opts, void* sig, void* bands_out, void* stream,
+                             double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget
+ * of the batch calls (one row is taken whole, however long).  row_off is validated on the host before
+ * anything is staged. */
+int64_t shred_minhash_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           const ShredMinhashOpts* opts, uint32_t* sig, uint64_t* bands_out);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

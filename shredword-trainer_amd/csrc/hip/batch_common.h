@@ -48,7 +48,8 @@ __device__ __forceinline__ u64 wave_upper_bound(const u64* __restrict__ E, u64 l
   return lo;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// (batch_minhash.hip has no vector stores)
+[[maybe_unused]] bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // A lane's kLane consecutive entries of p at g, cnt of them inside the array (the others read as
 // 0 and are not written).  vec: the host found p 16-byte aligned (aligned16; tensor views are only

@@ -1,4 +1,4 @@
-// The seeded draw of the dropout, masked-LM, span-corruption and fill-in-the-middle units:
+// The seeded draw of the dropout, masked-LM, span-corruption, fill-in-the-middle and MinHash units:
 //     d(x, c) = mix(mix(seed + G (x + 1)) ^ c)      (mix: murmur3's fmix64, arithmetic mod 2^64)
 // x is a position or a row index, c says which decision of that x is drawn (bits 63..32 of d).
 // Included by .hip files only.
@@ -37,12 +37,17 @@ enum Domain : uint64_t {
   kFimC,              // fill-in-the-middle: row x is transformed
   kCutA,              // fill-in-the-middle: its two cuts
   kCutB,
-  kMode               // fill-in-the-middle: PSM or SPM
+  kMode,              // fill-in-the-middle: PSM or SPM
+  kMhShingle,         // MinHash: where the hash chain of a shingle of x ids starts
+  kMhA,               // MinHash: multiplier and
+  kMhB,               //          addend of permutation x
+  kMhBand             // MinHash: where the hash chain of band x starts
 };
 // (strictly increasing, so pairwise distinct)
 static_assert(kSel >= 1ull << 40 && kAct == kSel + 1 && kStart == kAct + 1 && kLen == kStart + 1 &&
-                  kFimC == kLen + 1 && kCutA == kFimC + 1 && kCutB == kCutA + 1 && kMode == kCutB + 1,
-              "the domain constants are (1 << 40) + 0 .. 7 (include/shredword_encode.h)");
+                  kFimC == kLen + 1 && kCutA == kFimC + 1 && kCutB == kCutA + 1 && kMode == kCutB + 1 &&
+                  kMhShingle == kMode + 1 && kMhA == kMhShingle + 1 && kMhB == kMhA + 1 && kMhBand == kMhB + 1,
+              "the domain constants are (1 << 40) + 0 .. 11 (include/shredword_encode.h)");
 
 // Values of the definition as the tests' Python reference computes it; the second wraps mod 2^64
 // in seed + G (x + 1), the third is a dropout draw (c: a rank).

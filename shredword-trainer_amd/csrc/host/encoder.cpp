@@ -781,4 +781,43 @@ int shred_fim_cuts_device(ShredEncoder* enc, const void* text, size_t n, const v
                             (int8_t*)doc_mode, stream, kernel_ms);
 }
 
+namespace {
+// What the two MinHash calls refuse before any work (0 or -1), and their options.
+int minhash_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                 const ShredMinhashOpts* o, const void* sig, const void* bands_out,
+                 shred::EncodeDevice::MinhashOpts* m) {
+  if (!enc || !o || (n && !ids) || (!row_off && rows)) return -1;
+  const int32_t K = o->num_perm, w = o->shingle, B = o->bands;
+  if (K < 1 || K > SHRED_MINHASH_MAX_PERM || w < 1 || w > SHRED_MINHASH_MAX_SHINGLE) return -1;
+  if (B < 0 || B > K || (B && K % B) || (bands_out && !B)) return -1;
+  const uint64_t R = row_off ? rows : 1;
+  // outputs of no rows hold nothing: an empty tensor's NULL fits
+  if (R && (!sig || (B && !bands_out))) return -1;
+  // sig in bytes fits int64, and the band pass's grid of one thread per key fits
+  if (R > (uint64_t)INT64_MAX / (4 * (uint64_t)K) || !shred::batch_rows_fit(R * (uint64_t)K)) return -1;
+  *m = shred::EncodeDevice::MinhashOpts{o->seed, K, w, B};
+  return 0;
+}
+}  // namespace
+
+int64_t shred_minhash_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             const ShredMinhashOpts* opts, void* sig, void* bands_out, void* stream,
+                             double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::MinhashOpts o;
+  if (minhash_args(enc, ids, n, row_off, rows, opts, sig, bands_out, &o)) return -1;
+  return enc->dev->minhash((const int32_t*)ids, n, (const int64_t*)row_off, rows, o, (uint32_t*)sig,
+                           (uint64_t*)bands_out, stream, kernel_ms);
+}
+
+int64_t shred_minhash_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           const ShredMinhashOpts* opts, uint32_t* sig, uint64_t* bands_out) {
+  shred::EncodeDevice::MinhashOpts o;
+  if (minhash_args(enc, ids, n, row_off, rows, opts, sig, bands_out, &o)) return -1;
+  if (!shred::batch_rows_fit(rows)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  const int r = enc->dev->minhash_host(ids, n, row_off, rows, o, sig, bands_out);
+  return r < 0 ? r : (int64_t)(row_off ? rows : 1);
+}
+
 }  // extern "C"

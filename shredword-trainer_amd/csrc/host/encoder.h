@@ -269,6 +269,22 @@ class EncodeDevice {
   int fim_cuts(const uint8_t* text, size_t n, const int64_t* doc_off, size_t docs, const FimOpts& o,
                int64_t* piece_off, int8_t* doc_mode, void* stream, double* kernel_ms);
 
+  // ---- MinHash signatures and LSH band keys of rows (batch_minhash.hip; shred_minhash_*).  The callers
+  // have checked the arguments' ranges: 1 <= K <= kMinhashMaxPerm, 1 <= w <= kMinhashMaxShingle, B == 0
+  // (keys == nullptr) or B divides K, and rows x K x 4 fits int64.  minhash takes device buffers and
+  // returns the rows, -1 or -6; minhash_host takes host buffers whose row_off the caller has checked on
+  // the host and returns 0 or -1.
+  static constexpr int kMinhashMaxPerm = 512;    // SHRED_MINHASH_MAX_PERM
+  static constexpr int kMinhashMaxShingle = 64;  // SHRED_MINHASH_MAX_SHINGLE
+  struct MinhashOpts {
+    uint64_t seed;
+    int K, w, B;
+  };
+  int64_t minhash(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MinhashOpts& o,
+                  uint32_t* sig, uint64_t* keys, void* stream, double* kernel_ms);
+  int minhash_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MinhashOpts& o,
+                   uint32_t* sig, uint64_t* keys);
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -310,7 +326,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kFim, kPasses };
+              kCorrupt, kFim, kMinhash, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -269,3 +269,13 @@ lib.shred_fim_rows.restype = c_int64
 lib.shred_fim_cuts_device.argtypes = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredFimOpts), c_void_p,
                                       c_void_p, c_void_p, POINTER(c_double)]
 lib.shred_fim_cuts_device.restype = c_int
+# MinHash signatures and band keys: ids, n, row_off, rows, opts, sig, bands_out
+class ShredMinhashOpts(ctypes.Structure):
+    _fields_ = [("seed", c_uint64), ("num_perm", c_int32), ("shingle", c_int32), ("bands", c_int32)]
+
+
+_minhash_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(ShredMinhashOpts), c_void_p, c_void_p]
+lib.shred_minhash_device.argtypes = _minhash_rows + [c_void_p, POINTER(c_double)]
+lib.shred_minhash_device.restype = c_int64
+lib.shred_minhash_rows.argtypes = _minhash_rows
+lib.shred_minhash_rows.restype = c_int64

@@ -14,7 +14,7 @@ import weakref
 
 import numpy as np
 
-from .cbase import ShredCorruptOpts, ShredFimOpts, ShredMlmOpts, lib
+from .cbase import ShredCorruptOpts, ShredFimOpts, ShredMinhashOpts, ShredMlmOpts, lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
@@ -33,6 +33,10 @@ BATCH_STAGE = 512
 PAIR_TRUNCATION = ("longest_first", "only_first", "only_second", "window_second")
 MLM_MAX_PROTECT = 16   # SHRED_MLM_MAX_PROTECT
 CORRUPT_MAX_SPAN = 32  # SHRED_CORRUPT_MAX_SPAN
+# batch_minhash.hip: shingle positions per workgroup (kMhTile), and the limits of K and w
+MINHASH_TILE = 2048
+MINHASH_MAX_PERM = 512     # SHRED_MINHASH_MAX_PERM
+MINHASH_MAX_SHINGLE = 64   # SHRED_MINHASH_MAX_SHINGLE
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -1262,6 +1266,74 @@ class BPEEncoder:
                            dim=1).contiguous()
         res = self.fim_device(ids, row3[0::3].contiguous(), **dict(kw, min_len=0, cuts=cuts))
         return res[:-1] + ((st,) if starts else ()) + res[-1:]
+
+    # ---- MinHash signatures and LSH band keys (include/shredword_encode.h, shred_minhash_*) -----------
+
+    @staticmethod
+    def _minhash_opts(num_perm, shingle, seed, bands):
+        """-> ShredMinhashOpts as the C ABI takes it."""
+        K, w, B = int(num_perm), int(shingle), int(bands)
+        if not 1 <= K <= MINHASH_MAX_PERM:
+            raise ValueError(f"num_perm must be in [1, {MINHASH_MAX_PERM}]")
+        if not 1 <= w <= MINHASH_MAX_SHINGLE:
+            raise ValueError(f"shingle must be in [1, {MINHASH_MAX_SHINGLE}]")
+        if B and (not 1 <= B <= K or K % B):
+            raise ValueError("bands must be 0 or divide num_perm")
+        return ShredMinhashOpts(int(seed) & (2 ** 64 - 1), K, w, B)
+
+    def minhash_rows(self, ids, row_offsets=None, *, num_perm=128, shingle=5, seed=0, bands=0):
+        """-> sig, or (sig, keys) with bands: the MinHash signatures of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row) for near-duplicate removal.  sig: uint32
+        [rows, num_perm], per permutation the minimum hash over the row's shingles of `shingle` consecutive
+        ids (a shorter row is one shingle; an empty row is all 0xFFFFFFFF), so the share of equal columns
+        of two rows estimates the Jaccard similarity of their shingle sets.  keys: uint64 [rows, bands], one
+        hash per band of num_perm / bands signature columns; two rows are LSH candidates iff they share a
+        key in some column (all empty rows do: filter by length).  The result is a function of (seed,
+        num_perm, shingle, bands) and the row's ids alone.  Built on the GPU."""
+        opts = self._minhash_opts(num_perm, shingle, seed, bands)
+        a, row, R = self._host_rows(ids, row_offsets)
+        sig = np.empty((R, opts.num_perm), dtype=np.uint32)
+        keys = np.empty((R, opts.bands), dtype=np.uint64) if opts.bands else None
+        self._check_batch(lib.shred_minhash_rows(
+            self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data, 0 if row is None else R,
+            ctypes.byref(opts), sig.ctypes.data, None if keys is None else keys.ctypes.data))
+        return (sig, keys) if opts.bands else sig
+
+    def minhash_device(self, ids, row_offsets=None, *, num_perm=128, shingle=5, seed=0, bands=0, stream=None):
+        """minhash_rows on device tensors (ids 1-D int32, row_offsets 1-D int64, on the encoder's GPU; views
+        that are only element-aligned fit) -> (sig[, keys], device milliseconds of the passes): sig int32
+        [rows, num_perm] holding the uint32 bit patterns, keys int64 [rows, bands] holding the uint64 ones."""
+        import torch
+        opts = self._minhash_opts(num_perm, shingle, seed, bands)
+        R = self._device_rows(ids, row_offsets)
+        sig = torch.empty((R, opts.num_perm), dtype=torch.int32, device=ids.device)
+        keys = torch.empty((R, opts.bands), dtype=torch.int64, device=ids.device) if opts.bands else None
+        ms = ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        self._check_batch(lib.shred_minhash_device(
+            self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
+            0 if row_offsets is None else R, ctypes.byref(opts), sig.data_ptr(),
+            None if keys is None else keys.data_ptr(), st, ctypes.byref(ms)))
+        return ((sig, keys) if opts.bands else (sig,)) + (ms.value,)
+
+    def encode_minhash(self, text, *, doc_offsets=None, specials: bool = False, **kw):
+        """Text to signatures without leaving the GPU: encode_docs_device, then minhash_device(**kw) on its
+        rows -> (ids, row_offsets, sig[, keys]) as host arrays (sig uint32, keys uint64).  text: a list /
+        tuple of documents, or one text with doc_offsets (None: one document)."""
+        import torch
+        if isinstance(text, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(text)
+        else:
+            buf = self._host_text(text)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        ids, row = self.encode_docs_device(dev(buf), None if off is None else dev(off), specials=specials)[:2]
+        res = self.minhash_device(ids, row, **kw)[:-1]
+        host = lambda t, dt: t.cpu().numpy().view(dt)
+        return (host(ids, np.int32), host(row, np.int64), host(res[0], np.uint32)) \
+            + ((host(res[1], np.uint64),) if len(res) > 1 else ())
 
     def destroy(self):
         if getattr(self, "enc", None):

@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -43,7 +43,13 @@ scatters for both streams, the offsets and the closing sentinels); with a traili
 rows (fim_rate = spm_rate = 0.5, with out_src, out_seg and row_info): device ms (median of 7 after two warm-up calls) and
 GB/s by the traffic model of batch_fim.hip, beside a torch composition of the same definition on the same tensors in the
 same process (the per-row draws by the same hash in int64 arithmetic, a cumsum for the output offsets, bucketize for every
-output position's row, where for its source index and one gather); the two results must be equal, or the leg fails."""
+output position's row, where for its source index and one gather); the two results must be equal, or the leg fails; with a
+trailing `minhash`, minhash_device on the same ids and rows (128 permutations, shingles of 5, 16 bands): device ms (median
+of 7 after two warm-up calls), shingle x permutation evaluations per second and bytes read per second, beside a torch
+composition of the same definition (shifted views for the shingle hash, the [positions, K] table of values, a scatter-min
+per row, the keys from the signatures).  That table is 32 GiB for all ids, so the composition runs on the largest prefix
+of the rows for which it fits 4 GiB, must equal minhash_device there, and its time is scaled by the id count: an
+extrapolation, printed as one."""
 import os
 import subprocess
 import sys
@@ -85,7 +91,9 @@ else:
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
     long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
-    mlm = corrupt or fim or args[-1] == "mlm"  # the corrupt and fim legs run on the mlm leg's stream, in its place
+    minhash = args[-1] == "minhash"
+    # the corrupt, fim and minhash legs run on the mlm leg's stream, in its place
+    mlm = corrupt or fim or minhash or args[-1] == "mlm"
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -462,7 +470,7 @@ else:
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
         legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
-        for name, whole, per_id, ref in () if corrupt or fim else legs:
+        for name, whole, per_id, ref in () if corrupt or fim or minhash else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -475,6 +483,17 @@ else:
                   "| ms", med, "GB/s at", per_id, "B per id", per_id * n / med / 1e6, "min", ms[0], "max", ms[-1],
                   "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1], "max", t[2],
                   "selected share", picked / n, "| torch / ours", t[0] / med, flush=True)
+    # the draw hash of the fim and minhash legs in torch's int64 arithmetic
+    s64 = lambda v: v - (1 << 64) if v >= 1 << 63 else v           # a uint64 constant as torch's int64 holds it
+    lsr = lambda x, s: (x >> s) & ((1 << (64 - s)) - 1)            # the logical shift of a uint64
+
+    def tmix(x):
+        x = x ^ lsr(x, 33)
+        x = x * s64(0xff51afd7ed558ccd)
+        x = x ^ lsr(x, 33)
+        x = x * s64(0xc4ceb9fe1a85ec53)
+        return x ^ lsr(x, 33)
+
     if corrupt:
         del starts
         import math
@@ -532,15 +551,6 @@ else:
     if fim:
         del starts
         R, SEED, PRE, SUF, MID = row.numel() - 1, 1, V, V + 1, V + 2
-        s64 = lambda v: v - (1 << 64) if v >= 1 << 63 else v           # a uint64 constant as torch's int64 holds it
-        lsr = lambda x, s: (x >> s) & ((1 << (64 - s)) - 1)            # the logical shift of a uint64
-
-        def tmix(x):
-            x = x ^ lsr(x, 33)
-            x = x * s64(0xff51afd7ed558ccd)
-            x = x ^ lsr(x, 33)
-            x = x * s64(0xc4ceb9fe1a85ec53)
-            return x ^ lsr(x, 33)
 
         def draw(h, c):
             return lsr(tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (h + 1)) ^ c), 32)
@@ -593,4 +603,55 @@ else:
               "min", ms[0], "max", ms[-1], "| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0],
               "min", t[1], "max", t[2], "| equal to the torch composition", same, "| torch / ours", t[0] / med, flush=True)
         assert same, "fim_device and the torch composition of the same definition differ"
+    if minhash:
+        del starts
+        R, SEED, K, W, B = row.numel() - 1, 1, 128, 5, 16
+        mdraw = lambda x, c: tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (x + 1)) ^ c)
+
+        def torch_minhash(t_ids, t_row):
+            """the header's definition on rows of at least W ids: the shingle hash of every position by W
+            shifted views, the [positions, K] table of values, masked where no shingle starts, a scatter-min
+            per row, and the band keys from the signatures"""
+            cnt, rows = t_ids.numel() - W + 1, t_row.numel() - 1
+            t = t_ids.long() & 0xFFFFFFFF
+            h = mdraw(torch.full((cnt,), W, device=t.device), (1 << 40) + 8)
+            for j in range(W):
+                h = tmix(h ^ t[j:j + cnt])
+            p = torch.arange(cnt, device=t.device)
+            r = torch.bucketize(p, t_row, right=True) - 1
+            i = torch.arange(K, device=t.device)
+            a, b = mdraw(i, (1 << 40) + 9) | 1, mdraw(i, (1 << 40) + 10)
+            v = lsr(a[None, :] * lsr(h, 32)[:, None] + b[None, :], 32)
+            v = torch.where((p + W <= t_row[r + 1])[:, None], v, 0xFFFFFFFF)
+            sig = torch.full((rows, K), 0xFFFFFFFF, dtype=torch.int64, device=t.device)
+            sig.scatter_reduce_(0, r[:, None].expand(-1, K), v, "amin")
+            g = mdraw(torch.arange(B, device=t.device), (1 << 40) + 11)[None, :].expand(rows, -1)
+            for k in range(K // B):
+                g = tmix(g ^ sig[:, k::K // B])
+            return sig, g
+
+        run = lambda: enc.minhash_device(ids, row, num_perm=K, shingle=W, seed=SEED, bands=B)
+        run()  # first call: allocates the MinHash scratch
+        run()
+        res = [run() for _ in range(reps)]
+        ms = sorted(r[2] for r in res)
+        med = ms[len(ms) // 2]
+        c = events(run)
+        # the composition's [positions, K] int64 table must fit 4 GiB: the largest prefix of whole rows
+        Rp = int(torch.searchsorted(row, (4 << 30) // (8 * K), right=True).item()) - 1
+        p_row = row[:Rp + 1].contiguous()
+        p_ids = ids[:int(p_row[-1].item())]
+        ref = torch_minhash(p_ids, p_row)
+        same = torch.equal(res[0][0][:Rp].long() & 0xFFFFFFFF, ref[0]) and torch.equal(res[0][1][:Rp], ref[1])
+        t = events(lambda: torch_minhash(p_ids, p_row))
+        scale = n / p_ids.numel()
+        shingles = n - (W - 1) * R
+        print("minhash: ids", n, "rows", R, "K", K, "w", W, "bands", B, "| ms", med, "min", ms[0], "max", ms[-1],
+              "| shingle x permutation evaluations/s", shingles * K / med * 1e3, "| bytes read/s (4 B per id, 8 B per row)",
+              (4 * n + 8 * R) / med * 1e3, "| whole call (allocation, passes) ms", c[0],
+              "| torch composition on the first", Rp, "rows,", p_ids.numel(), "ids: ms", t[0], "min", t[1], "max", t[2],
+              "| equal to the torch composition on those rows", same,
+              "| EXTRAPOLATED to all ids by the id count (x", scale, "): torch ms", t[0] * scale,
+              "| extrapolated torch / ours", t[0] * scale / med, flush=True)
+        assert same, "minhash_device and the torch composition of the same definition differ"
     enc.destroy()
