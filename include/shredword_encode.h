@@ -970,6 +970,78 @@ int64_t shred_minhash_device(ShredEncoder* enc, const void* ids, size_t n, const
 int64_t shred_minhash_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
                            const ShredMinhashOpts* opts, uint32_t* sig, uint64_t* bands_out);
 
+/* ---- Near-duplicate clusters and a keep mask from signatures and band keys, on the GPU -----------------
+ *
+ * The step behind shred_minhash_*: which rows to drop.  The inputs are that pair's row-major outputs, or
+ * any arrays of their shape.
+ *
+ * Inputs:
+ *   sig         R x K uint32.  Read only when min_equal > 0; may be NULL otherwise.
+ *   keys        R x B uint64.  Every 64-bit value is a key like any other.
+ *   rows        R <= 2^31 - 1.
+ *   opts        ShredDedupOpts below:
+ *     num_perm  K, 1 <= K <= SHRED_MINHASH_MAX_PERM.
+ *     bands     B, 1 <= B <= SHRED_DEDUP_MAX_BANDS (B need not divide K here).
+ *     min_equal 0 <= min_equal <= K: the equal signature columns an edge needs; 0 for no verification.
+ *
+ * Definitions.
+ *   Bucket.   The bucket of cell (r, j) is the set of rows r' with keys[r', j] == keys[r, j]: equality on
+ *             all 64 bits, within band j only (the same value in two bands joins nothing).  rep(r, j) is
+ *             the smallest row index in that bucket.
+ *   Edge.     r -- rep(r, j) iff rep(r, j) != r and, when min_equal > 0, the number of columns i with
+ *             sig[r, i] == sig[rep(r, j), i] is >= min_equal.
+ *   Every row is verified against its bucket's first row only, so the work is linear in R x B whatever
+ *   the bucket sizes.  With min_equal == 0 the components are exactly those of "any two rows that share
+ *   a key in a band".  With min_equal > 0 recall has a limit: a bucket whose first row is a false
+ *   positive (it shares the key, not the content) links nobody in that band; real duplicates meet again
+ *   in other bands, which is what the bands are for.
+ *
+ * Outputs:
+ *   label       R int64: label[r] is the smallest row index in r's connected component.  Must not be NULL.
+ *   keep        R uint8, may be NULL: keep[r] = (label[r] == r), one row kept per component.
+ * Returns the number of components, which is the number of rows kept.  R == 0 returns 0 and touches
+ * nothing (every array may then be NULL).  Errors, with nothing written: -1 for a bad option, label NULL,
+ * sig NULL with min_equal > 0, rows past the limit, or an allocation or HIP error.
+ *
+ * The result is a function of (sig, keys, K, B, min_equal) alone: there is no seed, and it does not
+ * depend on the order in which the device takes the cells, on how the bands are grouped or on host
+ * versus device call.  All empty rows share every key and so form one cluster: callers filter by
+ * length, as above.
+ *
+ * The dedup scratch is allocated on the first dedup call and freed with the encoder: 4 R bytes of
+ * union-find and the bucket tables of one group of bands, 12 bytes x the power of two >= 2 R per band of
+ * the group.  The bands are taken in groups whose tables fit 256 MiB (at least one band at a time), so
+ * the scratch is O(R), not O(R B); SHREDWORD_DEDUP_GROUP caps the bands per group (tests).
+ */
+#define SHRED_DEDUP_MAX_BANDS 128
+
+typedef struct ShredDedupOpts {
+  int32_t num_perm;
+  int32_t bands;
+  int32_t min_equal;
+} ShredDedupOpts;
+
+/* All buffers on the encoder's device; queued on `stream` (NULL = the encoder's own) and synchronised
+ * before return.  Every buffer needs only its element's alignment, so tensor views fit (signature rows
+ * that are 16-byte aligned are read 16 bytes at a time).  kernel_ms (may be NULL) receives the device
+ * time of the passes. */
+int64_t shred_dedup_device(ShredEncoder* enc, const void* sig, const void* keys, size_t rows,
+                           const ShredDedupOpts* opts, void* label, void* keep, void* stream, double* kernel_ms);
+
+/* Host buffers.  Clustering is global, so this call has no pieces: keys (and sig when it is read) are
+ * uploaded whole, the device passes run once, label and keep are copied back; -1 with a message when
+ * that does not fit the device. */
+int64_t shred_dedup_rows(ShredEncoder* enc, const uint32_t* sig, const uint64_t* keys, size_t rows,
+                         const ShredDedupOpts* opts, int64_t* label, uint8_t* keep);
+
+/* What the dedup passes hold and what the last dedup call did (each pointer may be NULL): the bytes of
+ * device scratch (union-find and tables; 0 before the first call), the call's edges (cells whose bucket
+ * has an earlier row), the edges dropped unverified because both ends already shared a root (this count
+ * depends on the order in which the device took the cells; the result does not) and the edges accepted.
+ * Returns 0, -1 for NULL. */
+int shred_encoder_dedup_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* edges, uint64_t* dropped,
+                              uint64_t* accepted);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -820,4 +820,43 @@ int64_t shred_minhash_rows(ShredEncoder* enc, const int32_t* ids, size_t n, cons
   return r < 0 ? r : (int64_t)(row_off ? rows : 1);
 }
 
+namespace {
+// What the two dedup calls refuse before any work (0 or -1), and their options.
+int dedup_args(const ShredEncoder* enc, const void* sig, const void* keys, size_t rows, const ShredDedupOpts* o,
+               const void* label, shred::EncodeDevice::DedupOpts* d) {
+  if (!enc || !o) return -1;
+  const int32_t K = o->num_perm, B = o->bands, m = o->min_equal;
+  if (K < 1 || K > SHRED_MINHASH_MAX_PERM || B < 1 || B > SHRED_DEDUP_MAX_BANDS || m < 0 || m > K) return -1;
+  // arrays of no rows hold nothing: an empty tensor's NULL fits
+  if (rows > shred::EncodeDevice::kDedupMaxRows || (rows && (!label || !keys || (m > 0 && !sig)))) return -1;
+  *d = shred::EncodeDevice::DedupOpts{K, B, m};
+  return 0;
+}
+}  // namespace
+
+int64_t shred_dedup_device(ShredEncoder* enc, const void* sig, const void* keys, size_t rows,
+                           const ShredDedupOpts* opts, void* label, void* keep, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::DedupOpts o;
+  if (dedup_args(enc, sig, keys, rows, opts, label, &o)) return -1;
+  if (!rows) return 0;
+  return enc->dev->dedup((const uint32_t*)sig, (const uint64_t*)keys, rows, o, (int64_t*)label, (uint8_t*)keep, stream,
+                         kernel_ms);
+}
+
+int64_t shred_dedup_rows(ShredEncoder* enc, const uint32_t* sig, const uint64_t* keys, size_t rows,
+                         const ShredDedupOpts* opts, int64_t* label, uint8_t* keep) {
+  shred::EncodeDevice::DedupOpts o;
+  if (dedup_args(enc, sig, keys, rows, opts, label, &o)) return -1;
+  if (!rows) return 0;
+  return enc->dev->dedup_host(sig, keys, rows, o, label, keep);
+}
+
+int shred_encoder_dedup_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* edges, uint64_t* dropped,
+                              uint64_t* accepted) {
+  if (!enc) return -1;
+  enc->dev->dedup_stats(scratch_bytes, edges, dropped, accepted);
+  return 0;
+}
+
 }  // extern "C"

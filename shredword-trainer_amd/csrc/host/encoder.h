@@ -285,6 +285,23 @@ class EncodeDevice {
   int minhash_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const MinhashOpts& o,
                    uint32_t* sig, uint64_t* keys);
 
+  // ---- near-duplicate clusters from signatures and band keys (batch_dedup.hip; shred_dedup_*).  The
+  // callers have checked the arguments' ranges: 1 <= rows <= kDedupMaxRows, 1 <= K <= kMinhashMaxPerm,
+  // 1 <= B <= kDedupMaxBands, 0 <= min_equal <= K, sig given when min_equal > 0, label given (keep may be
+  // nullptr).  dedup takes device buffers, dedup_host host buffers; both return the number of components or -1.
+  static constexpr int kDedupMaxBands = 128;
+  static constexpr uint64_t kDedupMaxRows = 0x7FFFFFFFull;
+  struct DedupOpts {
+    int K, B, min_equal;
+  };
+  int64_t dedup(const uint32_t* sig, const uint64_t* keys, size_t rows, const DedupOpts& o, int64_t* label,
+                uint8_t* keep, void* stream, double* kernel_ms);
+  int64_t dedup_host(const uint32_t* sig, const uint64_t* keys, size_t rows, const DedupOpts& o, int64_t* label,
+                     uint8_t* keep);
+  // What the dedup passes hold (bytes of union-find and tables) and what the last call did: its edges
+  // (cells whose bucket has an earlier row), those the same-root tests dropped, those accepted.
+  void dedup_stats(uint64_t* scratch_bytes, uint64_t* edges, uint64_t* dropped, uint64_t* accepted) const;
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -326,7 +343,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kFim, kMinhash, kPasses };
+              kCorrupt, kFim, kMinhash, kDedup, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

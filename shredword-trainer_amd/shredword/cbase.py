@@ -279,3 +279,15 @@ lib.shred_minhash_device.argtypes = _minhash_rows + [c_void_p, POINTER(c_double)
 lib.shred_minhash_device.restype = c_int64
 lib.shred_minhash_rows.argtypes = _minhash_rows
 lib.shred_minhash_rows.restype = c_int64
+# near-duplicate clusters: sig, keys, rows, opts, label, keep
+class ShredDedupOpts(ctypes.Structure):
+    _fields_ = [("num_perm", c_int32), ("bands", c_int32), ("min_equal", c_int32)]
+
+
+_dedup_rows = [Encoder, c_void_p, c_void_p, c_size_t, POINTER(ShredDedupOpts), c_void_p, c_void_p]
+lib.shred_dedup_device.argtypes = _dedup_rows + [c_void_p, POINTER(c_double)]
+lib.shred_dedup_device.restype = c_int64
+lib.shred_dedup_rows.argtypes = _dedup_rows
+lib.shred_dedup_rows.restype = c_int64
+lib.shred_encoder_dedup_stats.argtypes = [Encoder] + [POINTER(c_uint64)] * 4
+lib.shred_encoder_dedup_stats.restype = c_int

@@ -10,11 +10,12 @@ frequencies.  Every call runs the gfx950 kernels through libtrainer.so; there is
 """
 import atexit
 import ctypes
+import math
 import weakref
 
 import numpy as np
 
-from .cbase import ShredCorruptOpts, ShredFimOpts, ShredMinhashOpts, ShredMlmOpts, lib
+from .cbase import ShredCorruptOpts, ShredDedupOpts, ShredFimOpts, ShredMinhashOpts, ShredMlmOpts, lib
 
 MAX_WORD = 1024  # SHRED_ENCODE_MAX_WORD
 MAX_LONG_WORD = 1 << 20  # SHRED_ENCODE_MAX_LONG_WORD
@@ -37,6 +38,7 @@ CORRUPT_MAX_SPAN = 32  # SHRED_CORRUPT_MAX_SPAN
 MINHASH_TILE = 2048
 MINHASH_MAX_PERM = 512     # SHRED_MINHASH_MAX_PERM
 MINHASH_MAX_SHINGLE = 64   # SHRED_MINHASH_MAX_SHINGLE
+DEDUP_MAX_BANDS = 128      # SHRED_DEDUP_MAX_BANDS
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -1334,6 +1336,90 @@ class BPEEncoder:
         host = lambda t, dt: t.cpu().numpy().view(dt)
         return (host(ids, np.int32), host(row, np.int64), host(res[0], np.uint32)) \
             + ((host(res[1], np.uint64),) if len(res) > 1 else ())
+
+    # ---- near-duplicate clusters from signatures and band keys (include/shredword_encode.h, shred_dedup_*) ----
+
+    @staticmethod
+    def _dedup_opts(shape_sig, shape_keys, threshold, min_equal):
+        """-> ShredDedupOpts from the arrays' shapes ([rows, K] and [rows, B]) and the threshold."""
+        if len(shape_sig) != 2 or len(shape_keys) != 2 or shape_sig[0] != shape_keys[0]:
+            raise ValueError("sig must be [rows, num_perm] and keys [rows, bands] of the same rows")
+        K, B = int(shape_sig[1]), int(shape_keys[1])
+        if not 1 <= K <= MINHASH_MAX_PERM or not 1 <= B <= DEDUP_MAX_BANDS:
+            raise ValueError(f"num_perm must be in [1, {MINHASH_MAX_PERM}] and bands in [1, {DEDUP_MAX_BANDS}]")
+        if min_equal is None:
+            if not 0.0 <= threshold <= 1.0:
+                raise ValueError("threshold must be in [0, 1]")
+            min_equal = math.ceil(threshold * K)
+        if not 0 <= int(min_equal) <= K:
+            raise ValueError("min_equal must be in [0, num_perm]")
+        return ShredDedupOpts(K, B, int(min_equal))
+
+    def dedup_rows(self, sig, keys, *, threshold=0.0, min_equal=None):
+        """-> (labels int64 [rows], keep bool [rows], kept): the near-duplicate clusters of the rows whose
+        signatures (uint32 / int32 [rows, num_perm]) and band keys (uint64 / int64 [rows, bands]) minhash_rows
+        returned.  Rows that share a key in a band are candidates; each is verified against the first row of
+        its bucket and linked to it when at least min_equal signature columns are equal (default
+        ceil(threshold * num_perm), threshold an estimate of the Jaccard similarity; 0 links every candidate).
+        labels[r] is the smallest row of r's connected component, keep[r] = labels[r] == r, kept their count:
+        ids rows are dropped by indexing with keep.  All empty rows form one cluster: filter by length.
+        Built on the GPU."""
+        sig, keys = np.ascontiguousarray(sig), np.ascontiguousarray(keys)
+        if sig.dtype not in (np.int32, np.uint32) or keys.dtype not in (np.int64, np.uint64):
+            raise ValueError("sig must be int32 / uint32 and keys int64 / uint64")
+        opts = self._dedup_opts(sig.shape, keys.shape, threshold, min_equal)
+        labels, keep = np.empty(sig.shape[0], dtype=np.int64), np.empty(sig.shape[0], dtype=np.uint8)
+        kept = self._check_batch(lib.shred_dedup_rows(self.enc, sig.ctypes.data, keys.ctypes.data, sig.shape[0],
+                                                      ctypes.byref(opts), labels.ctypes.data, keep.ctypes.data))
+        return labels, keep.view(np.bool_), kept
+
+    def dedup_device(self, sig, keys, *, threshold=0.0, min_equal=None, stream=None):
+        """dedup_rows on device tensors as minhash_device returns them (sig int32 / uint32, keys int64 / uint64,
+        contiguous, on the encoder's GPU) -> (labels int64, keep bool, kept, device milliseconds of the passes)."""
+        import torch
+        for name, t, dts in (("sig", sig, ("int32", "uint32")), ("keys", keys, ("int64", "uint64"))):
+            if not isinstance(t, torch.Tensor) or str(t.dtype).split(".")[-1] not in dts or not t.is_cuda \
+                    or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {' / '.join(dts)} CUDA tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the encoder on cuda:{self.device}")
+        opts = self._dedup_opts(tuple(sig.shape), tuple(keys.shape), threshold, min_equal)
+        R = sig.shape[0]
+        labels = torch.empty(R, dtype=torch.int64, device=sig.device)
+        keep = torch.empty(R, dtype=torch.bool, device=sig.device)
+        ms = ctypes.c_double()
+        st = self._stream(stream, sig.device)
+        kept = self._check_batch(lib.shred_dedup_device(self.enc, sig.data_ptr(), keys.data_ptr(), R, ctypes.byref(opts),
+                                                        labels.data_ptr(), keep.data_ptr(), st, ctypes.byref(ms)))
+        return labels, keep, kept, ms.value
+
+    @property
+    def dedup_stats(self) -> dict:
+        """The dedup passes: scratch_bytes they hold on the device (0 before the first call) and, of the last
+        call, its edges (cells whose bucket has an earlier row), those dropped unverified because both ends
+        already shared a root, and those accepted."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        lib.shred_encoder_dedup_stats(self.enc, *(ctypes.byref(x) for x in v))
+        return dict(zip(("scratch_bytes", "edges", "dropped", "accepted"), (x.value for x in v)))
+
+    def encode_dedup(self, text, *, doc_offsets=None, specials: bool = False, num_perm=128, shingle=5, seed=0,
+                     bands=16, threshold=0.0):
+        """Text to clusters without the signatures leaving the GPU: encode_docs_device, minhash_device and
+        dedup_device on its rows -> (ids, row_offsets, labels, keep) as host arrays.  text: a list / tuple
+        of documents, or one text with doc_offsets (None: one document)."""
+        import torch
+        if isinstance(text, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(text)
+        else:
+            buf = self._host_text(text)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        ids, row = self.encode_docs_device(dev(buf), None if off is None else dev(off), specials=specials)[:2]
+        sig, keys, _ = self.minhash_device(ids, row, num_perm=num_perm, shingle=shingle, seed=seed, bands=bands)
+        labels, keep = self.dedup_device(sig, keys, threshold=threshold)[:2]
+        return tuple(t.cpu().numpy() for t in (ids, row, labels, keep))
 
     def destroy(self):
         if getattr(self, "enc", None):

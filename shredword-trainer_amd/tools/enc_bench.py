@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -49,7 +49,14 @@ of 7 after two warm-up calls), shingle x permutation evaluations per second and 
 composition of the same definition (shifted views for the shingle hash, the [positions, K] table of values, a scatter-min
 per row, the keys from the signatures).  That table is 32 GiB for all ids, so the composition runs on the largest prefix
 of the rows for which it fits 4 GiB, must equal minhash_device there, and its time is scaled by the id count: an
-extrapolation, printed as one."""
+extrapolation, printed as one; with a trailing `dedup`, the minhash leg and then dedup_device on the signatures and keys
+of the same rows after 20 % of them were replaced by a copy of a row that stays (every other copy with 2 % of its ids
+changed; without copies the corpus has next to no edges): for min_equal 0 and num_perm / 2, device ms (median of 7 after
+two warm-up calls), cells per second, the edges, those dropped by the same-root tests and those accepted, and the
+clusters, for the row-major (the default) and the band-major cell order and for one edge per wave instead of per lane group
+(SHREDWORD_DEDUP_ORDER, SHREDWORD_DEDUP_LANES), beside a torch composition of the same definition on the same tensors
+(unique and a scatter-amin per band, the column count, min-label propagation with pointer jumping to a fixpoint), which
+must give equal labels."""
 import os
 import subprocess
 import sys
@@ -91,7 +98,8 @@ else:
     decode = batch or args[-1] == "decode"
     special, docs, window = args[-1] == "special", args[-1] == "docs", args[-1] == "window"
     long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
-    minhash = args[-1] == "minhash"
+    dedup = args[-1] == "dedup"
+    minhash = dedup or args[-1] == "minhash"  # the dedup leg runs behind the minhash leg, on its rows
     # the corrupt, fim and minhash legs run on the mlm leg's stream, in its place
     mlm = corrupt or fim or minhash or args[-1] == "mlm"
     if spans or decode or special or docs or window or long_leg or pair or mlm:
@@ -654,4 +662,74 @@ else:
               "| EXTRAPOLATED to all ids by the id count (x", scale, "): torch ms", t[0] * scale,
               "| extrapolated torch / ours", t[0] * scale / med, flush=True)
         assert same, "minhash_device and the torch composition of the same definition differ"
+    if dedup:
+        SHARE = 0.2
+        g = torch.Generator().manual_seed(11)
+        dup = torch.randperm(R, generator=g)[:int(SHARE * R)].cuda()          # the rows replaced
+        src = torch.arange(R, device="cuda")
+        rest = torch.ones(R, dtype=torch.bool, device="cuda")
+        rest[dup] = False
+        rest = rest.nonzero().squeeze(1)                                       # by the row it copies, one that stays
+        src[dup] = rest[torch.randint(0, rest.numel(), (dup.numel(),), generator=g).cuda()]
+        lens = (row[1:] - row[:-1])[src]
+        d_row = torch.cat([lens.new_zeros(1), lens.cumsum(0)])
+        total = int(d_row[-1].item())
+        col = torch.arange(total, device="cuda") - torch.repeat_interleave(d_row[:-1], lens, output_size=total)
+        d_ids = ids[torch.repeat_interleave(row[:-1][src], lens, output_size=total) + col]
+        near = torch.zeros(R, dtype=torch.bool, device="cuda")
+        near[dup[::2]] = True                                                  # every other copy is a near-copy:
+        hit = torch.repeat_interleave(near, lens, output_size=total) & (torch.rand(total, generator=g) < 0.02).cuda()
+        d_ids = torch.where(hit, torch.randint(5, V, (total,), generator=g, dtype=torch.int32).cuda(), d_ids)
+        del col, hit
+        sig, keys, _ = enc.minhash_device(d_ids, d_row, num_perm=K, shingle=W, seed=SEED, bands=B)
+        ar = torch.arange(R, device="cuda")
+
+        def torch_dedup(m):
+            """the header's definition: per band unique and a scatter-amin for rep, the column count against
+            the rep's row, then min-label propagation over the edges with pointer jumping to a fixpoint"""
+            ea, eb = [], []
+            for j in range(B):
+                inv = torch.unique(keys[:, j], return_inverse=True)[1]
+                first = torch.full((int(inv.max().item()) + 1,), R, device="cuda").scatter_reduce_(0, inv, ar, "amin")
+                rep = first[inv]
+                cand = rep != ar
+                if m:
+                    cand &= (sig == sig[rep]).sum(dim=1) >= m
+                ea.append(ar[cand])
+                eb.append(rep[cand])
+            ea, eb = torch.cat(ea), torch.cat(eb)
+            label = ar.clone()
+            while True:
+                la, lb = label[ea], label[eb]
+                mn = torch.minimum(la, lb)
+                new = label.clone()
+                for at in (la, lb, ea, eb):
+                    new.scatter_reduce_(0, at, mn, "amin")
+                new = new[new]
+                if torch.equal(new, label):
+                    return label
+                label = new
+
+        for order, lanes in (("row", "group"), ("band", "group"), ("row", "wave")):
+            os.environ["SHREDWORD_DEDUP_ORDER"], os.environ["SHREDWORD_DEDUP_LANES"] = order, lanes
+            for m in (0, K // 2):
+                run = lambda: enc.dedup_device(sig, keys, min_equal=m)
+                run()  # first call: allocates the dedup scratch
+                run()
+                res = [run() for _ in range(reps)]
+                ms = sorted(r[3] for r in res)
+                med, st = ms[len(ms) // 2], enc.dedup_stats
+                line = ("dedup: rows", R, "K", K, "bands", B, "rows replaced by a copy", dup.numel(), "share", SHARE,
+                        "(half of them with 2 % of the ids changed)", "| cell order", order, "| lanes per edge", lanes,
+                        "| min_equal", m, "| ms", med, "min", ms[0], "max", ms[-1], "| cells/s", R * B / med * 1e3,
+                        "| edges", st["edges"], "dropped by the same-root tests", st["dropped"], "accepted",
+                        st["accepted"], "| clusters", res[0][2], "| scratch bytes", st["scratch_bytes"])
+                if (order, lanes) == ("row", "group"):  # the library's defaults
+                    c, t = events(run), events(lambda: torch_dedup(m))
+                    same = torch.equal(res[0][0], torch_dedup(m))
+                    line += ("| whole call (allocation, passes) ms", c[0], "| torch composition ms", t[0], "min", t[1],
+                             "max", t[2], "| equal labels", same, "| torch / ours", t[0] / med)
+                    assert same, "dedup_device and the torch composition of the same definition differ"
+                print(*line, flush=True)
+        del os.environ["SHREDWORD_DEDUP_ORDER"], os.environ["SHREDWORD_DEDUP_LANES"]
     enc.destroy()
