@@ -1042,6 +1042,84 @@ int64_t shred_dedup_rows(ShredEncoder* enc, const uint32_t* sig, const uint64_t*
 int shred_encoder_dedup_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, uint64_t* edges, uint64_t* dropped,
                               uint64_t* accepted);
 
+/* ---- n-gram overlap of rows with a held-out reference set, on the GPU (benchmark decontamination) ------
+ *
+ * The n-gram test of GPT-3 (13-grams) and of PaLM / Llama 2 (a token counts as contaminated when it lies in
+ * a matching n-gram), between "encoded" and "batched": which rows of the corpus hold a run of w consecutive
+ * ids that also occurs in a fixed set of held-out rows (evaluation data), where, and how many of their
+ * tokens such runs cover.  The reference set is registered with the encoder once and stays until it is
+ * replaced or the encoder is destroyed; the corpus calls work on the flat (ids, row_off) pair.
+ *
+ * Definitions.  mix, G and d(x, c) are those of the masked-LM section; the constants are
+ * NGRAM = (1 << 40) + 12 and MULT = (1 << 40) + 13, beside BAND of MinHash.  All arithmetic is mod 2^64.  An
+ * id enters as its 32-bit pattern, zero-extended, as in MinHash; ids are never looked up.
+ *   g(t) = d(t, NGRAM),  A = d(w, MULT) | 1.
+ *   The w-gram at position k of a stream exists iff k and k + w - 1 lie in the same row.  A row shorter than
+ *             w has none: unlike MinHash, which hashes a short row as one shingle, a short row can neither
+ *             hit nor be hit.  No gram crosses a row.
+ *   S(k) = the sum over j in [0, w) of A^(w-1-j) * g(t[k+j]);  F(k) = mix(S(k)), with the value 2^64 - 1
+ *             replaced by 2^64 - 2 (the all-ones pattern marks a free table slot).
+ *   Reference set: ref_ids (m int32, m <= 2^31 - 1) with ref_row_off in the usual format (NULL with 0 rows:
+ *             one row), 1 <= w <= SHRED_OVERLAP_MAX_NGRAM and a 64-bit seed.  P(f) is the smallest position
+ *             in ref_ids whose gram has fingerprint f.
+ *   Hit:      position k of the corpus stream is a hit iff its gram exists and F(k) is the fingerprint of some
+ *             reference gram.  Equality is on all 64 bits of F, not on the ids: two different grams share a
+ *             fingerprint with probability about 2^-64, so a call sees a false hit with probability about
+ *             (corpus grams x distinct reference grams) / 2^64; tok_ref gives the reference position, so a
+ *             caller who needs certainty compares the w ids.
+ *   Covered:  token j is covered iff some hit k has k <= j < k + w.  A hit's tokens all lie in its row.
+ *
+ * Outputs of a corpus call (ids: n int32; row_off: rows + 1 int64, or NULL with rows == 0 for one row,
+ * validated as elsewhere; R is the number of rows):
+ *   hits      R int64, required: the hit positions in row r.
+ *   covered   R int64, may be NULL: the covered tokens of row r.
+ *   first     R int64, may be NULL: the index in ids of the row's first hit, -1 for none.
+ *   tok_ref   n int64, may be NULL: P(F(k)) for a hit k, else -1.  The benchmark row is found by a search of
+ *             ref_row_off.
+ *   tok_cov   n uint8, may be NULL: 1 iff token j is covered.
+ * Returns the number of rows with at least one hit.  With no reference set registered, or one without
+ * grams, every row has 0 hits (a legal call).  With R == 0 nothing is touched.  Errors write nothing: -1 for
+ * a bad argument (hits NULL) or a HIP or allocation error, -6 for a bad row_off.  (A HIP error after the first
+ * piece of shred_overlap_rows leaves the earlier pieces' output in place.)
+ *
+ * The result is a function of (seed, w, the reference set, the row's ids) alone, not of where the row lies
+ * in the stream or of how a host call was staged: host and device calls, and every piece size, agree.
+ *
+ * The table of a reference set of m ids takes 12 bytes x the power of two >= 2 m on the device; the other
+ * overlap scratch (result words, events, the host calls' staging) is allocated on the first overlap call.
+ */
+#define SHRED_OVERLAP_MAX_NGRAM 64
+
+/* Registers the reference set from host buffers, replacing the encoder's previous one; m == 0 clears it.
+ * Returns the number of reference grams; -1 (w out of range, m past the limit, a HIP or allocation error)
+ * or -6 (bad ref_row_off), with the previous set kept. */
+int64_t shred_overlap_refs(ShredEncoder* enc, const int32_t* ref_ids, size_t m, const int64_t* ref_row_off,
+                           size_t ref_rows, int32_t w, uint64_t seed);
+
+/* The same from buffers on the encoder's device (ref_row_off is validated there); queued on `stream`
+ * (NULL = the encoder's own) and synchronised before return.  kernel_ms (may be NULL) receives the
+ * device time of the passes. */
+int64_t shred_overlap_refs_device(ShredEncoder* enc, const void* ref_ids, size_t m, const void* ref_row_off,
+                                  size_t ref_rows, int32_t w, uint64_t seed, void* stream, double* kernel_ms);
+
+/* All buffers on the encoder's device (row_off is validated there before anything is written); queued
+ * on `stream` (NULL = the encoder's own) and synchronised before return.  Every buffer needs only its
+ * element's alignment, so tensor views fit. */
+int64_t shred_overlap_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             void* hits, void* covered, void* first, void* tok_ref, void* tok_cov, void* stream,
+                             double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget of
+ * the batch calls (one row is taken whole, however long); `first` is rebased to the call's ids by each
+ * piece's base.  row_off is validated on the host before anything is staged. */
+int64_t shred_overlap_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           int64_t* hits, int64_t* covered, int64_t* first, int64_t* tok_ref, uint8_t* tok_cov);
+
+/* The registered reference set (each pointer may be NULL): the bytes of its table on the device (0 without
+ * a set), its grams, and its distinct fingerprints.  Returns 0, -1 for NULL. */
+int shred_encoder_overlap_stats(const ShredEncoder* enc, uint64_t* table_bytes, uint64_t* ref_grams,
+                                uint64_t* distinct);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

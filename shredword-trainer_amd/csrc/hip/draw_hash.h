@@ -1,4 +1,4 @@
-// The seeded draw of the dropout, masked-LM, span-corruption, fill-in-the-middle and MinHash units:
+// The seeded draw of the dropout, masked-LM, span-corruption, fill-in-the-middle, MinHash and overlap units:
 //     d(x, c) = mix(mix(seed + G (x + 1)) ^ c)      (mix: murmur3's fmix64, arithmetic mod 2^64)
 // x is a position or a row index, c says which decision of that x is drawn (bits 63..32 of d).
 // Included by .hip files only.
@@ -41,13 +41,16 @@ enum Domain : uint64_t {
   kMhShingle,         // MinHash: where the hash chain of a shingle of x ids starts
   kMhA,               // MinHash: multiplier and
   kMhB,               //          addend of permutation x
-  kMhBand             // MinHash: where the hash chain of band x starts
+  kMhBand,            // MinHash: where the hash chain of band x starts
+  kNgram,             // n-gram overlap: g(x), what id x adds to a fingerprint
+  kMult               // n-gram overlap: the multiplier of grams of x ids
 };
 // (strictly increasing, so pairwise distinct)
 static_assert(kSel >= 1ull << 40 && kAct == kSel + 1 && kStart == kAct + 1 && kLen == kStart + 1 &&
                   kFimC == kLen + 1 && kCutA == kFimC + 1 && kCutB == kCutA + 1 && kMode == kCutB + 1 &&
-                  kMhShingle == kMode + 1 && kMhA == kMhShingle + 1 && kMhB == kMhA + 1 && kMhBand == kMhB + 1,
-              "the domain constants are (1 << 40) + 0 .. 11 (include/shredword_encode.h)");
+                  kMhShingle == kMode + 1 && kMhA == kMhShingle + 1 && kMhB == kMhA + 1 && kMhBand == kMhB + 1 &&
+                  kNgram == kMhBand + 1 && kMult == kNgram + 1,
+              "the domain constants are (1 << 40) + 0 .. 13 (include/shredword_encode.h)");
 
 // Values of the definition as the tests' Python reference computes it; the second wraps mod 2^64
 // in seed + G (x + 1), the third is a dropout draw (c: a rank).

@@ -859,4 +859,60 @@ int shred_encoder_dedup_stats(const ShredEncoder* enc, uint64_t* scratch_bytes, 
   return 0;
 }
 
+namespace {
+// What the two reference calls and the two corpus calls of the overlap unit refuse before any work (0 or -1).
+int overlap_refs_args(const ShredEncoder* enc, const void* ref_ids, size_t m, const void* ref_row_off, size_t ref_rows,
+                      int32_t w) {
+  if (!enc || (m && !ref_ids) || (!ref_row_off && ref_rows)) return -1;
+  if (w < 1 || w > SHRED_OVERLAP_MAX_NGRAM || m > shred::EncodeDevice::kOverlapMaxRefIds) return -1;
+  return shred::batch_rows_fit(ref_rows) ? 0 : -1;
+}
+
+int overlap_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                 const void* hits) {
+  if (!enc || (n && !ids) || (!row_off && rows)) return -1;
+  // outputs of no rows hold nothing: an empty tensor's NULL fits
+  if ((row_off ? rows : 1) && !hits) return -1;
+  return shred::batch_rows_fit(rows) ? 0 : -1;
+}
+}  // namespace
+
+int64_t shred_overlap_refs(ShredEncoder* enc, const int32_t* ref_ids, size_t m, const int64_t* ref_row_off,
+                           size_t ref_rows, int32_t w, uint64_t seed) {
+  if (overlap_refs_args(enc, ref_ids, m, ref_row_off, ref_rows, w)) return -1;
+  if (ref_row_off && !offsets_ok(ref_row_off, ref_rows, m)) return -6;
+  return enc->dev->overlap_refs_host(ref_ids, m, ref_row_off, ref_rows, w, seed);
+}
+
+int64_t shred_overlap_refs_device(ShredEncoder* enc, const void* ref_ids, size_t m, const void* ref_row_off,
+                                  size_t ref_rows, int32_t w, uint64_t seed, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  if (overlap_refs_args(enc, ref_ids, m, ref_row_off, ref_rows, w)) return -1;
+  return enc->dev->overlap_refs((const int32_t*)ref_ids, m, (const int64_t*)ref_row_off, ref_rows, w, seed, stream,
+                                kernel_ms);
+}
+
+int64_t shred_overlap_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                             void* hits, void* covered, void* first, void* tok_ref, void* tok_cov, void* stream,
+                             double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  if (overlap_args(enc, ids, n, row_off, rows, hits)) return -1;
+  return enc->dev->overlap((const int32_t*)ids, n, (const int64_t*)row_off, rows, (int64_t*)hits, (int64_t*)covered,
+                           (int64_t*)first, (int64_t*)tok_ref, (uint8_t*)tok_cov, stream, kernel_ms);
+}
+
+int64_t shred_overlap_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                           int64_t* hits, int64_t* covered, int64_t* first, int64_t* tok_ref, uint8_t* tok_cov) {
+  if (overlap_args(enc, ids, n, row_off, rows, hits)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  return enc->dev->overlap_host(ids, n, row_off, rows, hits, covered, first, tok_ref, tok_cov);
+}
+
+int shred_encoder_overlap_stats(const ShredEncoder* enc, uint64_t* table_bytes, uint64_t* ref_grams,
+                                uint64_t* distinct) {
+  if (!enc) return -1;
+  enc->dev->overlap_stats(table_bytes, ref_grams, distinct);
+  return 0;
+}
+
 }  // extern "C"

@@ -302,6 +302,25 @@ class EncodeDevice {
   // (cells whose bucket has an earlier row), those the same-root tests dropped, those accepted.
   void dedup_stats(uint64_t* scratch_bytes, uint64_t* edges, uint64_t* dropped, uint64_t* accepted) const;
 
+  // ---- n-gram overlap with a held-out reference set (batch_overlap.hip; shred_overlap_*).  The callers
+  // have checked the arguments' ranges: 1 <= w <= kOverlapMaxNgram, m <= kOverlapMaxRefIds, hits given.
+  // overlap_refs takes device buffers (row_off validated on the device), overlap_refs_host host buffers
+  // whose row_off the caller has checked; both replace the encoder's reference set (m == 0: clear it)
+  // and return its grams, -1 or -6 with the previous set kept.  overlap takes device buffers and returns
+  // the rows with hits, -1 or -6; overlap_host takes host buffers whose row_off the caller has checked
+  // and returns the rows with hits or -1.
+  static constexpr int kOverlapMaxNgram = 64;  // SHRED_OVERLAP_MAX_NGRAM
+  static constexpr uint64_t kOverlapMaxRefIds = 0x7FFFFFFFull;
+  int64_t overlap_refs(const int32_t* ids, size_t m, const int64_t* row_off, size_t rows, int w, uint64_t seed,
+                       void* stream, double* kernel_ms);
+  int64_t overlap_refs_host(const int32_t* ids, size_t m, const int64_t* row_off, size_t rows, int w, uint64_t seed);
+  int64_t overlap(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, int64_t* hits, int64_t* covered,
+                  int64_t* first, int64_t* tok_ref, uint8_t* tok_cov, void* stream, double* kernel_ms);
+  int64_t overlap_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, int64_t* hits,
+                       int64_t* covered, int64_t* first, int64_t* tok_ref, uint8_t* tok_cov);
+  // The registered set: bytes of its table (0 without one), its grams, its distinct fingerprints.
+  void overlap_stats(uint64_t* table_bytes, uint64_t* ref_grams, uint64_t* distinct) const;
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -343,7 +362,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kFim, kMinhash, kDedup, kPasses };
+              kCorrupt, kFim, kMinhash, kDedup, kOverlap, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

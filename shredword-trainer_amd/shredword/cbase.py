@@ -291,3 +291,17 @@ lib.shred_dedup_rows.argtypes = _dedup_rows
 lib.shred_dedup_rows.restype = c_int64
 lib.shred_encoder_dedup_stats.argtypes = [Encoder] + [POINTER(c_uint64)] * 4
 lib.shred_encoder_dedup_stats.restype = c_int
+# n-gram overlap: the reference set (ref_ids, m, ref_row_off, ref_rows, w, seed), then the corpus rows
+# (ids, n, row_off, rows, hits, covered, first, tok_ref, tok_cov)
+_overlap_refs = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_uint64]
+lib.shred_overlap_refs.argtypes = _overlap_refs
+lib.shred_overlap_refs.restype = c_int64
+lib.shred_overlap_refs_device.argtypes = _overlap_refs + [c_void_p, POINTER(c_double)]
+lib.shred_overlap_refs_device.restype = c_int64
+_overlap_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t] + [c_void_p] * 5
+lib.shred_overlap_device.argtypes = _overlap_rows + [c_void_p, POINTER(c_double)]
+lib.shred_overlap_device.restype = c_int64
+lib.shred_overlap_rows.argtypes = _overlap_rows
+lib.shred_overlap_rows.restype = c_int64
+lib.shred_encoder_overlap_stats.argtypes = [Encoder] + [POINTER(c_uint64)] * 3
+lib.shred_encoder_overlap_stats.restype = c_int

@@ -39,6 +39,9 @@ MINHASH_TILE = 2048
 MINHASH_MAX_PERM = 512     # SHRED_MINHASH_MAX_PERM
 MINHASH_MAX_SHINGLE = 64   # SHRED_MINHASH_MAX_SHINGLE
 DEDUP_MAX_BANDS = 128      # SHRED_DEDUP_MAX_BANDS
+# batch_overlap.hip: gram positions per workgroup (kOvTile), and the limit of the n-gram length
+OVERLAP_TILE = 2048
+OVERLAP_MAX_NGRAM = 64     # SHRED_OVERLAP_MAX_NGRAM
 
 # Encoders still alive at interpreter exit are destroyed while the HIP runtime is up (a destructor
 # that ran after the runtime's own teardown would free its device memory twice).
@@ -1420,6 +1423,96 @@ class BPEEncoder:
         sig, keys, _ = self.minhash_device(ids, row, num_perm=num_perm, shingle=shingle, seed=seed, bands=bands)
         labels, keep = self.dedup_device(sig, keys, threshold=threshold)[:2]
         return tuple(t.cpu().numpy() for t in (ids, row, labels, keep))
+
+    # ---- n-gram overlap with a held-out reference set (include/shredword_encode.h, shred_overlap_*) ------
+
+    @staticmethod
+    def _overlap_host(ids, row_offsets):
+        """_host_rows that refuses arrays of another dtype instead of converting them."""
+        for name, a, dt in (("ids", ids, np.int32), ("row_offsets", row_offsets, np.int64)):
+            if isinstance(a, np.ndarray) and a.dtype != dt:
+                raise ValueError(f"{name} must be {np.dtype(dt).name}")
+        return BPEEncoder._host_rows(ids, row_offsets)
+
+    def set_overlap_refs(self, ids, row_offsets=None, *, ngram=13, seed=0):
+        """Registers the held-out rows ids[row_offsets[r]:row_offsets[r + 1]] (None: one row; numpy arrays, or
+        int32 / int64 tensors on the encoder's GPU) as the reference set of overlap_rows / overlap_device,
+        replacing the previous one; no ids clears it.  -> the number of reference grams of `ngram` ids (a row
+        shorter than that has none).  The table is built on the GPU and stays there."""
+        w = int(ngram)
+        if not 1 <= w <= OVERLAP_MAX_NGRAM:
+            raise ValueError(f"ngram must be in [1, {OVERLAP_MAX_NGRAM}]")
+        seed = int(seed) & (2 ** 64 - 1)
+        if isinstance(ids, np.ndarray) or not hasattr(ids, "data_ptr"):
+            a, row, R = self._overlap_host(ids, row_offsets)
+            return self._check_batch(lib.shred_overlap_refs(
+                self.enc, a.ctypes.data, a.size, None if row is None else row.ctypes.data, 0 if row is None else R,
+                w, seed))
+        R = self._device_rows(ids, row_offsets)
+        return self._check_batch(lib.shred_overlap_refs_device(
+            self.enc, ids.data_ptr(), ids.numel(), None if row_offsets is None else row_offsets.data_ptr(),
+            0 if row_offsets is None else R, w, seed, self._stream(None, ids.device), None))
+
+    def overlap_rows(self, ids, row_offsets=None, *, token_outputs=False):
+        """-> (hits, covered, first, tok_ref, tok_cov, rows_hit): the overlap of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row) with the reference set of set_overlap_refs.
+        A position is a hit when the ngram ids from it on lie in one row and occur, in one row, in the
+        reference set.  hits, covered, first: int64 [rows], a row's hit positions, its tokens inside a matching
+        gram, and the index in ids of its first hit (-1: none).  With token_outputs, tok_ref: int64 [len(ids)],
+        a hit's smallest position in the reference ids, else -1, and tok_cov: bool [len(ids)]; else both are
+        None.  rows_hit: the rows with a hit.  Without a reference set nothing hits.  Built on the GPU."""
+        a, row, R = self._overlap_host(ids, row_offsets)
+        hits, covered, first = (np.empty(R, dtype=np.int64) for _ in range(3))
+        tok_ref = np.empty(a.size, dtype=np.int64) if token_outputs else None
+        tok_cov = np.empty(a.size, dtype=np.uint8) if token_outputs else None
+        ptr = lambda x: None if x is None else x.ctypes.data
+        rows_hit = self._check_batch(lib.shred_overlap_rows(
+            self.enc, a.ctypes.data, a.size, ptr(row), 0 if row is None else R, hits.ctypes.data, covered.ctypes.data,
+            first.ctypes.data, ptr(tok_ref), ptr(tok_cov)))
+        return hits, covered, first, tok_ref, None if tok_cov is None else tok_cov.view(np.bool_), rows_hit
+
+    def overlap_device(self, ids, row_offsets=None, *, token_outputs=False, stream=None):
+        """overlap_rows on device tensors (ids 1-D int32, row_offsets 1-D int64, on the encoder's GPU; views
+        that are only element-aligned fit) -> (hits, covered, first, tok_ref, tok_cov, rows_hit, device
+        milliseconds of the passes), the arrays as tensors (tok_cov bool)."""
+        import torch
+        R = self._device_rows(ids, row_offsets)
+        new = lambda count, dt: torch.empty(count, dtype=dt, device=ids.device)
+        hits, covered, first = (new(R, torch.int64) for _ in range(3))
+        tok_ref = new(ids.numel(), torch.int64) if token_outputs else None
+        tok_cov = new(ids.numel(), torch.bool) if token_outputs else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        ms = ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        rows_hit = self._check_batch(lib.shred_overlap_device(
+            self.enc, ids.data_ptr(), ids.numel(), ptr(row_offsets), 0 if row_offsets is None else R, hits.data_ptr(),
+            covered.data_ptr(), first.data_ptr(), ptr(tok_ref), ptr(tok_cov), st, ctypes.byref(ms)))
+        return hits, covered, first, tok_ref, tok_cov, rows_hit, ms.value
+
+    def overlap_stats(self) -> dict:
+        """The registered reference set: table_bytes it holds on the device (0 without one), its ref_grams and
+        its distinct fingerprints."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        lib.shred_encoder_overlap_stats(self.enc, *(ctypes.byref(x) for x in v))
+        return dict(zip(("table_bytes", "ref_grams", "distinct"), (x.value for x in v)))
+
+    def encode_overlap(self, texts, *, doc_offsets=None, specials: bool = False, token_outputs=False):
+        """Text to its overlap with the reference set without the ids leaving the GPU: encode_docs_device, then
+        overlap_device on its rows -> (ids, row_offsets, hits, covered, first, tok_ref, tok_cov, rows_hit), the
+        arrays on the host.  texts: a list / tuple of documents, or one text with doc_offsets (None: one
+        document)."""
+        import torch
+        if isinstance(texts, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(texts)
+        else:
+            buf = self._host_text(texts)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        ids, row = self.encode_docs_device(dev(buf), None if off is None else dev(off), specials=specials)[:2]
+        res = self.overlap_device(ids, row, token_outputs=token_outputs)
+        return tuple(None if t is None else t.cpu().numpy() for t in (ids, row) + res[:5]) + (res[5],)
 
     def destroy(self):
         if getattr(self, "enc", None):

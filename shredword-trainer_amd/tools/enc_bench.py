@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup | overlap] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -56,7 +56,13 @@ two warm-up calls), cells per second, the edges, those dropped by the same-root 
 clusters, for the row-major (the default) and the band-major cell order and for one edge per wave instead of per lane group
 (SHREDWORD_DEDUP_ORDER, SHREDWORD_DEDUP_LANES), beside a torch composition of the same definition on the same tensors
 (unique and a scatter-amin per band, the column count, min-label propagation with pointer jumping to a fixpoint), which
-must give equal labels."""
+must give equal labels; with a trailing `overlap`, the n-gram overlap of the same ids and rows (ngram 13) with a reference
+set of 2,000 of those rows and 2,000 random rows: the device ms of set_overlap_refs on tensors, of overlap_device without
+and with the token outputs (median of 7 after two warm-up calls), ids per second and the table's bytes, beside a torch
+composition of the same definition on the same tensors, all ids (the fingerprints by 13 shifted views and the same
+arithmetic, unique with a scatter-amin for the smallest reference position, isin and searchsorted for the hits, a
+difference array and a cumsum for the coverage, index_add and a scatter-amin for the rows), which must give equal
+results."""
 import os
 import subprocess
 import sys
@@ -100,8 +106,9 @@ else:
     long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
     dedup = args[-1] == "dedup"
     minhash = dedup or args[-1] == "minhash"  # the dedup leg runs behind the minhash leg, on its rows
-    # the corrupt, fim and minhash legs run on the mlm leg's stream, in its place
-    mlm = corrupt or fim or minhash or args[-1] == "mlm"
+    overlap = args[-1] == "overlap"
+    # the corrupt, fim, minhash and overlap legs run on the mlm leg's stream, in its place
+    mlm = corrupt or fim or minhash or overlap or args[-1] == "mlm"
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -478,7 +485,7 @@ else:
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
         legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
-        for name, whole, per_id, ref in () if corrupt or fim or minhash else legs:
+        for name, whole, per_id, ref in () if corrupt or fim or minhash or overlap else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -732,4 +739,77 @@ else:
                     assert same, "dedup_device and the torch composition of the same definition differ"
                 print(*line, flush=True)
         del os.environ["SHREDWORD_DEDUP_ORDER"], os.environ["SHREDWORD_DEDUP_LANES"]
+    if overlap:
+        del starts
+        R, SEED, W, PICK = row.numel() - 1, 1, 13, 2000
+        odraw = lambda x, c: tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (x + 1)) ^ c)
+        # the reference set: PICK rows of the corpus and as many random rows
+        g = torch.Generator().manual_seed(13)
+        pick = torch.randperm(R, generator=g)[:PICK].sort()[0].cuda()
+        lens = (row[1:] - row[:-1])[pick]
+        p_row = torch.cat([lens.new_zeros(1), lens.cumsum(0)])
+        total = int(p_row[-1].item())
+        col = torch.arange(total, device="cuda") - torch.repeat_interleave(p_row[:-1], lens, output_size=total)
+        taken = ids[torch.repeat_interleave(row[:-1][pick], lens, output_size=total) + col]
+        noise = torch.randint(5, V, (PICK * 350,), generator=g, dtype=torch.int32).cuda()
+        ref_ids = torch.cat([taken, noise])
+        ref_row = torch.cat([p_row, total + 350 * torch.arange(1, PICK + 1, device="cuda")])
+        del col, taken, noise
+
+        def prints(t_ids, t_row):
+            """-> (F of every position that starts a gram, those positions, the row of every id)"""
+            cnt = t_ids.numel() - W + 1
+            gt = odraw(t_ids.long() & 0xFFFFFFFF, (1 << 40) + 12)
+            A = int(odraw(torch.tensor([W], device="cuda"), (1 << 40) + 13).item()) | 1
+            S = torch.zeros(cnt, dtype=torch.int64, device="cuda")
+            for j in range(W):
+                S = S * A + gt[j:j + cnt]
+            F = tmix(S)
+            F = torch.where(F == -1, -2, F)
+            of = torch.bucketize(torch.arange(t_ids.numel(), device="cuda"), t_row, right=True) - 1
+            k = (torch.arange(cnt, device="cuda") + W <= t_row[of[:cnt] + 1]).nonzero().squeeze(1)
+            return F[k], k, of
+
+        def torch_overlap():
+            rF, rk, _ = prints(ref_ids, ref_row)
+            uniq, inv = torch.unique(rF, return_inverse=True)
+            P = torch.full((uniq.numel(),), 1 << 62, device="cuda").scatter_reduce_(0, inv, rk, "amin")
+            F, k, of = prints(ids, row)
+            hit = torch.isin(F, uniq)
+            at = k[hit]
+            tok_ref = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+            tok_ref[at] = P[torch.searchsorted(uniq, F[hit])]
+            edge = torch.zeros(n + W, dtype=torch.int32, device="cuda")
+            edge.index_add_(0, at, torch.ones_like(at, dtype=torch.int32))
+            edge.index_add_(0, at + W, -torch.ones_like(at, dtype=torch.int32))
+            tok_cov = edge.cumsum(0)[:n] > 0
+            hits = torch.zeros(R, dtype=torch.int64, device="cuda").index_add_(0, of[at], torch.ones_like(at))
+            covered = torch.zeros(R, dtype=torch.int64, device="cuda").index_add_(0, of, tok_cov.long())
+            first = torch.full((R,), 1 << 62, device="cuda").scatter_reduce_(0, of[at], at, "amin")
+            return hits, covered, torch.where(first == 1 << 62, -1, first), tok_ref, tok_cov
+
+        build = lambda: enc.set_overlap_refs(ref_ids, ref_row, ngram=W, seed=SEED)
+        grams = build()
+        bt = events(build)
+        line = ("overlap: ids", n, "rows", R, "ngram", W, "| reference set:", PICK, "rows of the corpus and", PICK,
+                "random rows,", ref_ids.numel(), "ids,", grams, "grams,", enc.overlap_stats()["distinct"], "distinct, table bytes",
+                enc.overlap_stats()["table_bytes"], "| set_overlap_refs on tensors, whole call ms", bt[0], "min", bt[1], "max", bt[2])
+        for tokens in (False, True):
+            run = lambda: enc.overlap_device(ids, row, token_outputs=tokens)
+            run()  # first call: allocates the outputs' pages
+            run()
+            res = [run() for _ in range(reps)]
+            ms = sorted(r[6] for r in res)
+            med, c = ms[len(ms) // 2], events(run)
+            line += ("| probe", "with" if tokens else "without", "token outputs: ms", med, "min", ms[0], "max", ms[-1],
+                     "ids/s", n / med * 1e3, "whole call (allocation, passes) ms", c[0])
+        t = events(torch_overlap)
+        ref = torch_overlap()
+        same = all(torch.equal(a, b) for a, b in zip(res[0][:5], ref)) and res[0][5] == int((ref[0] > 0).sum().item())
+        print(*line, "| rows hit", res[0][5], "hit positions", int(ref[0].sum().item()), "covered tokens",
+              int(ref[1].sum().item()), "| torch composition on all ids (the reference set's fingerprints included) ms", t[0],
+              "min", t[1], "max", t[2], "| equal to the torch composition", same,
+              "| torch / ours (build + probe with token outputs)", t[0] / (bt[0] + med), "| torch / probe alone", t[0] / med,
+              flush=True)
+        assert same, "overlap_device and the torch composition of the same definition differ"
     enc.destroy()
