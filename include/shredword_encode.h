@@ -1120,6 +1120,57 @@ int64_t shred_overlap_rows(ShredEncoder* enc, const int32_t* ids, size_t n, cons
 int shred_encoder_overlap_stats(const ShredEncoder* enc, uint64_t* table_bytes, uint64_t* ref_grams,
                                 uint64_t* distinct);
 
+/* ---- repeated n-grams within a row, on the GPU (the Gopher / MassiveText repetition measures) -----------
+ *
+ * The share of a document inside n-grams that occur more than once in it (n = 5 .. 10) and the share of its
+ * most frequent n-gram (n = 2 .. 4), beside MinHash, dedup and overlap on the flat (ids, row_off) pair.  The
+ * calls give counts; thresholds and the filtering decision are the caller's.
+ *
+ * Definitions.  Options are w, 1 <= w <= SHRED_OVERLAP_MAX_NGRAM, and a 64-bit seed.
+ *   Position k of the id stream has a gram iff k + w does not pass the end of k's row.  Its fingerprint F(k)
+ *             is the overlap section's, unchanged: g, A, S and F under (seed, w).
+ *   Two grams of one row are equal iff their F are equal on all 64 bits (two different grams share one with
+ *             probability about 2^-64).  Grams of different rows are never compared.
+ *   c(k)      the number of positions of k's row whose gram equals k's.
+ * Per row r (R int64 each, all required):
+ *   grams     the positions with a gram.
+ *   distinct  the distinct fingerprints among them.
+ *   repeated  the positions with c(k) >= 2, first occurrences included.
+ *   covered   the ids of the row inside at least one gram with c >= 2: a union, an id inside several such
+ *             grams counts once.  The Gopher "duplicate n-gram" measure, in tokens.
+ *   top_count the largest c in the row, 0 without grams.
+ *   top_pos   the smallest position whose gram has c == top_count[r] (a tie goes to the gram that occurs
+ *             first): an index into the call's ids, -1 without grams.
+ * Per token (n entries each, may be NULL):
+ *   tok_first int64: the smallest position of the row whose gram equals k's (k itself for a first occurrence),
+ *             an index into the call's ids; -1 where k has no gram.
+ *   tok_cov   uint8: 1 iff id k is covered as above.
+ * Returns the number of rows with repeated > 0.  row_off == NULL (with rows == 0) means one row of all ids;
+ * with R == 0 nothing is touched.  Errors write nothing: -1 for a bad argument (w out of range, a required
+ * pointer NULL), a HIP or allocation error, or a row of more than 2^32 - 2 ids (in-row positions are kept in
+ * 32 bits; the code the batch calls give an entry past int32); -6 for a bad row_off.  (A HIP error after the
+ * first piece of shred_repeat_rows leaves the earlier pieces' output in place.)
+ *
+ * The result is a function of (seed, w, the row's ids) alone, up to the base of the two position outputs: not
+ * of where the row lies, of scheduling, or of the piece size of a host call.  The rows' tables take 16 bytes x 2
+ * grams of device memory for the call's rows together, kept for the next call.
+ */
+
+/* All buffers on the encoder's device (row_off is validated there before anything is written); queued on
+ * `stream` (NULL = the encoder's own) and synchronised before return.  Every buffer needs only its element's
+ * alignment, so tensor views fit.  kernel_ms (may be NULL) receives the device time of the passes. */
+int64_t shred_repeat_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows, int32_t w,
+                            uint64_t seed, void* grams, void* distinct, void* repeated, void* covered, void* top_count,
+                            void* top_pos, void* tok_first, void* tok_cov, void* stream, double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget of the
+ * batch calls (one row is taken whole, however long); top_pos and tok_first are rebased to the call's ids by
+ * each piece's base.  row_off is validated on the host before anything is staged. */
+int64_t shred_repeat_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          int32_t w, uint64_t seed, int64_t* grams, int64_t* distinct, int64_t* repeated,
+                          int64_t* covered, int64_t* top_count, int64_t* top_pos, int64_t* tok_first,
+                          uint8_t* tok_cov);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

@@ -61,8 +61,8 @@
 #include "../host/encoder.h"
 #include "batch_common.h"
 #include "batch_state.h"
-#include "draw_hash.h"
 #include "encode_common.h"
+#include "ngram_print.h"
 
 namespace shred {
 namespace {
@@ -75,26 +75,11 @@ constexpr int kOvG = kOvTile + 2 * (kOvMaxW - 1);   // ids a tile reads: both ha
 constexpr int kOvWords = kOvPos / 64;               // words of the hit and coverage masks
 constexpr int kOvRows = 1024;                       // row ends staged in LDS
 constexpr int kOvFar = 1 << 20;                     // a row end past everything the tile holds
-constexpr u64 kOvFree = ~0ull;                      // a free slot's key
 constexpr uint32_t kOvNone = 0xFFFFFFFFu;           // no reference position: above every one
 static_assert(kOvTile + kOvMaxW - 1 <= kOvPos && kOvPos % 64 == 0 && kOvWords <= 64,
               "the strips hold the tile and its halo; wave 0 holds the masks a word per lane");
 static_assert(kOvMaxW <= 64, "a doubling step shifts by at most 32 bits");
-
-// The definition's pieces, for the kernels, the host and the asserts below.
-constexpr __host__ __device__ u64 ov_g(u64 seed, int32_t id) { return draw(seed, (u64)(uint32_t)id, kNgram); }
-constexpr __host__ __device__ u64 ov_mult(u64 seed, u64 w) { return draw(seed, w, kMult) | 1; }
-constexpr __host__ __device__ u64 ov_print(u64 S) {
-  const u64 f = fmix64(S);
-  return f == kOvFree ? kOvFree - 1 : f;
-}
-// Values of the definition as the tests' numpy reference computes it, under seed 3: the 1-gram [7], the
-// multiplier of 13-grams, and the 3-gram [7, -1, 5].
-constexpr u64 ov_three(u64 seed, int32_t a, int32_t b, int32_t c) {
-  return ov_print((ov_g(seed, a) * ov_mult(seed, 3) + ov_g(seed, b)) * ov_mult(seed, 3) + ov_g(seed, c));
-}
-static_assert(ov_print(ov_g(3, 7)) == 0xcafcf3efc9b725e1ull && ov_mult(3, 13) == 0x5c864b2e1a922f5full, "overlap");
-static_assert(ov_three(3, 7, -1, 5) == 0xfe2c613d41db9357ull, "overlap");
+// (the fingerprint ov_g / ov_mult / ov_print and a free slot's key kOvFree: ngram_print.h)
 
 struct OvTable {
   u64* key;       // nullptr: no reference set, nothing hits
@@ -116,18 +101,6 @@ struct OvOut {
   uint8_t* tok_cov;
   u64 first_base;  // of the call's ids in the caller's (a host piece)
 };
-
-__device__ __forceinline__ u64 ov_sum(u64 v) {
-  for (int d = 32; d; d >>= 1) v += (u64)__shfl_xor((unsigned long long)v, d);
-  return v;
-}
-__device__ __forceinline__ u64 ov_min(u64 v) {
-  for (int d = 32; d; d >>= 1) {
-    const u64 o = (u64)__shfl_xor((unsigned long long)v, d);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // Positions [0, n) of the id stream, n >= 1; row: rows + 1 good offsets.  Insert: ctr[1] += grams,
 // ctr[2] += slots claimed.  Probe: out.hits / covered were preset to 0, out.first to all-ones.
@@ -357,12 +330,6 @@ int overlap_offsets(OverlapState& os, u64 n, const int64_t* row_off, u64 R, hipS
   ENC_OK(hipMemcpyAsync(os.host.get(), os.res.get(), 8, hipMemcpyDeviceToHost, st));
   ENC_OK(hipStreamSynchronize(st));
   return os.host[0] ? -6 : 0;
-}
-
-u64 ov_power(u64 a, int w) {
-  u64 r = 1;
-  for (int i = 0; i < w; ++i) r *= a;
-  return r;
 }
 
 }  // namespace

@@ -915,4 +915,43 @@ int shred_encoder_overlap_stats(const ShredEncoder* enc, uint64_t* table_bytes, 
   return 0;
 }
 
+namespace {
+// What the two repeat calls refuse before any work (0 or -1), and their outputs.
+int repeat_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows, int32_t w,
+                void* const* row_out, void* tok_first, void* tok_cov, shred::EncodeDevice::RepeatOut* o) {
+  if (!enc || (n && !ids) || (!row_off && rows)) return -1;
+  if (w < 1 || w > SHRED_OVERLAP_MAX_NGRAM || !shred::batch_rows_fit(rows)) return -1;
+  // outputs of no rows hold nothing: an empty tensor's NULL fits
+  for (int k = 0; k < 6; ++k)
+    if ((row_off ? rows : 1) && !row_out[k]) return -1;
+  *o = shred::EncodeDevice::RepeatOut{(int64_t*)row_out[0], (int64_t*)row_out[1], (int64_t*)row_out[2],
+                                      (int64_t*)row_out[3], (int64_t*)row_out[4], (int64_t*)row_out[5],
+                                      (int64_t*)tok_first, (uint8_t*)tok_cov};
+  return 0;
+}
+}  // namespace
+
+int64_t shred_repeat_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows, int32_t w,
+                            uint64_t seed, void* grams, void* distinct, void* repeated, void* covered, void* top_count,
+                            void* top_pos, void* tok_first, void* tok_cov, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  void* const row_out[6] = {grams, distinct, repeated, covered, top_count, top_pos};
+  shred::EncodeDevice::RepeatOut o;
+  if (repeat_args(enc, ids, n, row_off, rows, w, row_out, tok_first, tok_cov, &o)) return -1;
+  return enc->dev->repeat((const int32_t*)ids, n, (const int64_t*)row_off, rows, w, seed, o, stream, kernel_ms);
+}
+
+int64_t shred_repeat_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                          int32_t w, uint64_t seed, int64_t* grams, int64_t* distinct, int64_t* repeated,
+                          int64_t* covered, int64_t* top_count, int64_t* top_pos, int64_t* tok_first,
+                          uint8_t* tok_cov) {
+  void* const row_out[6] = {grams, distinct, repeated, covered, top_count, top_pos};
+  shred::EncodeDevice::RepeatOut o;
+  if (repeat_args(enc, ids, n, row_off, rows, w, row_out, tok_first, tok_cov, &o)) return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  for (size_t r = 0; r < (row_off ? rows : 1); ++r)
+    if ((uint64_t)(row_off ? row_off[r + 1] - row_off[r] : (int64_t)n) > shred::EncodeDevice::kRepeatMaxRow) return -1;
+  return enc->dev->repeat_host(ids, n, row_off, rows, w, seed, o);
+}
+
 }  // extern "C"

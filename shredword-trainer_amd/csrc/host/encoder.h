@@ -321,6 +321,22 @@ class EncodeDevice {
   // The registered set: bytes of its table (0 without one), its grams, its distinct fingerprints.
   void overlap_stats(uint64_t* table_bytes, uint64_t* ref_grams, uint64_t* distinct) const;
 
+  // ---- repeated n-grams within a row (batch_repeat.hip; shred_repeat_*).  The callers have checked the
+  // arguments' ranges: 1 <= w <= kOverlapMaxNgram, the six row outputs given.  repeat takes device buffers
+  // and returns the rows with repeats, -1 (also: a row whose positions do not fit 32 bits) or -6; repeat_host
+  // takes host buffers whose row_off and row lengths the caller has checked and returns the rows with
+  // repeats or -1.
+  static constexpr uint64_t kRepeatMaxRow = 0xFFFFFFFEull;
+  struct RepeatOut {
+    int64_t *grams, *distinct, *repeated, *covered, *top_count, *top_pos;
+    int64_t* tok_first;  // may be nullptr
+    uint8_t* tok_cov;    // may be nullptr
+  };
+  int64_t repeat(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, int w, uint64_t seed,
+                 const RepeatOut& out, void* stream, double* kernel_ms);
+  int64_t repeat_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, int w, uint64_t seed,
+                      const RepeatOut& out);
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -362,7 +378,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kFim, kMinhash, kDedup, kOverlap, kPasses };
+              kCorrupt, kFim, kMinhash, kDedup, kOverlap, kRepeat, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -305,3 +305,9 @@ lib.shred_overlap_rows.argtypes = _overlap_rows
 lib.shred_overlap_rows.restype = c_int64
 lib.shred_encoder_overlap_stats.argtypes = [Encoder] + [POINTER(c_uint64)] * 3
 lib.shred_encoder_overlap_stats.restype = c_int
+# repeated n-grams within a row: ids, n, row_off, rows, w, seed, the six row outputs, tok_first, tok_cov
+_repeat_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_uint64] + [c_void_p] * 8
+lib.shred_repeat_device.argtypes = _repeat_rows + [c_void_p, POINTER(c_double)]
+lib.shred_repeat_device.restype = c_int64
+lib.shred_repeat_rows.argtypes = _repeat_rows
+lib.shred_repeat_rows.restype = c_int64

@@ -1514,6 +1514,71 @@ class BPEEncoder:
         res = self.overlap_device(ids, row, token_outputs=token_outputs)
         return tuple(None if t is None else t.cpu().numpy() for t in (ids, row) + res[:5]) + (res[5],)
 
+    # ---- repeated n-grams within a row (include/shredword_encode.h, shred_repeat_*) ------
+
+    @staticmethod
+    def _repeat_opts(ngram, seed):
+        w = int(ngram)
+        if not 1 <= w <= OVERLAP_MAX_NGRAM:
+            raise ValueError(f"ngram must be in [1, {OVERLAP_MAX_NGRAM}]")
+        return w, int(seed) & (2 ** 64 - 1)
+
+    def repeat_rows(self, ids, row_offsets=None, *, ngram=5, seed=0, token_outputs=False):
+        """-> (grams, distinct, repeated, covered, top_count, top_pos, tok_first, tok_cov, rows_repeated): the
+        repeated n-grams inside each row ids[row_offsets[r]:row_offsets[r + 1]] (None: one row), the Gopher
+        repetition measures.  Per row, int64: its grams of `ngram` ids, the distinct ones, the positions whose
+        gram occurs at least twice in the row, the ids inside such a gram, the count of the most frequent gram
+        and the index in ids of its first occurrence (-1: no gram).  With token_outputs, tok_first: int64
+        [len(ids)], the first position of the row with the same gram (-1: no gram), and tok_cov: bool
+        [len(ids)]; else both are None.  rows_repeated: the rows with a repeat.  Grams of different rows are
+        never compared.  Built on the GPU."""
+        w, seed = self._repeat_opts(ngram, seed)
+        a, row, R = self._overlap_host(ids, row_offsets)
+        outs = [np.empty(R, dtype=np.int64) for _ in range(6)]
+        tok_first = np.empty(a.size, dtype=np.int64) if token_outputs else None
+        tok_cov = np.empty(a.size, dtype=np.uint8) if token_outputs else None
+        ptr = lambda x: None if x is None else x.ctypes.data
+        rows_rep = self._check_batch(lib.shred_repeat_rows(
+            self.enc, a.ctypes.data, a.size, ptr(row), 0 if row is None else R, w, seed, *(ptr(x) for x in outs),
+            ptr(tok_first), ptr(tok_cov)))
+        return (*outs, tok_first, None if tok_cov is None else tok_cov.view(np.bool_), rows_rep)
+
+    def repeat_device(self, ids, row_offsets=None, *, ngram=5, seed=0, token_outputs=False, stream=None):
+        """repeat_rows on device tensors (ids 1-D int32, row_offsets 1-D int64, on the encoder's GPU; views that
+        are only element-aligned fit) -> (grams, distinct, repeated, covered, top_count, top_pos, tok_first,
+        tok_cov, rows_repeated, device milliseconds of the passes), the arrays as tensors (tok_cov bool)."""
+        import torch
+        w, seed = self._repeat_opts(ngram, seed)
+        R = self._device_rows(ids, row_offsets)
+        new = lambda count, dt: torch.empty(count, dtype=dt, device=ids.device)
+        outs = [new(R, torch.int64) for _ in range(6)]
+        tok_first = new(ids.numel(), torch.int64) if token_outputs else None
+        tok_cov = new(ids.numel(), torch.bool) if token_outputs else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        ms = ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        rows_rep = self._check_batch(lib.shred_repeat_device(
+            self.enc, ids.data_ptr(), ids.numel(), ptr(row_offsets), 0 if row_offsets is None else R, w, seed,
+            *(ptr(t) for t in outs), ptr(tok_first), ptr(tok_cov), st, ctypes.byref(ms)))
+        return (*outs, tok_first, tok_cov, rows_rep, ms.value)
+
+    def encode_repeats(self, texts, *, doc_offsets=None, specials: bool = False, ngram=5, seed=0, token_outputs=False):
+        """Text to its repeated n-grams without the ids leaving the GPU: encode_docs_device, then repeat_device
+        on its rows -> (ids, row_offsets) + the nine results of repeat_rows, the arrays on the host.  texts: a
+        list / tuple of documents, or one text with doc_offsets (None: one document)."""
+        import torch
+        if isinstance(texts, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(texts)
+        else:
+            buf = self._host_text(texts)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        ids, row = self.encode_docs_device(dev(buf), None if off is None else dev(off), specials=specials)[:2]
+        res = self.repeat_device(ids, row, ngram=ngram, seed=seed, token_outputs=token_outputs)
+        return tuple(None if t is None else t.cpu().numpy() for t in (ids, row) + res[:8]) + (res[8],)
+
     def destroy(self):
         if getattr(self, "enc", None):
             lib.shred_encoder_destroy(self.enc)

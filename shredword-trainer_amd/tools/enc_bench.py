@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup | overlap] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup | overlap | repeat] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -62,7 +62,11 @@ and with the token outputs (median of 7 after two warm-up calls), ids per second
 composition of the same definition on the same tensors, all ids (the fingerprints by 13 shifted views and the same
 arithmetic, unique with a scatter-amin for the smallest reference position, isin and searchsorted for the hits, a
 difference array and a cumsum for the coverage, index_add and a scatter-amin for the rows), which must give equal
-results."""
+results; with a trailing `repeat`, the repeated n-grams inside the same rows at ngram 5 and 13: the device ms of
+repeat_device without and with the token outputs (median of 7 after two warm-up calls), beside a torch composition
+of the same definition (the fingerprints as in the overlap leg, unique over (row, fingerprint) with inverse and counts,
+scatter reductions) on a prefix of 20,000 rows, where it must give equal results, its time scaled by the id count: an
+extrapolation, printed as one."""
 import os
 import subprocess
 import sys
@@ -106,9 +110,9 @@ else:
     long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
     dedup = args[-1] == "dedup"
     minhash = dedup or args[-1] == "minhash"  # the dedup leg runs behind the minhash leg, on its rows
-    overlap = args[-1] == "overlap"
-    # the corrupt, fim, minhash and overlap legs run on the mlm leg's stream, in its place
-    mlm = corrupt or fim or minhash or overlap or args[-1] == "mlm"
+    overlap, repeat = args[-1] == "overlap", args[-1] == "repeat"
+    # the corrupt, fim, minhash, overlap and repeat legs run on the mlm leg's stream, in its place
+    mlm = corrupt or fim or minhash or overlap or repeat or args[-1] == "mlm"
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -485,7 +489,7 @@ else:
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
         legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
-        for name, whole, per_id, ref in () if corrupt or fim or minhash or overlap else legs:
+        for name, whole, per_id, ref in () if corrupt or fim or minhash or overlap or repeat else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -812,4 +816,63 @@ else:
               "| torch / ours (build + probe with token outputs)", t[0] / (bt[0] + med), "| torch / probe alone", t[0] / med,
               flush=True)
         assert same, "overlap_device and the torch composition of the same definition differ"
+    if repeat:
+        del starts
+        R, SEED, PRE = row.numel() - 1, 1, 20000
+        rdraw = lambda x, c: tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (x + 1)) ^ c)
+        p_row = row[:PRE + 1].clone()
+        p_ids = ids[:int(p_row[-1].item())].clone()
+
+        def torch_repeat(W):
+            """the definition on the prefix -> the eight arrays of repeat_device"""
+            m, cnt, big = p_ids.numel(), p_ids.numel() - W + 1, 1 << 62
+            gt = rdraw(p_ids.long() & 0xFFFFFFFF, (1 << 40) + 12)
+            A = int(rdraw(torch.tensor([W], device="cuda"), (1 << 40) + 13).item()) | 1
+            S = torch.zeros(cnt, dtype=torch.int64, device="cuda")
+            for j in range(W):
+                S = S * A + gt[j:j + cnt]
+            F = tmix(S)
+            F = torch.where(F == -1, -2, F)
+            of = torch.bucketize(torch.arange(m, device="cuda"), p_row, right=True) - 1
+            k = (torch.arange(cnt, device="cuda") + W <= p_row[of[:cnt] + 1]).nonzero().squeeze(1)
+            rk = of[k]
+            uniq, inv, c = torch.unique(torch.stack([rk, F[k]], 1), dim=0, return_inverse=True, return_counts=True)
+            first = torch.full((uniq.shape[0],), big, device="cuda").scatter_reduce_(0, inv, k, "amin")[inv]
+            c = c[inv]
+            tok_first = torch.full((m,), -1, dtype=torch.int64, device="cuda")
+            tok_first[k] = first
+            at = k[c >= 2]
+            edge = torch.zeros(m + W, dtype=torch.int32, device="cuda")
+            edge.index_add_(0, at, torch.ones_like(at, dtype=torch.int32))
+            edge.index_add_(0, at + W, -torch.ones_like(at, dtype=torch.int32))
+            tok_cov = edge.cumsum(0)[:m] > 0
+            zeros = lambda: torch.zeros(PRE, dtype=torch.int64, device="cuda")
+            top = zeros().scatter_reduce_(0, rk, c, "amax")
+            pos = torch.full((PRE,), big, device="cuda").scatter_reduce_(0, rk, torch.where(c == top[rk], first, big), "amin")
+            return (zeros().index_add_(0, rk, torch.ones_like(rk)), zeros().index_add_(0, uniq[:, 0], torch.ones_like(uniq[:, 0])),
+                    zeros().index_add_(0, of[at], torch.ones_like(at)), zeros().index_add_(0, of, tok_cov.long()), top,
+                    torch.where(pos == big, -1, pos), tok_first, tok_cov)
+
+        for W in (5, 13):
+            line = ("repeat: ids", n, "rows", R, "ngram", W)
+            for tokens in (False, True):
+                run = lambda: enc.repeat_device(ids, row, ngram=W, seed=SEED, token_outputs=tokens)
+                run()  # first call: allocates the outputs' pages
+                run()
+                res = [run() for _ in range(reps)]
+                ms = sorted(r[9] for r in res)
+                med = ms[len(ms) // 2]
+                line += ("|", "with" if tokens else "without", "token outputs: ms", med, "min", ms[0], "max", ms[-1],
+                         "ids/s", n / med * 1e3)
+            ours = enc.repeat_device(ids, row, ngram=W, seed=SEED, token_outputs=True)
+            pre = enc.repeat_device(p_ids, p_row, ngram=W, seed=SEED, token_outputs=True)
+            t = events(lambda: torch_repeat(W))
+            same = all(torch.equal(a, b) for a, b in zip(pre[:8], torch_repeat(W)))
+            scale = n / p_ids.numel()
+            print(*line, "| rows with repeats", ours[8], "repeated positions", int(ours[2].sum().item()), "covered tokens",
+                  int(ours[3].sum().item()), "| torch composition on the first", PRE, "rows,", p_ids.numel(), "ids: ms", t[0],
+                  "min", t[1], "max", t[2], "| equal to the torch composition there", same,
+                  "| scaled by the id count (an extrapolation) ms", t[0] * scale, "| scaled torch / ours with token outputs",
+                  t[0] * scale / med, flush=True)
+            assert same, "repeat_device and the torch composition of the same definition differ"
     enc.destroy()
