@@ -1171,6 +1171,83 @@ int64_t shred_repeat_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const
                           int64_t* covered, int64_t* top_count, int64_t* top_pos, int64_t* tok_first,
                           uint8_t* tok_cov);
 
+/* ---- exact dedup of whole rows, across calls, on the GPU ---------------------------------------------------
+ *
+ * The step before MinHash: which rows are, id for id, a copy of an earlier row, among the rows of this call and
+ * of every call since the last reset.  With documents as rows it finds exact duplicate documents; with lines as
+ * rows, the duplicate lines of a corpus (CCNet, RefinedWeb: menus, banners, licence headers), and with documents
+ * as groups of lines the Gopher measures, the share of a document's lines and of its tokens that sit in
+ * duplicated lines.  The calls give indices, flags and counts; the filtering decision is the caller's.
+ *
+ * Definitions.  mix, G and d(x, c) are those of the masked-LM section; NGRAM and MULT are those of the overlap
+ * section, and the new constants are ROW = (1 << 40) + 14 and GROUP = (1 << 40) + 15.  All arithmetic is mod 2^64.
+ * An id enters as its 32-bit pattern, zero-extended; ids are never looked up.
+ *   g(t) = d(t, NGRAM), as in overlap;  A = d(0, MULT) | 1 (overlap's multipliers have w >= 1).
+ *   Row sum:  for a row of len ids t[0 .. len): S = the sum over j of A^(len-1-j) * g(t[j]); 0 for an empty row.
+ *   F = mix(S ^ d(len, ROW)), with the value 2^64 - 1 replaced by 2^64 - 2 (the all-ones pattern marks a free
+ *             table slot).  The length enters, so a row and its extension by one id differ even where the sums
+ *             collide.  F depends on (seed, the row's ids) alone, not on where the row lies.
+ *   State:    shred_exact_reset(enc, capacity, seed, min_len) gives the encoder an empty table for up to
+ *             `capacity` distinct keys (slots = the power of two >= 2 x capacity, 16 bytes a slot: a u64 key and a
+ *             u64 smallest index), a row counter seen = 0 and a group counter groups_seen = 0.  capacity == 0
+ *             frees it.  The state lasts until the next reset or until the encoder is destroyed.
+ *   Index:    row r of a call has the global index seen + r; a successful call adds its R rows to seen.
+ *   Compared: a row of at least min_len ids (min_len >= 0).  A shorter row is never inserted and never a
+ *             duplicate.
+ *   first(r)  the smallest global index of a compared row with the same F, among the rows of all calls since the
+ *             reset up to and including this one; the row's own index for a row that is not compared.
+ *   Duplicate: row r is one iff first(r) is below its own global index.  Equality is on the 64 bits of F, not on
+ *             the ids: two different rows share one with probability 2^-64, so a state sees a false duplicate
+ *             with probability about (compared rows)^2 / 2^65; a caller who needs certainty compares the ids of a
+ *             reported duplicate with those at `first`.
+ *   Groups:   grp_off (optional) holds G + 1 int64 offsets into the call's rows, validated like row_off, with
+ *             grp_off[G] == R: lines as rows, documents as groups.  Group q of a call has the global index
+ *             groups_seen + q; a successful call with grp_off adds G to groups_seen.
+ *   In-group: when g_in_rows is requested every compared row is also inserted under
+ *             F2 = mix(F ^ d(global group index, GROUP)), with the same all-ones rule, and is an in-group duplicate
+ *             iff the smallest index under F2 is below its own.
+ * A row's result depends only on the rows with a smaller global index: not on scheduling, on host or device
+ * staging, or on the piece size of a host call.
+ *
+ * Outputs (R rows, G groups):
+ *   first       R int64, required: as defined.
+ *   dup         R uint8, may be NULL: 1 iff the row is a duplicate.
+ *   print       R uint64, may be NULL: the row's F, also for rows that are not compared.
+ *   g_dup_rows  G int64, may be NULL: the group's duplicate rows.
+ *   g_dup_ids   G int64, may be NULL: the ids inside the group's duplicate rows.
+ *   g_in_rows   G int64, may be NULL: the group's in-group duplicates; requesting it turns the F2 inserts on.
+ * The three group outputs need grp_off.  Returns the number of duplicate rows of the call.  row_off == NULL (with
+ * rows == 0) means one row of all ids; with R == 0 nothing is touched.  Errors write nothing and leave the table,
+ * seen and groups_seen as they were: -1 when first is NULL, a group output is given without grp_off, the call
+ * comes before a reset, a HIP or allocation error occurs, or the call could overfill the table: the distinct
+ * keys so far + the compared rows of this call (twice that with g_in_rows), counted before anything is inserted,
+ * must not exceed capacity (a conservative bound: duplicates add no key); -6 for a bad row_off or grp_off.  (A HIP
+ * error after the first piece of shred_exact_rows leaves the earlier pieces in place.)
+ */
+
+/* Replaces the encoder's exact-dedup state as defined above.  Returns 0; -1 for NULL, min_len < 0 or a table that
+ * cannot be allocated (the encoder then has no table). */
+int shred_exact_reset(ShredEncoder* enc, uint64_t capacity, uint64_t seed, int64_t min_len);
+
+/* All buffers on the encoder's device (row_off and grp_off are validated there before anything is written); queued
+ * on `stream` (NULL = the encoder's own) and synchronised before return.  Every buffer needs only its element's
+ * alignment, so tensor views fit.  kernel_ms (may be NULL) receives the device time of the passes. */
+int64_t shred_exact_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                           const void* grp_off, size_t groups, void* first, void* dup, void* print, void* g_dup_rows,
+                           void* g_dup_ids, void* g_in_rows, void* stream, double* kernel_ms);
+
+/* Host buffers, staged through cached device buffers in pieces of whole rows under the piece budget of the batch
+ * calls (one row is taken whole, however long).  row_off, grp_off and the capacity bound of the whole call are
+ * checked on the host before anything is staged. */
+int64_t shred_exact_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                         const int64_t* grp_off, size_t groups, int64_t* first, uint8_t* dup, uint64_t* print,
+                         int64_t* g_dup_rows, int64_t* g_dup_ids, int64_t* g_in_rows);
+
+/* The exact-dedup state (each pointer may be NULL): the bytes of its table on the device (0 without one), its
+ * capacity, its distinct keys, and seen and groups_seen.  Returns 0, -1 for NULL. */
+int shred_encoder_exact_stats(const ShredEncoder* enc, uint64_t* table_bytes, uint64_t* capacity, uint64_t* distinct,
+                              uint64_t* seen, uint64_t* groups_seen);
+
 /* Largest vocabulary (sum of all token byte lengths) the device decoder holds. */
 #define SHRED_DECODE_MAX_VOCAB_BYTES (1u << 30)
 /* Longest replacement for ids outside the vocabulary. */

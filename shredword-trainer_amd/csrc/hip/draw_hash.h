@@ -1,4 +1,4 @@
-// The seeded draw of the dropout, masked-LM, span-corruption, fill-in-the-middle, MinHash and overlap units:
+// The seeded draw of the dropout, masked-LM, span-corruption, fill-in-the-middle, MinHash, overlap and exact-dedup units:
 //     d(x, c) = mix(mix(seed + G (x + 1)) ^ c)      (mix: murmur3's fmix64, arithmetic mod 2^64)
 // x is a position or a row index, c says which decision of that x is drawn (bits 63..32 of d).
 // Included by .hip files only.
@@ -43,14 +43,16 @@ enum Domain : uint64_t {
   kMhB,               //          addend of permutation x
   kMhBand,            // MinHash: where the hash chain of band x starts
   kNgram,             // n-gram overlap: g(x), what id x adds to a fingerprint
-  kMult               // n-gram overlap: the multiplier of grams of x ids
+  kMult,              // n-gram overlap: the multiplier of grams of x ids (exact dedup: x = 0)
+  kRow,               // exact dedup: what a row of x ids adds to its sum
+  kGroup              // exact dedup: what group x adds to a row's fingerprint
 };
 // (strictly increasing, so pairwise distinct)
 static_assert(kSel >= 1ull << 40 && kAct == kSel + 1 && kStart == kAct + 1 && kLen == kStart + 1 &&
                   kFimC == kLen + 1 && kCutA == kFimC + 1 && kCutB == kCutA + 1 && kMode == kCutB + 1 &&
                   kMhShingle == kMode + 1 && kMhA == kMhShingle + 1 && kMhB == kMhA + 1 && kMhBand == kMhB + 1 &&
-                  kNgram == kMhBand + 1 && kMult == kNgram + 1,
-              "the domain constants are (1 << 40) + 0 .. 13 (include/shredword_encode.h)");
+                  kNgram == kMhBand + 1 && kMult == kNgram + 1 && kRow == kMult + 1 && kGroup == kRow + 1,
+              "the domain constants are (1 << 40) + 0 .. 15 (include/shredword_encode.h)");
 
 // Values of the definition as the tests' Python reference computes it; the second wraps mod 2^64
 // in seed + G (x + 1), the third is a dropout draw (c: a rank).

@@ -954,4 +954,53 @@ int64_t shred_repeat_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const
   return enc->dev->repeat_host(ids, n, row_off, rows, w, seed, o);
 }
 
+namespace {
+// What the two exact calls refuse before any work (0 or -1), and their outputs.
+int exact_args(const ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows, const void* grp_off,
+               size_t groups, void* first, void* dup, void* print, void* g_dup_rows, void* g_dup_ids, void* g_in_rows,
+               shred::EncodeDevice::ExactOut* o) {
+  if (!enc || (n && !ids) || (!row_off && rows) || (!grp_off && groups)) return -1;
+  if (!shred::batch_rows_fit(rows) || !shred::batch_rows_fit(groups)) return -1;
+  if (!grp_off && (g_dup_rows || g_dup_ids || g_in_rows)) return -1;
+  // outputs of no rows hold nothing: an empty tensor's NULL fits
+  if ((row_off ? rows : 1) && !first) return -1;
+  *o = shred::EncodeDevice::ExactOut{(int64_t*)first,      (uint8_t*)dup,       (uint64_t*)print,
+                                     (int64_t*)g_dup_rows, (int64_t*)g_dup_ids, (int64_t*)g_in_rows};
+  return 0;
+}
+}  // namespace
+
+int shred_exact_reset(ShredEncoder* enc, uint64_t capacity, uint64_t seed, int64_t min_len) {
+  return enc ? enc->dev->exact_reset(capacity, seed, min_len) : -1;
+}
+
+int64_t shred_exact_device(ShredEncoder* enc, const void* ids, size_t n, const void* row_off, size_t rows,
+                           const void* grp_off, size_t groups, void* first, void* dup, void* print, void* g_dup_rows,
+                           void* g_dup_ids, void* g_in_rows, void* stream, double* kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  shred::EncodeDevice::ExactOut o;
+  if (exact_args(enc, ids, n, row_off, rows, grp_off, groups, first, dup, print, g_dup_rows, g_dup_ids, g_in_rows, &o))
+    return -1;
+  return enc->dev->exact((const int32_t*)ids, n, (const int64_t*)row_off, rows, (const int64_t*)grp_off, groups, o,
+                         stream, kernel_ms);
+}
+
+int64_t shred_exact_rows(ShredEncoder* enc, const int32_t* ids, size_t n, const int64_t* row_off, size_t rows,
+                         const int64_t* grp_off, size_t groups, int64_t* first, uint8_t* dup, uint64_t* print,
+                         int64_t* g_dup_rows, int64_t* g_dup_ids, int64_t* g_in_rows) {
+  shred::EncodeDevice::ExactOut o;
+  if (exact_args(enc, ids, n, row_off, rows, grp_off, groups, first, dup, print, g_dup_rows, g_dup_ids, g_in_rows, &o))
+    return -1;
+  if (row_off && !offsets_ok(row_off, rows, n)) return -6;
+  if (grp_off && !offsets_ok(grp_off, groups, row_off ? rows : 1)) return -6;
+  return enc->dev->exact_host(ids, n, row_off, rows, grp_off, groups, o);
+}
+
+int shred_encoder_exact_stats(const ShredEncoder* enc, uint64_t* table_bytes, uint64_t* capacity, uint64_t* distinct,
+                              uint64_t* seen, uint64_t* groups_seen) {
+  if (!enc) return -1;
+  enc->dev->exact_stats(table_bytes, capacity, distinct, seen, groups_seen);
+  return 0;
+}
+
 }  // extern "C"

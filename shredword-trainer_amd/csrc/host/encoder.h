@@ -337,6 +337,26 @@ class EncodeDevice {
   int64_t repeat_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, int w, uint64_t seed,
                       const RepeatOut& out);
 
+  // ---- exact dedup of whole rows across calls (batch_exact.hip; shred_exact_*).  exact_reset gives the encoder an
+  // empty table for `capacity` keys (0: frees it) and returns 0 or -1.  The callers of the two calls have checked
+  // the arguments: first given, the group outputs only with grp_off.  exact takes device buffers and returns the
+  // duplicate rows of the call, -1 (also: before a reset, or a call that could overfill the table) or -6; exact_host
+  // takes host buffers whose row_off and grp_off the caller has checked and returns the duplicate rows or -1.
+  struct ExactOut {
+    int64_t* first;
+    uint8_t* dup;        // may be nullptr, as may all below
+    uint64_t* print;
+    int64_t *g_dup_rows, *g_dup_ids, *g_in_rows;
+  };
+  int exact_reset(uint64_t capacity, uint64_t seed, int64_t min_len);
+  int64_t exact(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const int64_t* grp_off, size_t groups,
+                const ExactOut& out, void* stream, double* kernel_ms);
+  int64_t exact_host(const int32_t* ids, size_t n, const int64_t* row_off, size_t rows, const int64_t* grp_off,
+                     size_t groups, const ExactOut& out);
+  // The table's bytes (0 without one), its capacity and distinct keys, and the rows and groups seen since the reset.
+  void exact_stats(uint64_t* table_bytes, uint64_t* capacity, uint64_t* distinct, uint64_t* seen,
+                   uint64_t* groups_seen) const;
+
  private:
   EncodeDevice() = default;
   // The token-length table of the span passes on the device (encode_spans.hip), uploaded when it is
@@ -378,7 +398,7 @@ class EncodeDevice {
   // Everything a pass keeps on the device lives in its state, defined by the unit that runs the
   // pass and created on the pass's first call (kCore: by create()); the destructor destroys them.
   enum Pass { kCore, kStage, kSpans, kSpecial, kDocs, kDecode, kBatch, kWindow, kLong, kDropout, kPair, kMask,
-              kCorrupt, kFim, kMinhash, kDedup, kOverlap, kRepeat, kPasses };
+              kCorrupt, kFim, kMinhash, kDedup, kOverlap, kRepeat, kExact, kPasses };
   std::unique_ptr<PassState> pass_[kPasses];
 };
 

@@ -311,3 +311,14 @@ lib.shred_repeat_device.argtypes = _repeat_rows + [c_void_p, POINTER(c_double)]
 lib.shred_repeat_device.restype = c_int64
 lib.shred_repeat_rows.argtypes = _repeat_rows
 lib.shred_repeat_rows.restype = c_int64
+# exact dedup of whole rows: reset (capacity, seed, min_len); ids, n, row_off, rows, grp_off, groups, first, dup,
+# print, g_dup_rows, g_dup_ids, g_in_rows
+lib.shred_exact_reset.argtypes = [Encoder, c_uint64, c_uint64, c_int64]
+lib.shred_exact_reset.restype = c_int
+_exact_rows = [Encoder, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t] + [c_void_p] * 6
+lib.shred_exact_device.argtypes = _exact_rows + [c_void_p, POINTER(c_double)]
+lib.shred_exact_device.restype = c_int64
+lib.shred_exact_rows.argtypes = _exact_rows
+lib.shred_exact_rows.restype = c_int64
+lib.shred_encoder_exact_stats.argtypes = [Encoder] + [POINTER(c_uint64)] * 5
+lib.shred_encoder_exact_stats.restype = c_int

@@ -1579,6 +1579,109 @@ class BPEEncoder:
         res = self.repeat_device(ids, row, ngram=ngram, seed=seed, token_outputs=token_outputs)
         return tuple(None if t is None else t.cpu().numpy() for t in (ids, row) + res[:8]) + (res[8],)
 
+    # ---- exact dedup of whole rows across calls (include/shredword_encode.h, shred_exact_*) ------
+
+    def exact_reset(self, capacity, *, seed=0, min_len=1):
+        """Gives the encoder an empty table for up to `capacity` distinct fingerprints (16 bytes x the power of two
+        >= 2 x capacity on the GPU; 0 frees it) and sets the row and group counters of exact_rows / exact_device
+        to 0.  Rows shorter than min_len ids are never compared."""
+        capacity, min_len = int(capacity), int(min_len)
+        if capacity < 0 or min_len < 0:
+            raise ValueError("capacity and min_len must not be negative")
+        if lib.shred_exact_reset(self.enc, capacity, int(seed) & (2 ** 64 - 1), min_len) < 0:
+            raise RuntimeError("exact_reset failed (the table does not fit the device?)")
+
+    def exact_rows(self, ids, row_offsets=None, *, group_offsets=None, in_group=False, prints=False):
+        """-> (first, dup, print, g_dup_rows, g_dup_ids, g_in_rows, dups): exact dedup of the rows
+        ids[row_offsets[r]:row_offsets[r + 1]] (None: one row) against each other and against the rows of every
+        call since exact_reset, by a 64-bit fingerprint of the whole row.  first: int64 [rows], the smallest
+        global index (rows are numbered across the calls) of a row with the same fingerprint, the row's own for a
+        first occurrence; dup: bool [rows], first is below the row's own index; print: uint64 [rows] with prints,
+        else None.  With group_offsets (int64 [groups + 1] offsets into the rows, documents of lines), int64
+        [groups] each: a group's duplicate rows, the ids inside them and, with in_group, its rows that repeat an
+        earlier row of the same group; else None.  dups: the duplicate rows of the call.  Built on the GPU."""
+        a, row, R = self._overlap_host(ids, row_offsets)
+        grp = self._exact_groups(group_offsets, in_group, np.ndarray)
+        G = 0 if grp is None else grp.size - 1
+        first, dup = np.empty(R, dtype=np.int64), np.empty(R, dtype=np.uint8)
+        fp = np.empty(R, dtype=np.uint64) if prints else None
+        gout = [None if grp is None or (k == 2 and not in_group) else np.empty(G, dtype=np.int64) for k in range(3)]
+        ptr = lambda x: None if x is None else x.ctypes.data
+        dups = self._check_exact(lib.shred_exact_rows(
+            self.enc, a.ctypes.data, a.size, ptr(row), 0 if row is None else R, ptr(grp), G, first.ctypes.data,
+            dup.ctypes.data, ptr(fp), *(ptr(g) for g in gout)))
+        return (first, dup.view(np.bool_), fp, *gout, dups)
+
+    def exact_device(self, ids, row_offsets=None, *, group_offsets=None, in_group=False, prints=False, stream=None):
+        """exact_rows on device tensors (ids 1-D int32, row_offsets and group_offsets 1-D int64, on the encoder's GPU;
+        views that are only element-aligned fit) -> (first, dup, print, g_dup_rows, g_dup_ids, g_in_rows, dups, device
+        milliseconds of the passes), the arrays as tensors (dup bool, print int64 holding the uint64 patterns)."""
+        import torch
+        R = self._device_rows(ids, row_offsets)
+        grp = self._exact_groups(group_offsets, in_group, torch.Tensor)
+        G = 0 if grp is None else grp.numel() - 1
+        new = lambda count, dt: torch.empty(count, dtype=dt, device=ids.device)
+        first, dup = new(R, torch.int64), new(R, torch.bool)
+        fp = new(R, torch.int64) if prints else None
+        gout = [None if grp is None or (k == 2 and not in_group) else new(G, torch.int64) for k in range(3)]
+        ptr = lambda t: None if t is None else t.data_ptr()
+        ms = ctypes.c_double()
+        st = self._stream(stream, ids.device)
+        dups = self._check_exact(lib.shred_exact_device(
+            self.enc, ids.data_ptr(), ids.numel(), ptr(row_offsets), 0 if row_offsets is None else R, ptr(grp), G,
+            first.data_ptr(), dup.data_ptr(), ptr(fp), *(ptr(g) for g in gout), st, ctypes.byref(ms)))
+        return (first, dup, fp, *gout, dups, ms.value)
+
+    def _exact_groups(self, group_offsets, in_group, kind):
+        """group_offsets of an exact call, checked as row_offsets are: a numpy array or a tensor (`kind`)."""
+        if group_offsets is None:
+            if in_group:
+                raise ValueError("in_group needs group_offsets")
+            return None
+        if kind is np.ndarray:
+            return self._overlap_host(np.empty(0, dtype=np.int32), group_offsets)[1]
+        self._device_rows(None, group_offsets)
+        return group_offsets
+
+    def _check_exact(self, r: int) -> int:
+        if r == -6:
+            raise ValueError("row_offsets must be 0 = row_offsets[0] <= ... <= row_offsets[rows] = len(ids), and "
+                             "group_offsets the same over the rows")
+        if r < 0:
+            raise RuntimeError("exact call failed: no exact_reset yet, the call could pass its capacity "
+                               f"({self.exact_stats()}), or a device error")
+        return r
+
+    def exact_stats(self) -> dict:
+        """The exact-dedup state: table_bytes on the device (0 without a table), its capacity, the distinct
+        fingerprints it holds, and the rows (seen) and groups (groups_seen) of the calls since exact_reset."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        lib.shred_encoder_exact_stats(self.enc, *(ctypes.byref(x) for x in v))
+        return dict(zip(("table_bytes", "capacity", "distinct", "seen", "groups_seen"), (x.value for x in v)))
+
+    def encode_exact(self, texts, *, doc_offsets=None, group_offsets=None, specials: bool = False, in_group=False,
+                     prints=False):
+        """Text to its exact duplicates without the ids leaving the GPU: encode_docs_device, then exact_device on its
+        rows -> (ids, row_offsets) + the seven results of exact_rows, the arrays on the host.  texts: a list / tuple
+        of documents, or one text with doc_offsets (None: one document); line offsets as doc_offsets make the
+        lines the rows, and group_offsets (offsets into those rows) then say which lines form a document."""
+        import torch
+        if isinstance(texts, (list, tuple)):
+            if doc_offsets is not None:
+                raise ValueError("doc_offsets goes with one text, not with a list of documents")
+            buf, off = join_docs(texts)
+        else:
+            buf = self._host_text(texts)
+            off = None if doc_offsets is None else np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        dev = lambda a: torch.from_numpy(np.array(a)).cuda(self.device)
+        ids, row = self.encode_docs_device(dev(buf), None if off is None else dev(off), specials=specials)[:2]
+        grp = None if group_offsets is None else dev(np.ascontiguousarray(group_offsets, dtype=np.int64).reshape(-1))
+        res = self.exact_device(ids, row, group_offsets=grp, in_group=in_group, prints=prints)
+        host = [None if t is None else t.cpu().numpy() for t in (ids, row) + res[:6]]
+        if host[4] is not None:
+            host[4] = host[4].view(np.uint64)
+        return (*host, res[6])
+
     def destroy(self):
         if getattr(self, "enc", None):
             lib.shred_encoder_destroy(self.enc)

@@ -1,5 +1,5 @@
 """Encoder timing on one corpus: python enc_bench.py prepare CORPUS BYTES DIR  (generate + train + save)
-                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup | overlap | repeat] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
+                                   python enc_bench.py run CORPUS DIR [reps] [spans | decode | batch | window | pair | special | docs | long | mlm | corrupt | fim | minhash | dedup | overlap | repeat | exact] [--dropout P [--seed S]]   (SHREDWORD_LIB picks the build)
 With --dropout P (anywhere on the line) the encoder is created with BPE-dropout (P, seed S, default 0): every
 leg then runs the direct dropout kernels, and the first line also reports P, the seed and the ids per byte.
 With a trailing `spans`, run also times encode_spans_device (token starts + line offsets); with a
@@ -66,7 +66,13 @@ results; with a trailing `repeat`, the repeated n-grams inside the same rows at 
 repeat_device without and with the token outputs (median of 7 after two warm-up calls), beside a torch composition
 of the same definition (the fingerprints as in the overlap leg, unique over (row, fingerprint) with inverse and counts,
 scatter reductions) on a prefix of 20,000 rows, where it must give equal results, its time scaled by the id count: an
-extrapolation, printed as one."""
+extrapolation, printed as one; with a trailing `exact`, exact dedup of whole rows on the dedup leg's rows (20 % of them an
+exact copy of a row that stays) and on the same ids cut into lines of 12 ids, the rows as groups, with in_group: the device
+ms of exact_device behind an exact_reset each (median of 7 after two warm-up calls), rows per second, the device ms of the
+same call with min_len above every row (the offset check and the fingerprint passes; nothing is inserted) and its read
+bandwidth at 4 B per id and 16 B per row, beside a torch composition of the same definition on the same tensors, all ids
+(powers of A by a cumprod, index_add for the row sums, unique with a scatter-amin for the first occurrences, index_add for
+the groups), which must give equal results."""
 import os
 import subprocess
 import sys
@@ -110,9 +116,9 @@ else:
     long_leg, pair, corrupt, fim = args[-1] == "long", args[-1] == "pair", args[-1] == "corrupt", args[-1] == "fim"
     dedup = args[-1] == "dedup"
     minhash = dedup or args[-1] == "minhash"  # the dedup leg runs behind the minhash leg, on its rows
-    overlap, repeat = args[-1] == "overlap", args[-1] == "repeat"
-    # the corrupt, fim, minhash, overlap and repeat legs run on the mlm leg's stream, in its place
-    mlm = corrupt or fim or minhash or overlap or repeat or args[-1] == "mlm"
+    overlap, repeat, exact = args[-1] == "overlap", args[-1] == "repeat", args[-1] == "exact"
+    # the corrupt, fim, minhash, overlap, repeat and exact legs run on the mlm leg's stream, in its place
+    mlm = corrupt or fim or minhash or overlap or repeat or exact or args[-1] == "mlm"
     if spans or decode or special or docs or window or long_leg or pair or mlm:
         args = args[:-1]
     d = args[0]
@@ -489,7 +495,7 @@ else:
 
         kw = dict(mask_id=MASK, p=P, seed=1, random_vocab=V, protect=(0, 1, 2, 3))
         legs = (("token", False, 12, torch_token), ("whole-word", True, 44, torch_whole))
-        for name, whole, per_id, ref in () if corrupt or fim or minhash or overlap or repeat else legs:
+        for name, whole, per_id, ref in () if corrupt or fim or minhash or overlap or repeat or exact else legs:
             run = lambda: enc.mlm_device(ids, row, whole_word=whole, starts=starts, **kw)
             run()  # first call: allocates the masking scratch
             run()
@@ -875,4 +881,73 @@ else:
                   "| scaled by the id count (an extrapolation) ms", t[0] * scale, "| scaled torch / ours with token outputs",
                   t[0] * scale / med, flush=True)
             assert same, "repeat_device and the torch composition of the same definition differ"
+    if exact:
+        del starts
+        R, SEED, LINE = row.numel() - 1, 1, 12
+        xdraw = lambda x, c: tmix(tmix(s64(SEED) + s64(0x9E3779B97F4A7C15) * (x + 1)) ^ c)
+        g = torch.Generator().manual_seed(11)
+        dup = torch.randperm(R, generator=g)[:int(0.2 * R)].cuda()            # the rows replaced
+        src = torch.arange(R, device="cuda")
+        rest = torch.ones(R, dtype=torch.bool, device="cuda")
+        rest[dup] = False
+        rest = rest.nonzero().squeeze(1)                                       # by a copy of a row that stays
+        src[dup] = rest[torch.randint(0, rest.numel(), (dup.numel(),), generator=g).cuda()]
+        lens = (row[1:] - row[:-1])[src]
+        d_row = torch.cat([lens.new_zeros(1), lens.cumsum(0)])
+        n = int(d_row[-1].item())                                              # (the copies change the id count a little)
+        col = torch.arange(n, device="cuda") - torch.repeat_interleave(d_row[:-1], lens, output_size=n)
+        d_ids = ids[torch.repeat_interleave(row[:-1][src], lens, output_size=n) + col].contiguous()
+        l_row = torch.cat([(col % LINE == 0).nonzero().squeeze(1), d_row[-1:]])  # lines of 12 ids, a document's last shorter
+        l_grp = torch.searchsorted(l_row, d_row)                              # the documents as groups of lines
+        del col, src, rest
+
+        def torch_exact(t_row, t_grp):
+            """the definition on an empty state -> (first, dup, print, g_dup_rows, g_dup_ids, g_in_rows)"""
+            Rn, ln = t_row.numel() - 1, t_row[1:] - t_row[:-1]
+            A = int(xdraw(torch.tensor([0], device="cuda"), (1 << 40) + 13).item()) | 1
+            pw = torch.cat([ln.new_ones(1), torch.full((int(ln.max().item()),), A, device="cuda")]).cumprod(0)
+            of = torch.repeat_interleave(torch.arange(Rn, device="cuda"), ln, output_size=n)
+            gt = xdraw(d_ids.long() & 0xFFFFFFFF, (1 << 40) + 12) * pw[t_row[1:][of] - 1 - torch.arange(n, device="cuda")]
+            F = tmix(torch.zeros(Rn, dtype=torch.int64, device="cuda").index_add_(0, of, gt) ^ xdraw(ln, (1 << 40) + 14))
+            F = torch.where(F == -1, -2, F)
+            ar = torch.arange(Rn, device="cuda")
+
+            def first_of(key):
+                inv = torch.unique(key, return_inverse=True)[1]
+                return torch.full((int(inv.max().item()) + 1,), Rn, device="cuda").scatter_reduce_(0, inv, ar, "amin")[inv]
+
+            first = torch.where(ln > 0, first_of(F), ar)
+            out = [first, first < ar, F]
+            if t_grp is not None:
+                G = t_grp.numel() - 1
+                of_g = torch.bucketize(ar, t_grp, right=True) - 1
+                F2 = tmix(F ^ xdraw(of_g, (1 << 40) + 15))
+                inn = (ln > 0) & (first_of(torch.where(F2 == -1, -2, F2)) < ar)
+                out += [torch.zeros(G, dtype=torch.int64, device="cuda").index_add_(0, of_g, v)
+                        for v in (out[1].long(), out[1] * ln, inn.long())]
+            return out
+
+        for name, t_row, t_grp, cap in (("documents", d_row, None, 1 << 18), ("lines of %d ids in documents" % LINE, l_row, l_grp, 1 << 24)):
+            Rn, kw = t_row.numel() - 1, dict(group_offsets=t_grp, in_group=t_grp is not None, prints=True)
+
+            def run(min_len=1):
+                enc.exact_reset(cap, seed=SEED, min_len=min_len)
+                return enc.exact_device(d_ids, t_row, **kw)
+
+            run(), run()  # first calls: allocate the scratch and the outputs' pages
+            res = [run() for _ in range(reps)]
+            ms = sorted(r[7] for r in res)
+            fp = sorted(run(1 << 40)[7] for _ in range(reps))
+            med, fmed = ms[len(ms) // 2], fp[len(fp) // 2]
+            t = events(lambda: torch_exact(t_row, t_grp))
+            ref = torch_exact(t_row, t_grp)
+            same = all(torch.equal(a, b) for a, b in zip([x for x in res[0][:6] if x is not None], ref))
+            print("exact:", name, "| ids", n, "rows", Rn, "groups", 0 if t_grp is None else t_grp.numel() - 1, "capacity", cap,
+                  "table bytes", enc.exact_stats()["table_bytes"], "| duplicate rows", res[0][6], "| ms", med, "min", ms[0], "max", ms[-1],
+                  "rows/s", Rn / med * 1e3, "ids/s", n / med * 1e3, "| offset check and fingerprint passes alone (min_len above every row) ms",
+                  fmed, "min", fp[0], "max", fp[-1], "read TB/s at 4 B per id and 16 B per row", (4 * n + 16 * Rn) / fmed / 1e9,
+                  "| torch composition on all ids ms", t[0], "min", t[1], "max", t[2], "| equal to the torch composition", same,
+                  "| torch / ours", t[0] / med, flush=True)
+            assert same, "exact_device and the torch composition of the same definition differ"
+        enc.exact_reset(0)
     enc.destroy()
